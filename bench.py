@@ -9,7 +9,15 @@ already resident in HBM (BASELINE.json configs[1]: batch 256, 512x256).  The pat
 data-path collective, so N ranks each run the full batch: weak scaling, value = all ranks'
 spectrograms / max-over-ranks time.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line; everything else below runs only with --full:
+
+    python bench.py --gpus 1 --steps K --warmup W --full
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (the two U-Nets' outputs; a fixed, seeded sample
+of the batch when the whole would exceed 48 MiB) as DIR/<name>.npy in float32: the inputs and weights are seeded, so two builds
+compare output for output.
+
+Extra objects on the line (--full):
   roofline     dominant kernel family (the MFMA implicit-GEMM conv): algorithmic FLOP / HIP-event time,
                measured inside the timed region on the launch stream.
   cpu_baseline the oracle (oracle/m2h_oracle.py, a PyTorch-CPU restatement of the reference) timed on this
@@ -39,6 +47,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--tm", type=int, default=256, help="time frames (32 = reference-native, 256 = headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: per-kernel roofline pass, the other arithmetic modes and their parity, CPU baselines, the DD-PPO, "
+                         "passive-training and feeder legs, clock probe (the options below shape those)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last timed step as DIR/<name>.npy (float32; seeded batch sample above 48 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -91,6 +104,24 @@ def make_inputs(dev, batch, tm, seed):
     mix = torch.log1p(torch.sqrt(re * re + im * im) * gain).contiguous()
     tc = torch.randint(0, 11, (batch, 1), device=dev, generator=g)
     return mix, tc
+
+
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """outputs: {name: device tensor with the batch first}.  Writes each as out_dir/<name>.npy in float32: whole when all of them fit in
+    DUMP_BUDGET_BYTES, else the same seeded sample of batch rows (sorted) of each.  Returns the batch rows written."""
+    batch = next(iter(outputs.values())).shape[0]
+    per_row = sum(t[0].numel() * 4 for t in outputs.values())
+    rows = torch.arange(batch)
+    if per_row * batch > DUMP_BUDGET_BYTES:
+        k = max(1, DUMP_BUDGET_BYTES // per_row)
+        rows = torch.from_numpy(np.sort(np.random.default_rng(0).choice(batch, size=k, replace=False)))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t[rows.to(t.device)].float().cpu().numpy())
+    return rows.tolist()
 
 
 def cpu_baseline(sd, tm, seconds):
@@ -746,7 +777,7 @@ def main():
         return metas
 
     META = {}
-    for m_ in ((args.math,) if args.no_other_mode else ("bf16x3", "fp32")):
+    for m_ in (() if not args.full else (args.math,) if args.no_other_mode else ("bf16x3", "fp32")):
         lab = stage_labels(m_)
         META[m_] = {"binSep": unet_kernel_meta(32, False, True, lab["binSep"]), "bin2mono": unet_kernel_meta(16, True, False, lab["bin2mono"])}
     ops.set_math_mode(ops.MATH_FP32)
@@ -773,7 +804,7 @@ def main():
     PEAK_BF16 = 2500.0   # dense bf16 MFMA peak, TFLOP/s (MI355X_MICROARCH.md)
 
     def timed_run(mode, steps, warmup, with_events):
-        """W untimed + K timed steps of the pair in the given math mode -> (elapsed s, HIP-event sink or None)."""
+        """W untimed + K timed steps of the pair in the given math mode -> (elapsed s, HIP-event sink or None, last step's outputs)."""
         ops.set_math_mode({"bf16x3": ops.MATH_BF16X3, "bf16": ops.MATH_BF16}.get(mode, ops.MATH_FP32))
         current_mode[0] = mode if mode != "bf16" else "bf16x3"   # (the hi-halves-only mode runs the bf16x3 mode's engines)
         for _ in range(warmup):
@@ -784,11 +815,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        out = None
         for _ in range(steps):
             if with_events:
-                step_events(sink)
+                out = step_events(sink)
             else:
-                step()
+                out = step()
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -797,7 +829,7 @@ def main():
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el, sink
+        return el, sink, out
 
     def account(sink, steps, mode):
         """per-kernel accounting from the HIP events of a timed region -> (roofline dict, per-layer dict)"""
@@ -871,9 +903,13 @@ def main():
     # runs).  Kernel durations for the roofline come from a second pass of the same K steps through the same runner with an
     # event recorded around each of its kernels (m2h_unet_fwd_events): identical kernels, ~24 extra event records per step.
     other = "fp32" if args.math == "bf16x3" else "bf16x3"
-    elapsed, _ = timed_run(args.math, args.steps, args.warmup, False)
+    elapsed, _, last_out = timed_run(args.math, args.steps, args.warmup, False)
+    if args.dump_outputs and rank == 0:
+        # (before any other pass: the graph replays return their static output buffers)
+        dump_outputs(args.dump_outputs, {"pred_binSepMasks": last_out[0], "pred_mono": last_out[1]})
+    del last_out
     roofline, layers, evented_ms = None, None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # the per-kernel pass enqueues kernel by kernel with an event around each: when the host is slow (a busy box) the device idles between
         # the kernels, clocks down, and every duration reads high (seen: 8.4 ms per evented step, kernels +15 %).  Up to three passes; the one
         # whose wall time is closest to the graph replay's is kept, and the number of passes is reported.
@@ -881,7 +917,7 @@ def main():
         # in all, and the first that is not host-bound is taken (none: the fastest, flagged).  Every pass's wall time is in the line.
         passes = []
         for attempt in range(3):
-            passes.append(timed_run(args.math, args.steps, 1, True))
+            passes.append(timed_run(args.math, args.steps, 1, True)[:2])
             if passes[-1][0] <= 1.25 * elapsed:
                 break
         host_bound = passes[-1][0] > 1.25 * elapsed
@@ -903,12 +939,12 @@ def main():
         roofline["achieved_what"] = ("algorithmic GFLOP of one step / ms_per_step of the timed region (HIP-graph replay); achieved_kernel_sum / frac_kernel_sum: "
                                      "the same GFLOP over the sum of the conv kernels' HIP-event durations in the evented pass")
     other_mode, parity, bf16_mode = None, None, None
-    if not args.no_other_mode:
+    if args.full and not args.no_other_mode:
         o_steps = max(2, args.steps // 3)
-        o_elapsed, _ = timed_run(other, o_steps, 1, False)
+        o_elapsed, _, _ = timed_run(other, o_steps, 1, False)
         o_roof = None
         if not args.no_kernel_timing:
-            _e, o_sink = timed_run(other, o_steps, 1, True)
+            _e, o_sink, _ = timed_run(other, o_steps, 1, True)
             o_roof, _ = account(o_sink, o_steps, other)
         ops.set_math_mode(ops.MATH_FP32)
         m_a, mono_a = (t.clone() for t in step())  # (graph replays return their static output buffers)
@@ -926,7 +962,7 @@ def main():
                   "pred_bin": rel(m_b * em, m_a * em), "pred_mono": rel(mono_b, mono_a)}
         # BASELINE config 2's literal dtype, a REPORTED mode (never `value`): one bf16 product per product (the hi halves of the same
         # split32 tensors: include/m2h.h M2H_MATH_BF16), with its distance from the fp32 result and whether that holds the contract
-        b_elapsed, _ = timed_run("bf16", o_steps, 1, False)
+        b_elapsed, _, _ = timed_run("bf16", o_steps, 1, False)
         ops.set_math_mode(ops.MATH_BF16)
         m_c, mono_c = (t.clone() for t in step())
         ops.set_math_mode(ops.MATH_FP32)
@@ -946,12 +982,12 @@ def main():
     ops.set_math_mode(ops.MATH_FP32)
 
     # the host-core baselines are single-GPU-run figures (rank 0, N = 1); the pair's comes first: its probe picks the thread count
-    with_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    with_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu = cpu_baseline(sd, args.tm, args.cpu_seconds) if with_cpu else None
-    ddppo = run_ddppo(args, dev, rank, world, dist, with_cpu=with_cpu) if args.ddppo_cycles > 0 else None
-    ddppo_far = run_ddppo(args, dev, rank, world, dist, far_target=True) if (args.ddppo_cycles > 0 and not args.no_far_target) else None
-    ptrain = run_passive_train(args, dev, rank, with_cpu=with_cpu) if args.train_steps > 0 else None
-    feeder = run_feeder(args, dev, rank, with_cpu=with_cpu) if args.feeder_steps > 0 else None
+    ddppo = run_ddppo(args, dev, rank, world, dist, with_cpu=with_cpu) if (args.full and args.ddppo_cycles > 0) else None
+    ddppo_far = run_ddppo(args, dev, rank, world, dist, far_target=True) if (args.full and args.ddppo_cycles > 0 and not args.no_far_target) else None
+    ptrain = run_passive_train(args, dev, rank, with_cpu=with_cpu) if (args.full and args.train_steps > 0) else None
+    feeder = run_feeder(args, dev, rank, with_cpu=with_cpu) if (args.full and args.feeder_steps > 0) else None
 
     if rank != 0:
         if dist is not None:

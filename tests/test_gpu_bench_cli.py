@@ -15,7 +15,7 @@ def test_bench_gpus_2_spawns_two_ranks_and_reports_them():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(M2H_BENCH_DEVICE="0", M2H_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--tm", "32",
-           "--ddppo-cycles", "1", "--no-far-target", "--train-steps", "0", "--feeder-steps", "0", "--no-cpu-baseline"]
+           "--ddppo-cycles", "1", "--no-far-target", "--train-steps", "0", "--feeder-steps", "0", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -46,3 +46,29 @@ def test_bench_refuses_a_rank_count_that_disagrees_with_gpus():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "process group has 1 rank" in r.stderr
+
+
+def _plain_run(out_dir, steps):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--batch", "8", "--tm", "32",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    import numpy as np
+    line = _plain_run(tmp_path / "a", 3)
+    assert line["metric"] == "passive_unet_pair_spectrograms_per_sec" and line["unit"] == "spectrograms/s" and line["higher_is_better"] is True
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"].startswith("bf16x3")
+    for leg in ("roofline", "ddppo", "ddppo_far_target", "passive_train", "feeder", "cpu_baseline", "math_mode_parity"):
+        assert line[leg] is None, leg   # (those are --full's)
+    out = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("pred_binSepMasks", "pred_mono")}
+    assert out["pred_binSepMasks"].shape == (8, 512, 32, 2) and out["pred_mono"].shape == (8, 512, 32, 1)
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() and np.abs(v).sum() > 0 for v in out.values())
+    # same arguments but the step count: the same seeded inputs and weights, so the same outputs
+    _plain_run(tmp_path / "b", 2)
+    for n, v in out.items():
+        np.testing.assert_allclose(np.load(tmp_path / "b" / (n + ".npy")), v, rtol=1e-5, atol=1e-6)

@@ -1,12 +1,13 @@
 # one kernel trace of a DD-PPO cycle; prints, in launch order, the kernels of one replayed rollout step, one update_pol epoch
 # and one update_sep epoch (name, duration, gap to the previous kernel).  usage: gpurun -- 'bash tools/cycle_nodes.sh [tag]'
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
+export OUT=${OUT:-prof_out}; mkdir -p $OUT   # (where this script writes)
 TAG=${1:-nodes}
-rm -rf gpurun_out/prof_nodes
-rocprofv3 --kernel-trace -d gpurun_out/prof_nodes -o g --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-timing --ddppo-cycles 1 --no-far-target --train-steps 0 --feeder-steps 0 > gpurun_out/${TAG}_log.txt 2>&1
-python3 - > gpurun_out/${TAG}.txt <<'P'
-import csv, glob
-f = glob.glob("gpurun_out/prof_nodes/*kernel_trace.csv")[0]
+rm -rf $OUT/prof_nodes
+rocprofv3 --kernel-trace -d $OUT/prof_nodes -o g --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-timing --ddppo-cycles 1 --no-far-target --train-steps 0 --feeder-steps 0 > $OUT/${TAG}_log.txt 2>&1
+python3 - > $OUT/${TAG}.txt <<'P'
+import csv, glob, os
+f = glob.glob(os.environ["OUT"] + "/prof_nodes/*kernel_trace.csv")[0]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 names = [r["Kernel_Name"].split("(")[0].replace("void m2h::", "").replace("m2h::", "").replace("void at::native::", "at::")[:70] for r in rows]
@@ -41,5 +42,5 @@ show("one update_pol epoch (between two ppo_loss launches)", idx[-3], idx[-2])
 idx = [i for i, n in enumerate(names) if (n.startswith("l1_nhwc16") or n.startswith("l1_loss_kernel"))]
 show("one update_sep epoch (between two l1_loss launches)", idx[-3], idx[-2])
 P
-rm -rf gpurun_out/prof_nodes
-tail -3 gpurun_out/${TAG}.txt
+rm -rf $OUT/prof_nodes
+tail -3 $OUT/${TAG}.txt
