@@ -602,6 +602,31 @@ int m2h_stft_post(const float* spec, float* mag_out, float* phase_out, int B, in
 int m2h_istft_pre(const float* mag, const float* phase, float* rows, int B, int C, int c, int T, int nb, int ldr, m2h_stream stream);
 int m2h_istft_ola(const float* frames, const float* window, float* y, int S, int T, int n_fft, int hop, int ldf, int length, m2h_stream stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Separation of long recordings (m2h/separate.py, csrc/separate.hip): the glue around the same two DFT GEMMs for a binaural
+ * recording wave [R][2][L] cut into S = ceil(L / 16000) one-second segments (samples at or past L are zero), each transformed
+ * on its own: forward n_fft 1023 / hop 512 / 32 frames with the reflect padding taken inside the zero-padded segment, inverse
+ * n_fft 1022 / length 16000.  A call handles the chunk of segments [s0, s0 + nseg); its batch rows are segment-major,
+ * n = (s - s0) * R + r, N = nseg * R.  GEMM rows are 1024 floats.  All buffers except wave and y must be 16-byte aligned.
+ * ------------------------------------------------------------------------------------------------------------------ */
+
+/* frames [(n*2 + c)*32 + t][1024] = window[i] * segment[t*512 + i - 511] (np.pad "reflect" indexing inside the segment) for
+ * i < 1023, 0 at i = 1023.  window: 1024 floats, periodic Hann(1023) followed by one zero. */
+int m2h_sep_frames(const float* wave, const float* window, float* frames, int R, long long L, int s0, int nseg, m2h_stream stream);
+
+/* spec [(n*2 + c)*32 + t][1024] = [Re | Im] (the GEMM's output)  ->  mag BHWC [N][512][32][2] = log1p|X_c| and the unit phasor
+ * of the downmix D = X_0 + X_1, phasor [N][512][32][2] = (Re, Im) of D / |D|, exactly (1, 0) where |D| == 0. */
+int m2h_sep_stft_post(const float* spec, float* mag, float* phasor, int N, m2h_stream stream);
+
+/* P [N][512][32][1] (a log1p magnitude), phasor as above  ->  rows [n*32 + t][1024]: [k] = expm1(max(P, 0)) * Re,
+ * [512 + k] = expm1(max(P, 0)) * Im. */
+int m2h_sep_istft_pre(const float* P, const float* phasor, float* rows, int N, m2h_stream stream);
+
+/* frames [n*32 + t][1024] (the inverse GEMM's output, 1022 samples per row), window: periodic Hann(1022)  ->  windowed
+ * overlap-add with window-sum-of-squares normalisation (m2h_istft_ola's arithmetic), segment s written to
+ * y[r][s*16000 .. ) of y [R][L] and cut at L. */
+int m2h_sep_istft_ola(const float* frames, const float* window, float* y, int R, long long L, int s0, int nseg, m2h_stream stream);
+
 /* RIR-convolution feeder glue (pretrain/datasets/dataset.py:178-186,214-216; habitat_audio/simulator_train.py:416-424).
  * m2h_feeder_round_mix: takes the "same"-mode window [start, start+L) of S full linear convolutions (rows of ldfull floats),
  * applies np.round -> int16 -> float32 / 32768, optionally stores it (conv_out [S][L], NULL to skip) and accumulates it into

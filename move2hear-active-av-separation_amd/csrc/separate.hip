@@ -1,0 +1,246 @@
+// Waveform-to-waveform separation of long binaural recordings (m2h/separate.py): the HBM-bound glue around the two DFT GEMMs
+// (gfx950, fp32, wave64, 16-byte stores, no atomics).
+//
+// A recording [R][2][L] is cut into S = ceil(L / 16000) one-second segments (the agent's steps; samples at or past L are zero).
+// Every segment is transformed on its own with the feeder's semantics (csrc/stft.hip: n_fft 1023, hop 512, periodic Hann,
+// centred, reflect padding 511 taken INSIDE the zero-padded segment, 32 frames), goes through the separator networks as one
+// batch row, and comes back through the evaluation path's inverse transform (n_fft 1022, length 16000) with the phase of the
+// downmix spectrum D = X_left + X_right, carried as the unit phasor D / |D| ((1, 0) where |D| == 0, which is np.angle(0) = 0).
+//
+// Batch rows are segment-major: row n = sl * R + r for the chunk's local segment sl = s - s0, so that step s of the acoustic
+// memory's recurrence is a contiguous batch of R rows.  Fixed geometry below; the entry points check what they are given.
+#include "m2h_internal.h"
+
+namespace m2h {
+
+constexpr int SEP_SEG = 16000;    // samples per segment
+constexpr int SEP_T = 32;         // frames per segment
+constexpr int SEP_NB = 512;       // bins
+constexpr int SEP_LD = 1024;      // GEMM row length (K and N of both DFT matrices)
+constexpr int SEP_NFFT = 1023;    // forward transform
+constexpr int SEP_NIFFT = 1022;   // inverse transform (2 * (bins - 1))
+constexpr int SEP_HOP = 512;
+constexpr int SEP_KT = 32;        // bins per workgroup of the two transposing kernels
+
+// frames[((sl*R + r)*2 + c)*32 + t][n] = window[n] * seg[t*512 + n - 511] (reflected inside the segment), n < 1023; 0 at n = 1023.
+// seg[j] = wave[r][c][(s0 + sl)*16000 + j] below L, 0 from L on.  One thread = four consecutive n = one 16-byte store; the source
+// offsets are odd by construction (n - 511), so the reads are scalar and coalesced across the wave.
+__global__ __launch_bounds__(256) void sep_frames_kernel(const float* __restrict__ wave, const float* __restrict__ window /* [1024], [1023] = 0 */,
+                                                         float* __restrict__ frames, int R, long long L, int s0, int nseg) {
+  const size_t total = (size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int n0 = (int)(i % (SEP_LD / 4)) * 4;
+    size_t row = i / (SEP_LD / 4);
+    const int t = (int)(row % SEP_T);
+    const size_t sig = row / SEP_T;            // (sl*R + r)*2 + c
+    const int c = (int)(sig & 1);
+    const size_t nrow = sig >> 1;
+    const int r = (int)(nrow % R);
+    const int sl = (int)(nrow / R);
+    const long long base = (long long)(s0 + sl) * SEP_SEG;
+    const float* src = wave + ((size_t)r * 2 + c) * (size_t)L;
+    const float4 w = *reinterpret_cast<const float4*>(window + n0);
+    const float wv[4] = {w.x, w.y, w.z, w.w};
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int n = n0 + e;
+      float x = 0.f;
+      if (n < SEP_NFFT) {
+        int j = t * SEP_HOP + n - SEP_NFFT / 2;             // in [-511, 16383]
+        if (j < 0) j = -j;                                  // np.pad(mode="reflect"): edge sample not repeated
+        if (j >= SEP_SEG) j = 2 * (SEP_SEG - 1) - j;
+        const long long g = base + j;
+        if (g < L) x = wv[e] * src[g];
+      }
+      v[e] = x;
+    }
+    *reinterpret_cast<float4*>(frames + row * SEP_LD + n0) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// spec rows [(n*2 + c)*32 + t][1024] = [Re(512) | Im(512)]  ->  mag [n][512][32][2] = log1p|X_c|, phasor [n][512][32][2] = D / |D|
+// (re, im), D = X_0 + X_1.  A transpose (rows are k-major, the outputs t-major): one workgroup stages the 64 rows x 32 bins of
+// one batch row through LDS with 16-byte loads, and writes 8 KB of each output contiguously with 16-byte stores.
+__global__ __launch_bounds__(256) void sep_stft_post_kernel(const float* __restrict__ spec, float* __restrict__ mag, float* __restrict__ phasor, int N) {
+  __shared__ __align__(16) float tile[2 * SEP_T][2 * SEP_KT + 4];        // [c*32 + t][part*32 + kk]; row stride 68 floats keeps 16-byte alignment
+  const int ktiles = SEP_NB / SEP_KT;
+  const int n = blockIdx.x / ktiles;
+  const int k0 = (blockIdx.x % ktiles) * SEP_KT;
+  if (n >= N) return;
+  const float* base = spec + (size_t)n * 2 * SEP_T * SEP_LD;
+  // 64 rows x 2 parts x 8 float4 = 1024 loads
+  for (int q = threadIdx.x; q < 2 * SEP_T * 2 * (SEP_KT / 4); q += 256) {
+    const int v4 = q % (SEP_KT / 4);
+    const int part = (q / (SEP_KT / 4)) & 1;
+    const int row = q / (2 * (SEP_KT / 4));
+    const float4 x = *reinterpret_cast<const float4*>(base + (size_t)row * SEP_LD + part * SEP_NB + k0 + v4 * 4);
+    *reinterpret_cast<float4*>(&tile[row][part * SEP_KT + v4 * 4]) = x;
+  }
+  __syncthreads();
+  // 32 bins x 16 frame pairs: each item = (k, t0, t0 + 1) x both channels = one float4 of each output
+  for (int q = threadIdx.x; q < SEP_KT * (SEP_T / 2); q += 256) {
+    const int tp = q % (SEP_T / 2);
+    const int kk = q / (SEP_T / 2);
+    float m[4], ph[4];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int t = 2 * tp + e;
+      const float re0 = tile[t][kk], im0 = tile[t][SEP_KT + kk];
+      const float re1 = tile[SEP_T + t][kk], im1 = tile[SEP_T + t][SEP_KT + kk];
+      m[2 * e] = log1pf(sqrtf(re0 * re0 + im0 * im0));
+      m[2 * e + 1] = log1pf(sqrtf(re1 * re1 + im1 * im1));
+      float dr = re0 + re1, di = im0 + im1;
+      const float big = fmaxf(fabsf(dr), fabsf(di));
+      if (big == 0.f) {                                     // np.angle(0) = 0
+        dr = 1.f;
+        di = 0.f;
+      } else {
+        dr /= big;                                          // |D|^2 neither overflows nor flushes to zero
+        di /= big;
+        const float inv = 1.f / sqrtf(dr * dr + di * di);
+        dr *= inv;
+        di *= inv;
+      }
+      ph[2 * e] = dr;
+      ph[2 * e + 1] = di;
+    }
+    const size_t o = (((size_t)n * SEP_NB + k0 + kk) * SEP_T + 2 * tp) * 2;
+    *reinterpret_cast<float4*>(mag + o) = make_float4(m[0], m[1], m[2], m[3]);
+    *reinterpret_cast<float4*>(phasor + o) = make_float4(ph[0], ph[1], ph[2], ph[3]);
+  }
+}
+
+// P [n][512][32][1] (log1p magnitude from the networks), phasor [n][512][32][2]  ->  rows [n*32 + t][1024]:
+// [k] = expm1(max(P, 0)) * re, [512 + k] = expm1(max(P, 0)) * im.  The transpose of the kernel above, again through LDS.
+__global__ __launch_bounds__(256) void sep_istft_pre_kernel(const float* __restrict__ P, const float* __restrict__ phasor, float* __restrict__ rows, int N) {
+  __shared__ float tile[2][SEP_KT][SEP_T + 1];              // [part][kk][t]
+  const int ktiles = SEP_NB / SEP_KT;
+  const int n = blockIdx.x / ktiles;
+  const int k0 = (blockIdx.x % ktiles) * SEP_KT;
+  if (n >= N) return;
+  {
+    // 32 bins x 32 frames, contiguous in both inputs: one float4 of P and two of the phasor per thread
+    const int q = threadIdx.x;                              // 256 x 4 = 1024 elements
+    const size_t e0 = ((size_t)n * SEP_NB + k0) * SEP_T + (size_t)q * 4;
+    const float4 p = *reinterpret_cast<const float4*>(P + e0);
+    const float4 a = *reinterpret_cast<const float4*>(phasor + e0 * 2);
+    const float4 b = *reinterpret_cast<const float4*>(phasor + e0 * 2 + 4);
+    const float pv[4] = {p.x, p.y, p.z, p.w};
+    const float re[4] = {a.x, a.z, b.x, b.z}, im[4] = {a.y, a.w, b.y, b.w};
+    const int kk = (q * 4) / SEP_T, t0 = (q * 4) % SEP_T;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float m = expm1f(fmaxf(pv[e], 0.f));
+      tile[0][kk][t0 + e] = m * re[e];
+      tile[1][kk][t0 + e] = m * im[e];
+    }
+  }
+  __syncthreads();
+  // 32 frames x 2 parts x 8 float4 = 512 stores
+  for (int q = threadIdx.x; q < SEP_T * 2 * (SEP_KT / 4); q += 256) {
+    const int v4 = q % (SEP_KT / 4);
+    const int part = (q / (SEP_KT / 4)) & 1;
+    const int t = q / (2 * (SEP_KT / 4));
+    const float4 x = make_float4(tile[part][v4 * 4][t], tile[part][v4 * 4 + 1][t], tile[part][v4 * 4 + 2][t], tile[part][v4 * 4 + 3][t]);
+    *reinterpret_cast<float4*>(rows + ((size_t)n * SEP_T + t) * SEP_LD + part * SEP_NB + k0 + v4 * 4) = x;
+  }
+}
+
+// Windowed overlap-add as a gather (istft_ola_kernel's arithmetic), every segment written at its offset of y [R][L] and cut at L:
+// y[r][(s0 + sl)*16000 + j] = (sum_t frames[(sl*R + r)*32 + t][jj - 512 t] * window[jj - 512 t]) / wss(jj), jj = j + 511.
+// One thread = four consecutive j: one 16-byte store where the destination is aligned (always when L % 4 == 0) and inside L.
+__global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                            float* __restrict__ y, int R, long long L, int s0, int nseg) {
+  const size_t total = (size_t)nseg * R * (SEP_SEG / 4);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int j0 = (int)(i % (SEP_SEG / 4)) * 4;
+    const size_t nrow = i / (SEP_SEG / 4);                  // sl*R + r
+    const int r = (int)(nrow % R);
+    const int sl = (int)(nrow / R);
+    const long long g0 = (long long)(s0 + sl) * SEP_SEG + j0;
+    if (g0 >= L) continue;
+    const float* fr = frames + nrow * SEP_T * SEP_LD;
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int jj = j0 + e + SEP_NIFFT / 2;
+      float acc = 0.f, wss = 0.f;
+      int t1 = jj / SEP_HOP;
+      if (t1 > SEP_T - 1) t1 = SEP_T - 1;
+      for (int t = t1; t >= 0; --t) {
+        const int n = jj - t * SEP_HOP;
+        if (n >= SEP_NIFFT) break;
+        const float w = window[n];
+        acc += fr[(size_t)t * SEP_LD + n] * w;
+        wss += w * w;
+      }
+      v[e] = wss > 1.1754944e-38f ? acc / wss : acc;
+    }
+    float* dst = y + (size_t)r * (size_t)L + g0;
+    if (g0 + 4 <= L && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+      *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (g0 + e < L) dst[e] = v[e];
+    }
+  }
+}
+
+static inline unsigned sep_grid(size_t total) {
+  size_t g = (total + 255) / 256;
+  if (g > 16384) g = 16384;
+  if (g < 1) g = 1;
+  return (unsigned)g;
+}
+
+// chunk [s0, s0 + nseg) of a recording of L samples: inside its ceil(L / 16000) segments, batch rows within int range
+static inline bool sep_chunk_ok(int R, long long L, int s0, int nseg) {
+  if (R <= 0 || L <= 0 || s0 < 0 || nseg <= 0) return false;
+  const long long S = (L + SEP_SEG - 1) / SEP_SEG;
+  if ((long long)s0 + nseg > S) return false;
+  return (long long)nseg * R <= (1 << 20);
+}
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace m2h
+
+using namespace m2h;
+
+extern "C" {
+
+int m2h_sep_frames(const float* wave, const float* window, float* frames, int R, long long L, int s0, int nseg, m2h_stream stream) {
+  M2H_REQUIRE(wave && window && frames, "sep_frames: null pointer");
+  M2H_REQUIRE(sep_chunk_ok(R, L, s0, nseg), "sep_frames: bad sizes (R %d, L %lld, segments [%d, %d + %d))", R, L, s0, s0, nseg);
+  M2H_REQUIRE(aligned16(window) && aligned16(frames), "sep_frames: window / frames must be 16-byte aligned");
+  M2H_LAUNCH(sep_frames_kernel, dim3(sep_grid((size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4))), dim3(256), 0, as_stream(stream), wave, window, frames, R, L,
+             s0, nseg);
+  return launch_status("sep_frames");
+}
+
+int m2h_sep_stft_post(const float* spec, float* mag, float* phasor, int N, m2h_stream stream) {
+  M2H_REQUIRE(spec && mag && phasor, "sep_stft_post: null pointer");
+  M2H_REQUIRE(N > 0 && N <= (1 << 20), "sep_stft_post: bad sizes (N %d)", N);
+  M2H_REQUIRE(aligned16(spec) && aligned16(mag) && aligned16(phasor), "sep_stft_post: buffers must be 16-byte aligned");
+  M2H_LAUNCH(sep_stft_post_kernel, dim3((unsigned)N * (SEP_NB / SEP_KT)), dim3(256), 0, as_stream(stream), spec, mag, phasor, N);
+  return launch_status("sep_stft_post");
+}
+
+int m2h_sep_istft_pre(const float* P, const float* phasor, float* rows, int N, m2h_stream stream) {
+  M2H_REQUIRE(P && phasor && rows, "sep_istft_pre: null pointer");
+  M2H_REQUIRE(N > 0 && N <= (1 << 20), "sep_istft_pre: bad sizes (N %d)", N);
+  M2H_REQUIRE(aligned16(P) && aligned16(phasor) && aligned16(rows), "sep_istft_pre: buffers must be 16-byte aligned");
+  M2H_LAUNCH(sep_istft_pre_kernel, dim3((unsigned)N * (SEP_NB / SEP_KT)), dim3(256), 0, as_stream(stream), P, phasor, rows, N);
+  return launch_status("sep_istft_pre");
+}
+
+int m2h_sep_istft_ola(const float* frames, const float* window, float* y, int R, long long L, int s0, int nseg, m2h_stream stream) {
+  M2H_REQUIRE(frames && window && y, "sep_istft_ola: null pointer");
+  M2H_REQUIRE(sep_chunk_ok(R, L, s0, nseg), "sep_istft_ola: bad sizes (R %d, L %lld, segments [%d, %d + %d))", R, L, s0, s0, nseg);
+  M2H_LAUNCH(sep_istft_ola_kernel, dim3(sep_grid((size_t)nseg * R * (SEP_SEG / 4))), dim3(256), 0, as_stream(stream), frames, window, y, R, L, s0, nseg);
+  return launch_status("sep_istft_ola");
+}
+
+}  // extern "C"

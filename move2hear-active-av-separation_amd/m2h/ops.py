@@ -1055,3 +1055,86 @@ def acoustic_mem_small(pred_mono, prev_mem, not_done, w0p, w1p):
         _lib.check(_lib.load().m2h_acoustic_mem_small_fwd(_ptr(pred_mono), _ptr(prev_mem), _ptr(not_done), _ptr(w0p), _ptr(w1p), _ptr(out),
                                                           B, F, T, _stream(pred_mono)), "m2h_acoustic_mem_small_fwd")
     return out
+
+
+# ---- separation of long recordings (csrc/separate.hip; driven by m2h/separate.py) ----
+SEP_SEGMENT, SEP_FRAMES, SEP_BINS, SEP_LD = 16000, 32, 512, 1024
+
+
+def _sep_chunk(name, R, L, s0, nseg):
+    S = -(-L // SEP_SEGMENT)
+    if R < 1 or L < 1 or s0 < 0 or nseg < 1 or s0 + nseg > S:
+        raise RuntimeError("m2h.%s: segments [%d, %d) do not lie inside a [%d, 2, %d] recording of %d segments" % (name, s0, s0 + nseg, R, L, S))
+
+
+def sep_frames(wave, window, s0, nseg, out=None):
+    """wave [R,2,L] -> the forward DFT GEMM's rows [nseg*R*2*32, 1024] for segments [s0, s0+nseg), framed and windowed straight from
+    the recording (segment-local reflect index, zeros past L; m2h_sep_frames).  window: [1024] = periodic Hann(1023) + one zero."""
+    _chk(wave, "sep_frames(wave)")
+    _chk(window, "sep_frames(window)")
+    if wave.dim() != 3 or wave.shape[1] != 2:
+        raise RuntimeError("m2h.sep_frames: expected a [R, 2, L] recording, got %s" % (tuple(wave.shape),))
+    if window.numel() != SEP_LD:
+        raise RuntimeError("m2h.sep_frames: window must hold %d floats, got %d" % (SEP_LD, window.numel()))
+    R, _, L = wave.shape
+    _sep_chunk("sep_frames", R, L, s0, nseg)
+    rows = nseg * R * 2 * SEP_FRAMES
+    if out is None:
+        out = torch.empty((rows, SEP_LD), device=wave.device, dtype=torch.float32)
+    else:
+        _chk(out, "sep_frames(out)")
+        if tuple(out.shape) != (rows, SEP_LD):
+            raise RuntimeError("m2h.sep_frames: out must be [%d, %d], got %s" % (rows, SEP_LD, tuple(out.shape)))
+    with torch.cuda.device(wave.device):
+        _lib.check(_lib.load().m2h_sep_frames(_ptr(wave), _ptr(window), _ptr(out), R, L, s0, nseg, _stream(wave)), "m2h_sep_frames")
+    return out
+
+
+def sep_stft_post(spec, N):
+    """The forward GEMM's [Re | Im] rows [N*2*32, 1024] -> (log1p magnitudes BHWC [N,512,32,2], downmix unit phasor [N,512,32,2]
+    (re, im), exactly (1, 0) where the downmix bin is zero)  (m2h_sep_stft_post)."""
+    _chk(spec, "sep_stft_post(spec)")
+    if tuple(spec.shape) != (N * 2 * SEP_FRAMES, SEP_LD):
+        raise RuntimeError("m2h.sep_stft_post: expected spec [%d, %d], got %s" % (N * 2 * SEP_FRAMES, SEP_LD, tuple(spec.shape)))
+    mag = torch.empty((N, SEP_BINS, SEP_FRAMES, 2), device=spec.device, dtype=torch.float32)
+    phasor = torch.empty_like(mag)
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().m2h_sep_stft_post(_ptr(spec), _ptr(mag), _ptr(phasor), N, _stream(spec)), "m2h_sep_stft_post")
+    return mag, phasor
+
+
+def sep_istft_pre(P, phasor, out=None):
+    """P [N,512,32,1] (log1p magnitude), phasor [N,512,32,2] -> the inverse DFT GEMM's rows [N*32, 1024] =
+    expm1(max(P, 0)) * (re | im)  (m2h_sep_istft_pre)."""
+    _chk(P, "sep_istft_pre(P)")
+    _chk(phasor, "sep_istft_pre(phasor)")
+    N = P.shape[0]
+    if tuple(P.shape) != (N, SEP_BINS, SEP_FRAMES, 1) or tuple(phasor.shape) != (N, SEP_BINS, SEP_FRAMES, 2):
+        raise RuntimeError("m2h.sep_istft_pre: expected P [N,512,32,1] and phasor [N,512,32,2], got %s and %s" % (tuple(P.shape), tuple(phasor.shape)))
+    if out is None:
+        out = torch.empty((N * SEP_FRAMES, SEP_LD), device=P.device, dtype=torch.float32)
+    else:
+        _chk(out, "sep_istft_pre(out)")
+        if tuple(out.shape) != (N * SEP_FRAMES, SEP_LD):
+            raise RuntimeError("m2h.sep_istft_pre: out must be [%d, %d], got %s" % (N * SEP_FRAMES, SEP_LD, tuple(out.shape)))
+    with torch.cuda.device(P.device):
+        _lib.check(_lib.load().m2h_sep_istft_pre(_ptr(P), _ptr(phasor), _ptr(out), N, _stream(P)), "m2h_sep_istft_pre")
+    return out
+
+
+def sep_istft_ola(frames, window, y, s0, nseg):
+    """The inverse GEMM's rows [nseg*R*32, 1024] -> windowed overlap-add of segments [s0, s0+nseg) written at their offsets of
+    y [R, L], cut at L (m2h_sep_istft_ola).  window: periodic Hann(1022)."""
+    _chk(frames, "sep_istft_ola(frames)")
+    _chk(window, "sep_istft_ola(window)")
+    _chk(y, "sep_istft_ola(y)")
+    if y.dim() != 2:
+        raise RuntimeError("m2h.sep_istft_ola: y must be [R, L], got %s" % (tuple(y.shape),))
+    R, L = y.shape
+    _sep_chunk("sep_istft_ola", R, L, s0, nseg)
+    if tuple(frames.shape) != (nseg * R * SEP_FRAMES, SEP_LD) or window.numel() < 1022:
+        raise RuntimeError("m2h.sep_istft_ola: expected frames [%d, %d] and a 1022-point window, got %s and %d points"
+                           % (nseg * R * SEP_FRAMES, SEP_LD, tuple(frames.shape), window.numel()))
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().m2h_sep_istft_ola(_ptr(frames), _ptr(window), _ptr(y), R, L, s0, nseg, _stream(y)), "m2h_sep_istft_ola")
+    return y

@@ -1,0 +1,186 @@
+"""Separation of binaural recordings of any length: waveform in, the target class's waveform out.
+
+    sep = Separator("ckpt.pth", torch.device("cuda", 0))
+    mono = sep.separate(wave, target_class)          # wave [R, 2, L] (or [2, L]) fp32 at 16 kHz  ->  [R, L]
+
+Semantics (the CPU statement of the same thing is tests/separate_ref.py):
+  * the recording is cut into S = ceil(L / 16000) non-overlapping one-second segments -- the agent's steps; samples at or past L are zero;
+  * every segment is transformed on its own with the feeder's STFT (m2h.audio.stft.STFT, mode 1: n_fft 1023, hop 512, periodic
+    Hann, centred, the reflect padding of 511 taken inside the zero-padded segment): 32 frames, log1p|X|, [512, 32, 2];
+  * the output phase is the phase of the downmix spectrum D = X_left + X_right, kept as the unit phasor D / |D| and as (1, 0) where
+    |D| == 0 (np.angle(0) = 0) -- at inference there is no ground-truth phase to borrow, as PPOTrainer.eval() does;
+  * get_binSepMasks -> convert_bin2mono give pred_mono; with the acoustic memory P_0 = mem(pred_mono_0, 0) and
+    P_s = mem(pred_mono_s, P_{s-1}) (eval()'s recurrence without an episode boundary), without it P_s = pred_mono_s;
+  * the networks work on log1p magnitudes: the inverse transform gets expm1(max(P, 0)) times the phasor, then the evaluation
+    path's iSTFT (n_fft 1022 inferred from 512 bins, length 16000); the segments are concatenated and cut at L.
+Overlapping or cross-faded segments and resampling are not part of this.
+
+The two DFTs are dense 1024 x 1024 GEMMs (ops.linear) and follow the calling thread's arithmetic like the U-Nets; framing, the
+magnitude / phasor store, the inverse transform's operand and the overlap-add are the HIP kernels of csrc/separate.hip, which
+read the recording and write the output in place: no padded, framed or angle copies.
+"""
+import numpy as np
+import torch
+
+from . import ops
+
+SEGMENT = ops.SEP_SEGMENT
+SEPARATOR_ROOTS = ("binSep_enc.", "binSep_dec.", "bin2mono_enc.", "bin2mono_dec.")
+MEMORY_ROOT = "acoustic_mem."
+# rows of a U-Net batch.  Measured on 16 recordings of 600 s in bf16x3 (tools/separate_bench.py): 64 rows 89 K, 256 rows 203 K, 1024 rows
+# 282 K seconds of audio per second -- below a few hundred rows of 512 x 32 the U-Nets' 22 launches are bound by their boundaries.
+# 1024 rows hold 0.5 GB of transform buffers and half the activations of the benchmark's batch (256 spectrograms of 512 x 256).
+DEFAULT_MAX_SEGMENTS = 1024
+
+
+def segment_plan(L, max_segments):
+    """The chunks a recording of L samples is processed in: a list of (first_segment, n_segments) covering its ceil(L / 16000)
+    one-second segments in order, each of at most max_segments segments.  Pure Python."""
+    L, max_segments = int(L), int(max_segments)
+    if L < 1:
+        raise ValueError("segment_plan: a recording needs at least one sample, got L = %d" % L)
+    if max_segments < 1:
+        raise ValueError("segment_plan: max_segments must be at least 1, got %d" % max_segments)
+    S = -(-L // SEGMENT)
+    return [(s0, min(max_segments, S - s0)) for s0 in range(0, S, max_segments)]
+
+
+def split_checkpoint(ckpt):
+    """(separator state dict, memory state dict or None, memory variant or None) of any accepted checkpoint form: a passive
+    checkpoint (the 124 separator entries) or a PPO checkpoint, as a {"state_dict", "config"} file's dict or a bare state dict,
+    with or without the "actor_critic." root.  The memory variant is "ddppo" (cnn.0, cnn.2) or "bn" (cnn.0, cnn.1.*, cnn.3).
+    Values stay what they were (tensors or arrays); works without a GPU."""
+    if not isinstance(ckpt, dict):
+        raise RuntimeError("m2h.separate: a checkpoint must be a dict, got %s" % type(ckpt).__name__)
+    sd = ckpt["state_dict"] if "state_dict" in ckpt and isinstance(ckpt["state_dict"], dict) else ckpt
+    root = "actor_critic."
+    if any(k.startswith(root) for k in sd):
+        sd = {k[len(root):]: v for k, v in sd.items() if k.startswith(root)}
+    sep = {k: v for k, v in sd.items() if k.startswith(SEPARATOR_ROOTS)}
+    if not sep:
+        raise RuntimeError("m2h.separate: the checkpoint holds no separator weights (%s*); its first keys are %s"
+                           % ("* / ".join(SEPARATOR_ROOTS), list(sd)[:3]))
+    mem = {k[len(MEMORY_ROOT):]: v for k, v in sd.items() if k.startswith(MEMORY_ROOT + "cnn.")}
+    if not mem:
+        return sep, None, None
+    return sep, mem, ("bn" if "cnn.3.weight" in mem else "ddppo")
+
+
+def _as_tensor(v):
+    return v.detach().clone() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v))
+
+
+class Separator:
+    """checkpoint: a path (torch.load) or a dict in any form ``split_checkpoint`` accepts.  math: the arithmetic of the U-Nets and
+    the two DFTs (ops.MATH_FP32 or ops.MATH_BF16X3).  max_segments: the largest U-Net batch in one-second segments; activations and
+    transform buffers are allocated per chunk, never for the whole recording."""
+
+    def __init__(self, checkpoint, device, math=ops.MATH_BF16X3, max_segments=DEFAULT_MAX_SEGMENTS):
+        from .audio.stft import ISTFT, STFT
+        from .common.spaces import move2hear_observation_space
+        from .pretrain.passive.policy import Move2HearPassiveWoMemoryPolicy
+        from .rl.models.memory_nets import AcousticMem
+        if math not in (ops.MATH_FP32, ops.MATH_BF16X3):
+            raise ValueError("m2h.Separator: math must be ops.MATH_FP32 or ops.MATH_BF16X3")
+        if int(max_segments) < 1:
+            raise ValueError("m2h.Separator: max_segments must be at least 1, got %s" % (max_segments,))
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("m2h.Separator: device must be a GPU (got %s); the m2h ops have no CPU path" % (self.device,))
+        if not isinstance(checkpoint, dict):
+            checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=False)
+        sep_sd, mem_sd, variant = split_checkpoint(checkpoint)
+        self.math, self.max_segments = math, int(max_segments)
+        self.policy = Move2HearPassiveWoMemoryPolicy(move2hear_observation_space())
+        self.policy.load_state_dict({k: _as_tensor(v) for k, v in sep_sd.items()}, strict=True)
+        self.policy = self.policy.to(self.device).eval()
+        self.memory = None
+        if mem_sd is not None:
+            self.memory = AcousticMem(use_ddppo=(variant == "ddppo"))
+            self.memory.load_state_dict({k: _as_tensor(v) for k, v in mem_sd.items()}, strict=True)
+            self.memory = self.memory.to(self.device).eval()
+        for p in list(self.policy.parameters()) + (list(self.memory.parameters()) if self.memory is not None else []):
+            p.requires_grad_(False)
+        fwd, inv = STFT(self.device), ISTFT(self.device)
+        self._W_fwd, self._W_inv = fwd.W, inv.W
+        self._win_fwd = torch.cat((fwd.window, torch.zeros(ops.SEP_LD - fwd.n_fft, device=self.device)))
+        self._win_inv = inv.window
+        self._timing = None    # tools/separate_bench.py: a list that takes (stage, event) marks
+
+    def _mark(self, stage):
+        if self._timing is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record(torch.cuda.current_stream(self.device))
+            self._timing.append((stage, ev))
+
+    def _memory_scope(self, R):
+        """The arithmetic of the memory's steps over R recordings: up to AcousticMem.SMALL_BATCH rows the DD-PPO variant's whole forward
+        is one launch, an fp32 kernel, taken in an fp32 scope; otherwise the tiled path in the separator's own arithmetic."""
+        small = self.memory._use_ddppo and R <= self.memory.SMALL_BATCH
+        return ops.math_scope(ops.MATH_FP32 if small else self.math)
+
+    @torch.no_grad()
+    def separate(self, wave, target_class, use_memory=None, return_spectrograms=False):
+        """wave [R, 2, L] or [2, L] fp32 on this separator's device, 16 kHz, L >= 1; target_class: an int or one per recording.
+        Returns the separated waveform [R, L] ([L] for a [2, L] input); with return_spectrograms also P [R, S, 512, 32] (the
+        log1p magnitude the inverse transform was given) and the phasor [R, S, 512, 32, 2]."""
+        if not torch.is_tensor(wave):
+            raise RuntimeError("m2h.Separator: wave must be a torch tensor, got %s" % type(wave).__name__)
+        single = wave.dim() == 2
+        if single:
+            wave = wave.unsqueeze(0)
+        if wave.dim() != 3 or wave.shape[1] != 2 or wave.shape[2] < 1 or wave.shape[0] < 1:
+            raise RuntimeError("m2h.Separator: expected a binaural recording [R, 2, L] or [2, L] with L >= 1, got %s" % (tuple(wave.shape[1:] if single else wave.shape),))
+        if wave.dtype != torch.float32:
+            raise RuntimeError("m2h.Separator: wave must be float32, got %s" % wave.dtype)
+        if wave.device != self.device:
+            raise RuntimeError("m2h.Separator: wave lives on %s, the separator on %s" % (wave.device, self.device))
+        if use_memory is None:
+            use_memory = self.memory is not None
+        if use_memory and self.memory is None:
+            raise RuntimeError("m2h.Separator: use_memory=True, but the checkpoint has no acoustic_mem.cnn.* weights")
+        wave = wave.contiguous()
+        R, _, L = wave.shape
+        tc = torch.as_tensor(target_class, dtype=torch.int64).reshape(-1)
+        if tc.numel() == 1:
+            tc = tc.expand(R)
+        if tc.numel() != R:
+            raise RuntimeError("m2h.Separator: target_class must be one int or one per recording (%d), got %d values" % (R, tc.numel()))
+        tc = tc.to(self.device).contiguous()
+        y = torch.empty((R, L), device=self.device, dtype=torch.float32)
+        keep_P, keep_ph = [], []
+        prev = None
+        with torch.cuda.device(self.device), ops.math_scope(self.math):
+            self._mark("start")
+            for s0, ns in segment_plan(L, max(1, self.max_segments // R)):
+                N = ns * R
+                frames = ops.sep_frames(wave, self._win_fwd, s0, ns)
+                spec = ops.linear(frames, self._W_fwd, None, name="separate.dft")
+                mag, phasor = ops.sep_stft_post(spec, N)
+                del frames, spec
+                self._mark("stft")
+                obs = {"mixed_bin_audio_mag": mag, "target_class": tc.repeat(ns)}
+                masks = self.policy.get_binSepMasks(obs)
+                P = self.policy.convert_bin2mono(masks, mixed_audio=mag)
+                self._mark("unets")
+                if use_memory:
+                    steps = []
+                    with self._memory_scope(R):
+                        for sl in range(ns):
+                            pm = P[sl * R:(sl + 1) * R]
+                            prev = self.memory(pm, prev if prev is not None else torch.zeros_like(pm))
+                            steps.append(prev)
+                    P = torch.cat(steps) if ns > 1 else steps[0]
+                    self._mark("memory")
+                rows = ops.sep_istft_pre(P, phasor)
+                out_frames = ops.linear(rows, self._W_inv, None, name="separate.idft")
+                ops.sep_istft_ola(out_frames, self._win_inv, y, s0, ns)
+                self._mark("istft")
+                if return_spectrograms:
+                    keep_P.append(P.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES))
+                    keep_ph.append(phasor.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES, 2))
+        if not return_spectrograms:
+            return y[0] if single else y
+        Pall = torch.cat(keep_P).transpose(0, 1).contiguous()
+        ph = torch.cat(keep_ph).transpose(0, 1).contiguous()
+        return (y[0], Pall[0], ph[0]) if single else (y, Pall, ph)

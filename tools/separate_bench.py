@@ -1,0 +1,186 @@
+#!/usr/bin/env python3
+"""End-to-end rate of m2h.separate: seconds of audio separated per second, and each stage's share of the time.
+
+    python tools/separate_bench.py --out profiles/separate_bench.json          # every case, each in a child process under a timeout
+    python tools/separate_bench.py --case 16x600 --math bf16x3 [--path new|composed|both]   # one case in this process
+
+Cases: R=1, L=60 s and R=16, L=600 s, in fp32 and bf16x3 arithmetic, acoustic memory on.  Stages: "stft" (framing + DFT + post),
+"unets" (the U-Net pair), "memory", "istft" (inverse pre + DFT + overlap-add).  Timing: HIP events on the stream at the stage
+borders of every chunk; a stage's time is the sum of its intervals, the rate is audio seconds over first-to-last event.
+
+--path composed is the same result assembled from what the library offered before m2h.separate: a zero-padded copy of the
+recording cut and permuted into segment batches, the STFT class (magnitude and per-channel angle), torch for the downmix
+(polar, sum, torch.angle), expm1 / clamp, the ISTFT class (which takes the angle through sincos), a permuted copy into the
+output and the cut.  The driver times composed, new, composed: the two composed runs give that path's run-to-run spread, which is
+the margin of the comparison.
+
+Weights are synthetic.policy_shapes() with the acoustic memory's weights scaled by 0.25: as generated they are not contractive,
+and a recurrence over 600 steps would overflow expm1.  Every GPU step runs under its own timeout and the driver stops at the
+first failure.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "move2hear-active-av-separation_amd"))
+
+CASES = {"1x60": (1, 60, 20), "16x600": (16, 600, 3)}   # R, seconds, timed repetitions
+STAGES = ("stft", "unets", "memory", "istft")
+SEG = 16000
+
+
+def composed_separate(sep, stft, istft, wave, tc, mark):
+    """m2h.separate's result from the STFT / ISTFT classes and torch (memory on), chunked like Separator.separate."""
+    import torch
+    import torch.nn.functional as F
+    from m2h.separate import segment_plan
+    R, _, L = wave.shape
+    S = -(-L // SEG)
+    padded = F.pad(wave, (0, S * SEG - L))
+    y = torch.empty((R, S * SEG), device=wave.device)
+    prev = None
+    mark("start")
+    for s0, ns in segment_plan(L, max(1, sep.max_segments // R)):
+        seg = padded[:, :, s0 * SEG:(s0 + ns) * SEG].reshape(R, 2, ns, SEG).permute(2, 0, 1, 3).reshape(ns * R, 2, SEG).contiguous()
+        mag, phase = stft(seg, mode=1, want_phase=True)
+        D = torch.polar(torch.expm1(mag), phase).sum(-1)
+        angle = torch.angle(D).unsqueeze(-1).contiguous()
+        mark("stft")
+        masks = sep.policy.get_binSepMasks({"mixed_bin_audio_mag": mag, "target_class": tc.repeat(ns)})
+        P = sep.policy.convert_bin2mono(masks, mixed_audio=mag)
+        mark("unets")
+        steps = []
+        with sep._memory_scope(R):
+            for sl in range(ns):
+                pm = P[sl * R:(sl + 1) * R]
+                prev = sep.memory(pm, prev if prev is not None else torch.zeros_like(pm))
+                steps.append(prev)
+        P = torch.cat(steps) if ns > 1 else steps[0]
+        mark("memory")
+        out = istft(torch.expm1(torch.clamp(P, min=0)), angle, length=SEG, channel=0)
+        y[:, s0 * SEG:(s0 + ns) * SEG] = out.reshape(ns, R, SEG).permute(1, 0, 2).reshape(R, ns * SEG)
+        mark("istft")
+    return y[:, :L].contiguous()
+
+
+def run_case(case, math_name, path, max_segments=None):
+    import numpy as np
+    import torch
+    from m2h import ops, synthetic
+    from m2h.audio.stft import ISTFT, STFT
+    from m2h.separate import Separator
+    if not torch.cuda.is_available():
+        raise SystemExit("separate_bench: no GPU; this measurement has no CPU path")
+    R, seconds, reps = CASES[case]
+    dev = torch.device("cuda", 0)
+    math = ops.MATH_FP32 if math_name == "fp32" else ops.MATH_BF16X3
+    sd = synthetic.make_state_dict(synthetic.policy_shapes(), 2)
+    for k in sd:
+        if k.startswith("acoustic_mem."):
+            sd[k] = sd[k] * np.float32(0.25)
+    sep = Separator(sd, dev, math=math, **({"max_segments": max_segments} if max_segments else {}))
+    stft, istft = STFT(dev), ISTFT(dev)
+    L = seconds * SEG
+    g = torch.Generator(device=dev).manual_seed(7)
+    wave = torch.randn((R, 2, L), device=dev, generator=g) * 0.05
+    t = torch.arange(L, device=dev) / 16000.0
+    wave += 0.3 * torch.sin(2 * np.pi * 440.0 * t)
+    tc = torch.full((R,), 4, dtype=torch.int64, device=dev)
+
+    marks = []
+
+    def mark(stage):
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record(torch.cuda.current_stream(dev))
+        marks.append((stage, ev))
+
+    def new_path():
+        sep._timing = marks
+        try:
+            return sep.separate(wave, tc, use_memory=True)
+        finally:
+            sep._timing = None
+
+    def composed_path():
+        with torch.no_grad(), ops.math_scope(math):
+            return composed_separate(sep, stft, istft, wave, tc, mark)
+
+    def timed(fn):
+        del marks[:]
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        stage_ms = dict.fromkeys(STAGES, 0.0)
+        total = 0.0
+        for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
+            if name == "start":
+                continue                                  # between two repetitions
+            dt = e0.elapsed_time(e1)
+            stage_ms[name] += dt
+            total += dt
+        return {"audio_s_per_s": R * seconds * reps / (total * 1e-3), "ms_per_run": total / reps,
+                "stage_share": {k: v / total for k, v in stage_ms.items()}}
+
+    res = {"case": case, "R": R, "audio_seconds_per_recording": seconds, "math": math_name, "reps": reps, "max_segments": sep.max_segments, "chunk_rows": max(1, sep.max_segments // R) * R}
+    order = {"new": ("new",), "composed": ("composed",), "both": ("composed", "new", "composed")}[path]
+    fns = {"new": new_path, "composed": composed_path}
+    outs = {}
+    for name in set(order):                               # warm-up: every shape of the timed window
+        outs[name] = fns[name]()
+    torch.cuda.synchronize()
+    if len(outs) == 2:
+        a, b = outs["new"].double(), outs["composed"].double()
+        res["new_vs_composed_rel_l1"] = float((a - b).abs().sum() / b.abs().sum())
+        res["finite"] = bool(torch.isfinite(outs["new"]).all())
+    del outs
+    for name in order:
+        r = timed(fns[name])
+        res.setdefault(name, []).append(r)
+    if path == "both":
+        c = [r["audio_s_per_s"] for r in res["composed"]]
+        res["composed_spread"] = abs(c[0] - c[1]) / max(c)
+        res["speedup_over_composed"] = res["new"][0]["audio_s_per_s"] / (0.5 * (c[0] + c[1]))
+        res["new_at_least_as_fast"] = bool(res["new"][0]["audio_s_per_s"] >= min(c) * (1.0 - res["composed_spread"]))
+        share = res["new"][0]["stage_share"]
+        res["bounding_stage"] = max(share, key=share.get)
+    print(json.dumps(res))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", choices=sorted(CASES), default=None)
+    ap.add_argument("--math", choices=["fp32", "bf16x3"], default="bf16x3")
+    ap.add_argument("--path", choices=["new", "composed", "both"], default="both")
+    ap.add_argument("--max-segments", type=int, default=None, help="the Separator's max_segments (default: its own)")
+    ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
+    ap.add_argument("--timeout", type=int, default=240, help="driver mode: seconds per case")
+    args = ap.parse_args()
+    if args.case is not None:
+        run_case(args.case, args.math, args.path, args.max_segments)
+        return
+    results = []
+    for case in ("1x60", "16x600"):
+        for math in ("fp32", "bf16x3"):
+            cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case, "--math", math, "--path", args.path]
+            if args.max_segments:
+                cmd += ["--max-segments", str(args.max_segments)]
+            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            if r.returncode != 0:
+                print(r.stdout[-4000:])
+                raise SystemExit("separate_bench: case %s / %s failed with status %d; stopping" % (case, math, r.returncode))
+            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+            results.append(json.loads(line))
+            print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/separate_bench.py", "device": "MI355X (gfx950)", "results": results}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
