@@ -627,6 +627,17 @@ int m2h_sep_istft_pre(const float* P, const float* phasor, float* rows, int N, m
  * y[r][s*16000 .. ) of y [R][L] and cut at L. */
 int m2h_sep_istft_ola(const float* frames, const float* window, float* y, int R, long long L, int s0, int nseg, m2h_stream stream);
 
+/* Rational-rate conversion (m2h/audio/resample.py, csrc/resample.hip): a polyphase FIR over every row of x [rows][L_in], one launch.
+ * For the reduced ratio up / down = f_out / f_in: half = 10 * max(up, down), taps h[0 .. 2 * half] designed on the host
+ * (c = 1 / max(up, down), h = c * sinc(c * m) * kaiser(2 * half + 1, 5.0) over m = -half .. half, normalised to sum up), and
+ *   y[n] = sum_j x[j] * h[n * down - j * up + half],  0 <= n < L_out = ceil(L_in * up / down),  x zero outside [0, L_in)
+ * -- scipy.signal.resample_poly(x, up, down, padtype="constant") with its default window.  G [up][T] is the polyphase table,
+ * G[p][k] = h[p + k * up] (zero past the end), T = ceil((2 * half + 1) / up):  with t = n * down + half,
+ * y[n] = sum_{k < T} G[t mod up][k] * x[t div up - k].  Rows are independent; fp32 accumulation; buffers 4-byte aligned.
+ * Errors before any launch: null pointers, non-positive sizes, max(up, down) > 1024, L_out != ceil(L_in * up / down),
+ * T * up < 2 * half + 1. */
+int m2h_resample_poly(const float* x, const float* G, float* y, int rows, long long L_in, long long L_out, int up, int down, int T, m2h_stream stream);
+
 /* RIR-convolution feeder glue (pretrain/datasets/dataset.py:178-186,214-216; habitat_audio/simulator_train.py:416-424).
  * m2h_feeder_round_mix: takes the "same"-mode window [start, start+L) of S full linear convolutions (rows of ldfull floats),
  * applies np.round -> int16 -> float32 / 32768, optionally stores it (conv_out [S][L], NULL to skip) and accumulates it into

@@ -16,7 +16,7 @@ CSRC = os.path.join(_PKG_ROOT, "csrc")
 INCLUDE = os.path.join(_REPO_ROOT, "include")
 # M2H_LIB: kernel-tuning override -- load an experimental build of the same C-ABI (tools/build_variant.sh) instead of the in-tree one
 LIB_PATH = os.environ.get("M2H_LIB") or os.path.join(_HERE, "libm2h.so")
-SOURCES = ["conv_igemm.hip", "conv_dma.hip", "conv_patch.hip", "convt_quad.hip", "conv_strip.hip", "acoustic_mem.hip", "conv_bwd.hip", "bn.hip", "stft.hip", "separate.hip", "layout.hip", "rl_ops.hip", "rollout_fused.hip", "pack_batch.hip", "fftconv.hip", "api.hip"]
+SOURCES = ["conv_igemm.hip", "conv_dma.hip", "conv_patch.hip", "convt_quad.hip", "conv_strip.hip", "acoustic_mem.hip", "conv_bwd.hip", "bn.hip", "stft.hip", "separate.hip", "resample.hip", "layout.hip", "rl_ops.hip", "rollout_fused.hip", "pack_batch.hip", "fftconv.hip", "api.hip"]
 
 _lock = threading.Lock()
 _lib = None
@@ -274,6 +274,7 @@ SIGNATURES = {
     "m2h_sep_stft_post": [_P, _P, _P, _I, _P],
     "m2h_sep_istft_pre": [_P, _P, _P, _I, _P],
     "m2h_sep_istft_ola": [_P, _P, _P, _I, _L, _I, _I, _P],
+    "m2h_resample_poly": [_P, _P, _P, _I, _L, _L, _I, _I, _I, _P],
     "m2h_split32": [_P, _P, ctypes.c_size_t, _P],
     "m2h_feeder_round_mix": [_P, _I, _I, _P, _P, _I, _I, _I, _F, _P],
     "m2h_rms_normalize": [_P, _I, _I, _F, _P],

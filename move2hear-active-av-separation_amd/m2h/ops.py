@@ -1138,3 +1138,32 @@ def sep_istft_ola(frames, window, y, s0, nseg):
     with torch.cuda.device(y.device):
         _lib.check(_lib.load().m2h_sep_istft_ola(_ptr(frames), _ptr(window), _ptr(y), R, L, s0, nseg, _stream(y)), "m2h_sep_istft_ola")
     return y
+
+
+# ---- rational-rate conversion (csrc/resample.hip; designed and driven by m2h/audio/resample.py) ----
+RESAMPLE_MAX_RATIO = 1024
+
+
+def resample_poly(x, G, up, down, out=None):
+    """x [rows, L_in] -> [rows, ceil(L_in * up / down)]: the polyphase FIR of m2h_resample_poly over every row, one launch.
+    G: the [up, T] table of the ratio up / down (m2h.audio.resample.polyphase_table of design()'s taps)."""
+    _chk(x, "resample_poly(x)")
+    _chk(G, "resample_poly(G)")
+    up, down = int(up), int(down)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise RuntimeError("m2h.resample_poly: expected rows of samples [rows, L] with L >= 1, got %s" % (tuple(x.shape),))
+    if up < 1 or down < 1 or G.dim() != 2 or G.shape[0] != up:
+        raise RuntimeError("m2h.resample_poly: expected a [up, T] table for the ratio %d/%d, got %s" % (up, down, tuple(G.shape)))
+    if G.device != x.device:
+        raise RuntimeError("m2h.resample_poly: the table lives on %s, x on %s" % (G.device, x.device))
+    rows, L_in = x.shape
+    L_out = -(-L_in * up // down)
+    if out is None:
+        out = torch.empty((rows, L_out), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, "resample_poly(out)")
+        if tuple(out.shape) != (rows, L_out) or out.device != x.device:
+            raise RuntimeError("m2h.resample_poly: out must be [%d, %d] on %s, got %s on %s" % (rows, L_out, x.device, tuple(out.shape), out.device))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().m2h_resample_poly(_ptr(x), _ptr(G), _ptr(out), rows, L_in, L_out, up, down, G.shape[1], _stream(x)), "m2h_resample_poly")
+    return out

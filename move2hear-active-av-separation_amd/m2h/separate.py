@@ -2,6 +2,7 @@
 
     sep = Separator("ckpt.pth", torch.device("cuda", 0))
     mono = sep.separate(wave, target_class)          # wave [R, 2, L] (or [2, L]) fp32 at 16 kHz  ->  [R, L]
+    mono = sep.separate(wave, target_class, sample_rate=44100)     # any supported rate in, the same rate and length out
 
 Semantics (the CPU statement of the same thing is tests/separate_ref.py):
   * the recording is cut into S = ceil(L / 16000) non-overlapping one-second segments -- the agent's steps; samples at or past L are zero;
@@ -13,7 +14,15 @@ Semantics (the CPU statement of the same thing is tests/separate_ref.py):
     P_s = mem(pred_mono_s, P_{s-1}) (eval()'s recurrence without an episode boundary), without it P_s = pred_mono_s;
   * the networks work on log1p magnitudes: the inverse transform gets expm1(max(P, 0)) times the phasor, then the evaluation
     path's iSTFT (n_fft 1022 inferred from 512 bins, length 16000); the segments are concatenated and cut at L.
-Overlapping or cross-faded segments and resampling are not part of this.
+Overlapping or cross-faded segments are not part of this.
+
+Other sample rates (``sample_rate=f``): the recording is converted to 16 kHz, separated exactly as above, converted back with the
+reversed ratio and cut at L.  The conversion is the polyphase FIR of m2h/audio/resample.py (csrc/resample.hip): for the reduced ratio
+up / down = f_out / f_in, half = 10 * max(up, down), h = c * sinc(c * m) * kaiser(2 * half + 1, 5.0) with c = 1 / max(up, down) over
+m = -half .. half, normalised to sum up, and y[n] = sum_j x[j] * h[n * down - j * up + half] for n < ceil(L * up / down), x zero
+outside the recording -- scipy.signal.resample_poly(x, up, down, padtype="constant") with its default window.  The 16 kHz
+recording has L16 = ceil(L * 16000 / f) samples; its back-conversion never has fewer than L.  Spectrograms are those of the
+16 kHz recording.  Rates with max(up, down) <= 1024 are supported (tests/resample_ref.py is the CPU statement).
 
 The two DFTs are dense 1024 x 1024 GEMMs (ops.linear) and follow the calling thread's arithmetic like the U-Nets; framing, the
 magnitude / phasor store, the inverse transform's operand and the overlap-add are the HIP kernels of csrc/separate.hip, which
@@ -25,6 +34,7 @@ import torch
 from . import ops
 
 SEGMENT = ops.SEP_SEGMENT
+SAMPLE_RATE = 16000
 SEPARATOR_ROOTS = ("binSep_enc.", "binSep_dec.", "bin2mono_enc.", "bin2mono_dec.")
 MEMORY_ROOT = "acoustic_mem."
 # rows of a U-Net batch.  Measured on 16 recordings of 600 s in bf16x3 (tools/separate_bench.py): 64 rows 89 K, 256 rows 203 K, 1024 rows
@@ -106,6 +116,7 @@ class Separator:
         self._win_fwd = torch.cat((fwd.window, torch.zeros(ops.SEP_LD - fwd.n_fft, device=self.device)))
         self._win_inv = inv.window
         self._timing = None    # tools/separate_bench.py: a list that takes (stage, event) marks
+        self._resamplers = {}  # sample rate -> (Resampler to 16 kHz, Resampler back)
 
     def _mark(self, stage):
         if self._timing is not None:
@@ -119,11 +130,21 @@ class Separator:
         small = self.memory._use_ddppo and R <= self.memory.SMALL_BATCH
         return ops.math_scope(ops.MATH_FP32 if small else self.math)
 
+    def resamplers(self, sample_rate):
+        """(to 16 kHz, back) for a recording's sample rate, built once per rate; ValueError for a rate that is not supported."""
+        from .audio.resample import Resampler
+        key = int(sample_rate) if int(sample_rate) == sample_rate else sample_rate
+        if key not in self._resamplers:
+            self._resamplers[key] = (Resampler(key, SAMPLE_RATE, self.device), Resampler(SAMPLE_RATE, key, self.device))
+        return self._resamplers[key]
+
     @torch.no_grad()
-    def separate(self, wave, target_class, use_memory=None, return_spectrograms=False):
-        """wave [R, 2, L] or [2, L] fp32 on this separator's device, 16 kHz, L >= 1; target_class: an int or one per recording.
+    def separate(self, wave, target_class, use_memory=None, return_spectrograms=False, sample_rate=SAMPLE_RATE):
+        """wave [R, 2, L] or [2, L] fp32 on this separator's device, L >= 1; target_class: an int or one per recording.
         Returns the separated waveform [R, L] ([L] for a [2, L] input); with return_spectrograms also P [R, S, 512, 32] (the
-        log1p magnitude the inverse transform was given) and the phasor [R, S, 512, 32, 2]."""
+        log1p magnitude the inverse transform was given) and the phasor [R, S, 512, 32, 2].  sample_rate: the recording's rate;
+        other than 16000 the recording is converted to 16 kHz and the result back (module docstring), the output has the
+        input's rate and length, and S counts the seconds of the 16 kHz recording."""
         if not torch.is_tensor(wave):
             raise RuntimeError("m2h.Separator: wave must be a torch tensor, got %s" % type(wave).__name__)
         single = wave.dim() == 2
@@ -140,6 +161,15 @@ class Separator:
         if use_memory and self.memory is None:
             raise RuntimeError("m2h.Separator: use_memory=True, but the checkpoint has no acoustic_mem.cnn.* weights")
         wave = wave.contiguous()
+        to16 = back = None
+        if sample_rate != SAMPLE_RATE:
+            to16, back = self.resamplers(sample_rate)
+        L_given = wave.shape[2]
+        if to16 is not None:
+            with torch.cuda.device(self.device):
+                self._mark("start")
+                wave = to16(wave)
+                self._mark("resample_in")
         R, _, L = wave.shape
         tc = torch.as_tensor(target_class, dtype=torch.int64).reshape(-1)
         if tc.numel() == 1:
@@ -151,7 +181,8 @@ class Separator:
         keep_P, keep_ph = [], []
         prev = None
         with torch.cuda.device(self.device), ops.math_scope(self.math):
-            self._mark("start")
+            if to16 is None:
+                self._mark("start")
             for s0, ns in segment_plan(L, max(1, self.max_segments // R)):
                 N = ns * R
                 frames = ops.sep_frames(wave, self._win_fwd, s0, ns)
@@ -179,6 +210,9 @@ class Separator:
                 if return_spectrograms:
                     keep_P.append(P.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES))
                     keep_ph.append(phasor.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES, 2))
+            if back is not None:
+                y = back(y)[:, :L_given].contiguous()      # ceil(ceil(L a / b) b / a) >= L: never short
+                self._mark("resample_out")
         if not return_spectrograms:
             return y[0] if single else y
         Pall = torch.cat(keep_P).transpose(0, 1).contiguous()

@@ -2,7 +2,7 @@
 """End-to-end rate of m2h.separate: seconds of audio separated per second, and each stage's share of the time.
 
     python tools/separate_bench.py --out profiles/separate_bench.json          # every case, each in a child process under a timeout
-    python tools/separate_bench.py --case 16x600 --math bf16x3 [--path new|composed|both]   # one case in this process
+    python tools/separate_bench.py --case 16x600 --math bf16x3 [--path new|composed|both] [--sample-rate 44100]   # one case in this process
 
 Cases: R=1, L=60 s and R=16, L=600 s, in fp32 and bf16x3 arithmetic, acoustic memory on.  Stages: "stft" (framing + DFT + post),
 "unets" (the U-Net pair), "memory", "istft" (inverse pre + DFT + overlap-add).  Timing: HIP events on the stream at the stage
@@ -13,6 +13,12 @@ recording cut and permuted into segment batches, the STFT class (magnitude and p
 (polar, sum, torch.angle), expm1 / clamp, the ISTFT class (which takes the angle through sincos), a permuted copy into the
 output and the cut.  The driver times composed, new, composed: the two composed runs give that path's run-to-run spread, which is
 the margin of the comparison.
+
+--sample-rate f (driver mode: --sample-rates, default 16000 44100 48000): the recording is at f Hz.  The new path is
+Separator.separate(..., sample_rate=f) with the two extra stages "resample_in" / "resample_out" (csrc/resample.hip); the composed path
+converts with torch -- one strided conv1d per direction with `up` output channels built from the same polyphase table, the channels
+interleaved into the output -- around composed_separate.  The case also times the conversion alone, kernel against conv1d
+(conv1d, kernel, conv1d), and reports the kernel's achieved HBM bytes per second (input read once + output written once).
 
 Weights are synthetic.policy_shapes() with the acoustic memory's weights scaled by 0.25: as generated they are not contractive,
 and a recurrence over 600 steps would overflow expm1.  Every GPU step runs under its own timeout and the driver stops at the
@@ -29,7 +35,41 @@ sys.path.insert(0, os.path.join(ROOT, "move2hear-active-av-separation_amd"))
 
 CASES = {"1x60": (1, 60, 20), "16x600": (16, 600, 3)}   # R, seconds, timed repetitions
 STAGES = ("stft", "unets", "memory", "istft")
+RESAMPLE_STAGES = ("resample_in", "resample_out")
 SEG = 16000
+
+
+class ComposedResampler:
+    """A Resampler's conversion from torch: outputs n = c + i * up of channel c share a phase, so channel c is a conv1d of stride
+    `down` with the reversed taps of its phase placed at its own offset inside a common window; the channels are then interleaved."""
+
+    def __init__(self, rs):
+        import numpy as np
+        import torch
+        from m2h.audio.resample import polyphase_table
+        up, down, half, T = rs.up, rs.down, rs.half, rs.T
+        G = polyphase_table(rs.taps.astype(np.float32), up)
+        c = np.arange(up)
+        t = c * down + half
+        p, j0 = t % up, t // up
+        self.pad_left = (T - 1) - int(j0.min())
+        K = int(j0.max()) + self.pad_left + 1
+        w = np.zeros((up, K), np.float32)
+        for k in range(T):
+            w[c, j0 - k + self.pad_left] = G[p, k]
+        self.w = torch.from_numpy(w).unsqueeze(1).to(rs.device)
+        self.rs, self.K = rs, K
+
+    def __call__(self, x):
+        import torch.nn.functional as F
+        rs = self.rs
+        lead, L = x.shape[:-1], x.shape[-1]
+        Lo = rs.output_length(L)
+        n_i = -(-Lo // rs.up)
+        need = (n_i - 1) * rs.down + self.K
+        xp = F.pad(x.reshape(-1, 1, L), (self.pad_left, max(0, need - L - self.pad_left)))
+        y = F.conv1d(xp, self.w, stride=rs.down)[:, :, :n_i]
+        return y.transpose(1, 2).reshape(-1, n_i * rs.up)[:, :Lo].reshape(*lead, Lo).contiguous()
 
 
 def composed_separate(sep, stft, istft, wave, tc, mark):
@@ -66,7 +106,7 @@ def composed_separate(sep, stft, istft, wave, tc, mark):
     return y[:, :L].contiguous()
 
 
-def run_case(case, math_name, path, max_segments=None):
+def run_case(case, math_name, path, max_segments=None, sample_rate=SEG):
     import numpy as np
     import torch
     from m2h import ops, synthetic
@@ -83,10 +123,10 @@ def run_case(case, math_name, path, max_segments=None):
             sd[k] = sd[k] * np.float32(0.25)
     sep = Separator(sd, dev, math=math, **({"max_segments": max_segments} if max_segments else {}))
     stft, istft = STFT(dev), ISTFT(dev)
-    L = seconds * SEG
+    L = seconds * sample_rate
     g = torch.Generator(device=dev).manual_seed(7)
     wave = torch.randn((R, 2, L), device=dev, generator=g) * 0.05
-    t = torch.arange(L, device=dev) / 16000.0
+    t = torch.arange(L, device=dev) / float(sample_rate)
     wave += 0.3 * torch.sin(2 * np.pi * 440.0 * t)
     tc = torch.full((R,), 4, dtype=torch.int64, device=dev)
 
@@ -97,16 +137,30 @@ def run_case(case, math_name, path, max_segments=None):
         ev.record(torch.cuda.current_stream(dev))
         marks.append((stage, ev))
 
+    resampled = sample_rate != SEG
+    stages = STAGES + (RESAMPLE_STAGES if resampled else ())
+    if resampled:
+        to16, back = sep.resamplers(sample_rate)
+        c_to16, c_back = ComposedResampler(to16), ComposedResampler(back)
+
     def new_path():
         sep._timing = marks
         try:
-            return sep.separate(wave, tc, use_memory=True)
+            return sep.separate(wave, tc, use_memory=True, **({"sample_rate": sample_rate} if resampled else {}))
         finally:
             sep._timing = None
 
     def composed_path():
         with torch.no_grad(), ops.math_scope(math):
-            return composed_separate(sep, stft, istft, wave, tc, mark)
+            if not resampled:
+                return composed_separate(sep, stft, istft, wave, tc, mark)
+            mark("start")
+            w16 = c_to16(wave)
+            mark("resample_in")
+            y16 = composed_separate(sep, stft, istft, w16, tc, lambda stage: None if stage == "start" else mark(stage))
+            y = c_back(y16)[:, :L].contiguous()
+            mark("resample_out")
+            return y
 
     def timed(fn):
         del marks[:]
@@ -114,7 +168,7 @@ def run_case(case, math_name, path, max_segments=None):
         for _ in range(reps):
             fn()
         torch.cuda.synchronize()
-        stage_ms = dict.fromkeys(STAGES, 0.0)
+        stage_ms = dict.fromkeys(stages, 0.0)
         total = 0.0
         for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
             if name == "start":
@@ -125,7 +179,7 @@ def run_case(case, math_name, path, max_segments=None):
         return {"audio_s_per_s": R * seconds * reps / (total * 1e-3), "ms_per_run": total / reps,
                 "stage_share": {k: v / total for k, v in stage_ms.items()}}
 
-    res = {"case": case, "R": R, "audio_seconds_per_recording": seconds, "math": math_name, "reps": reps, "max_segments": sep.max_segments, "chunk_rows": max(1, sep.max_segments // R) * R}
+    res = {"case": case, "R": R, "audio_seconds_per_recording": seconds, "sample_rate": sample_rate, "math": math_name, "reps": reps, "max_segments": sep.max_segments, "chunk_rows": max(1, sep.max_segments // R) * R}
     order = {"new": ("new",), "composed": ("composed",), "both": ("composed", "new", "composed")}[path]
     fns = {"new": new_path, "composed": composed_path}
     outs = {}
@@ -147,8 +201,38 @@ def run_case(case, math_name, path, max_segments=None):
         res["new_at_least_as_fast"] = bool(res["new"][0]["audio_s_per_s"] >= min(c) * (1.0 - res["composed_spread"]))
         share = res["new"][0]["stage_share"]
         res["bounding_stage"] = max(share, key=share.get)
+    if resampled:
+        res["resample"] = resample_alone(wave, to16, back, c_to16, c_back, reps)
     print(json.dumps(res))
     return res
+
+
+def resample_alone(wave, to16, back, c_to16, c_back, reps):
+    """The two conversions on their own, every repetition between two events: conv1d, kernel, conv1d."""
+    import torch
+    out = {}
+    mono16 = to16(wave)[:, 0].contiguous()
+    for name, x, kernel, composed in (("in", wave, to16, c_to16), ("out", mono16, back, c_back)):
+        a, b = kernel(x), composed(x)
+        err = float((a.double() - b.double()).abs().sum() / b.double().abs().sum())
+        nbytes = 4 * (x.numel() + a.numel())
+        del a, b
+
+        def ms(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(reps):
+                fn(x)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / reps
+
+        c0, k, c1 = ms(composed), ms(kernel), ms(composed)
+        out[name] = {"ratio": "%d/%d" % (kernel.up, kernel.down), "taps_per_output": kernel.T, "rows": x.numel() // x.shape[-1], "L_in": x.shape[-1],
+                     "kernel_ms": k, "conv1d_ms": [c0, c1], "kernel_hbm_gb_per_s": nbytes / (k * 1e-3) / 1e9, "kernel_vs_conv1d_rel_l1": err,
+                     "speedup_over_conv1d": 0.5 * (c0 + c1) / k, "conv1d_spread": abs(c0 - c1) / max(c0, c1)}
+    return out
 
 
 def main():
@@ -157,25 +241,27 @@ def main():
     ap.add_argument("--math", choices=["fp32", "bf16x3"], default="bf16x3")
     ap.add_argument("--path", choices=["new", "composed", "both"], default="both")
     ap.add_argument("--max-segments", type=int, default=None, help="the Separator's max_segments (default: its own)")
+    ap.add_argument("--sample-rate", type=int, default=SEG, help="the recording's sample rate (one case)")
+    ap.add_argument("--sample-rates", type=int, nargs="+", default=[SEG, 44100, 48000], help="driver mode: the rates every case is run at")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=240, help="driver mode: seconds per case")
     args = ap.parse_args()
     if args.case is not None:
-        run_case(args.case, args.math, args.path, args.max_segments)
+        run_case(args.case, args.math, args.path, args.max_segments, args.sample_rate)
         return
     results = []
-    for case in ("1x60", "16x600"):
-        for math in ("fp32", "bf16x3"):
-            cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case, "--math", math, "--path", args.path]
-            if args.max_segments:
-                cmd += ["--max-segments", str(args.max_segments)]
-            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            if r.returncode != 0:
-                print(r.stdout[-4000:])
-                raise SystemExit("separate_bench: case %s / %s failed with status %d; stopping" % (case, math, r.returncode))
-            line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
-            results.append(json.loads(line))
-            print(line, flush=True)
+    for case, math, rate in [(c, m, r) for r in args.sample_rates for c in ("1x60", "16x600") for m in ("fp32", "bf16x3")]:
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case, "--math", math, "--path", args.path,
+               "--sample-rate", str(rate)]
+        if args.max_segments:
+            cmd += ["--max-segments", str(args.max_segments)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0:
+            print(r.stdout[-4000:])
+            raise SystemExit("separate_bench: case %s / %s at %d Hz failed with status %d; stopping" % (case, math, rate, r.returncode))
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+        results.append(json.loads(line))
+        print(line, flush=True)
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/separate_bench.py", "device": "MI355X (gfx950)", "results": results}, f, indent=1)
