@@ -7,18 +7,38 @@
  * m2h_tuning_snapshot / m2h_tuning_restore copy the calling thread's whole state (M2H_TUNING_KNOBS ints) out / in: m2h.functional
  * uses them to carry a forward pass's knobs into the autograd thread that runs its backward.
  *
- * Knobs: 0 force split-K factor (-1 never), 1 / 2 LDS stages of the narrow / wide tiles,
- * 3 skinny-M tiles (-1 off), 4 16-wide MFMA tile (-1 off), 7 extra dynamic LDS, 8 phase-major transposed-conv order (-1 off),
- * 9 scalar-decode loader (-1 off), 11 weight-gradient block target, 14 = m2h_set_math_mode (kept for older callers; thread-local
- * like it), 15 / 16 tap-sharing transposed-conv kernel (-1 off, 2 = only for N <= 32 / tile: 128, 256, 512), 18 tap window (-1
- * off), 21 / 22 image-row 3x3 weight-gradient / conv kernels (-1 off), 23 skinny rows kernel for M <= 16 (-1 off), 24 skinny
- * gather kernel (-1 off, > 0 = pixel limit), 26 the 256 x 128 eight-wave tile of the bf16x3 arithmetic (-1 off, > 0 = minimum
- * tile count), 27 the LDS-DMA engine for split32 operands (csrc/conv_dma.hip; -1 off, 2 = below the tile-count threshold too),
- * 28 = 32: 32x32x16 instead of 16x16x32 MFMA fragments there, 30 the four-phase transposed-conv kernel (csrc/convt_quad.hip; -1
- * off, 1 = wherever its shape conditions hold), 34 = -1: no split-K launches of the LDS-DMA / shared-patch engines (two K-halves, K-parts of the deepest stages), 35 = -1: the whole-network
- * runner does not take the strip-walker kernels (csrc/conv_strip.hip), 36 the shared-patch LDS-DMA engine (csrc/conv_patch.hip; -1
- * off, 2 = below the tile-count threshold too, 3 = as 2 with the whole-image patch wherever it fits, 8 = one workgroup per tile instead of one per CU walking its tiles: A/B), 10 = n >= 8: the shared-patch engine's persistent launches take n workgroups instead of one per CU (tests, 25 = -1: weight gradients of layers with at most 1024 rows keep the 128-wide blocks (0: 64-wide, twice as many), 33 = -1: the skinny gather kernel does not take layers of 1024-4096 pixels with tiny weights (they go to the tiled engine's split-K launches), 39 walking direction of the strip kernels' images (bit 0: the masked first stage downwards, bit 1: the last stage upwards instead of downwards, bit 2: the unmasked first stage downwards; same values in any direction), 38 the skinny gather kernel's 16-row blocks (-1 never, 1 always; 0 = where 32-row blocks would leave most CUs empty).  Numbers of experiments that were measured and removed
- * (5, 6, 13, 17, 19, 20, 29, 31, 32) are accepted and ignored.  12 = -1: narrow weight-gradient blocks always take three k sub-tiles when K allows (0: two where that leaves fewer padding columns).  37 = -1: train-mode BatchNorm always takes its three-launch path (0: layers of at most 256 rows take one launch per direction, > 0: layers of at most that many rows, up to 4 096; csrc/bn.hip). */
+ * Live knobs, one per line: number, macro in csrc/m2h_internal.h, values, the test (or entry point) that uses it as a reference.
+ *    0  g_force_splitk    > 0: force this split-K factor of the register engine (and keep the other engines off), -1: never split
+ *                         -- tests/test_gpu_unet.py::test_dma_engine_matches_register_engine
+ *   10  g_patch_grid      n >= 8: the shared-patch engine's persistent launches take n workgroups instead of one per CU
+ *                         -- tests/test_gpu_patch.py (the grid-size test)
+ *   11  g_wgrad_blocks    > 0: block-count target of a weight-gradient launch -- tests/grad_routes.py (rows with S = ...)
+ *   12  (tl_tuning.v[12]) -1: narrow weight-gradient blocks always take three k sub-tiles when K allows (0: two where that leaves
+ *                         fewer padding columns) -- tests/grad_routes.py
+ *   14  (api.hip)         = m2h_set_math_mode (kept for older callers; thread-local like it)
+ *   18  g_tap_window      -1: walk every tap even where a whole kernel row / column lies in the padding -- tests/test_gpu_unet.py
+ *   21  g_wgrad_row3x3    -1: no image-row 3x3 weight-gradient kernel -- tests/test_gpu_train.py
+ *   22  g_row3x3          -1: no image-row 3x3 conv kernels -- tests/test_gpu_train.py
+ *   23  g_skinny_linear   -1: no skinny rows kernel for M <= 16 -- tests/test_gpu_rl.py, tests/test_gpu_unet.py
+ *   24  g_skinny_gather   -1: no skinny gather kernel, > 0: its pixel limit -- tests/test_gpu_unet.py, tests/test_cabi.py
+ *   25  g_wgrad_small_m   -1: weight gradients of layers with at most 1024 rows keep the 128-wide blocks (0: 64-wide, twice as many)
+ *                         -- tests/grad_routes.py
+ *   27  g_dma             the LDS-DMA engine for split32 operands (csrc/conv_dma.hip): -1 off, 2 = below the tile-count threshold
+ *                         too -- tests/test_gpu_unet.py, tests/test_gpu_patch.py
+ *   28  g_dma_shape       32: 32x32x16 instead of 16x16x32 MFMA fragments in that engine -- tests/test_gpu_unet.py
+ *   30  g_quad            the four-phase transposed-conv kernel (csrc/convt_quad.hip): -1 off, 1 = wherever its shape conditions
+ *                         hold -- tests/test_gpu_unet.py
+ *   35  g_strip           -1: the whole-network runner does not take the strip-walker kernels (csrc/conv_strip.hip)
+ *                         -- tests/test_gpu_strip.py, tests/test_gpu_unet.py
+ *   36  g_patch           the shared-patch LDS-DMA engine (csrc/conv_patch.hip): -1 off, 2 = below the tile-count threshold too,
+ *                         3 = as 2 with the whole-image patch wherever it fits (4..7: stamp variants of the M2H_CLOCK_DIAG build)
+ *                         -- tests/test_gpu_patch.py, __graft_entry__.smoke()
+ *   37  g_bn_small        train-mode BatchNorm (csrc/bn.hip): -1 always the three-launch path, 0: layers of at most 256 rows take
+ *                         one launch per direction, > 0: layers of at most that many rows (up to 4 096) -- tests/test_gpu_passive_train.py
+ *   39  g_strip_rev       walking direction of the strip kernels' images (bit 0: the masked first stage downwards, bit 1: the last
+ *                         stage upwards, bit 2: the unmasked first stage downwards; same values either way) -- tests/test_gpu_unet.py
+ * Retired -- experiments that were measured (results in DESIGN.md) and removed; m2h_tuning_set accepts and stores these numbers, and
+ * nothing reads them: 1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 15, 16, 17, 19, 20, 26, 29, 31, 32, 33, 34, 38 (and value 8 of knob 36). */
 #ifndef M2H_TUNING_H
 #define M2H_TUNING_H
 #ifdef __cplusplus

@@ -26,7 +26,6 @@
 
 namespace m2h {
 
-// (tuning knob g_dma_split2: thread-local, m2h_internal.h) m2h_tuning_set 34: -1 = no two-way split-K on the 256 x 128 tile
 // (tuning knob g_dma_shape: thread-local, m2h_internal.h) m2h_tuning_set 28: 32 = v_mfma_f32_32x32x16_bf16 fragments instead of 16x16x32
 // (tuning knob g_dma: thread-local, m2h_internal.h) m2h_tuning_set 27: -1 never use this engine; 2 = also below its tile-count threshold (tests)
 
@@ -479,16 +478,16 @@ static int launch_dma_cfg(IGemmP& p, int S, hipStream_t st) {
 // the two-way split-K launch of the 256 x 128 tile (see launch_igemm_dma): shape rule shared with conv_igemm_workspace_bytes
 bool dma_split2_rule(long M, int N, int Kw, int phases, bool ws_present, size_t ws_bytes) {
   const long t256 = ((M + 255) / 256) * (N / 128) * phases;
-  return g_dma == 0 && g_big_tile >= 0 && g_dma_split2 >= 0 && N % 128 == 0 && t256 < 224 && t256 * 2 >= 224 && Kw / BK >= 64 && ws_present &&
+  return g_dma == 0 && N % 128 == 0 && t256 < CHIP_TILES && t256 * 2 >= CHIP_TILES && Kw / BK >= 64 && ws_present &&
          (size_t)phases * 2 * M * N * sizeof(float) <= ws_bytes;
 }
-// split-K factor of the 256 x 128 tile for layers of 16 .. 223 tiles that the two-halves rule does not take: enough K-parts for one
+// split-K factor of the 256 x 128 tile for layers of 16 .. CHIP_TILES - 1 tiles that the two-halves rule does not take: enough K-parts for one
 // block per CU, at most 8, at least 8 k-tiles each (1 = not this engine's shape; fewer than 16 tiles: the weight-streaming tiles
 // of the register engine)
 int dma_deep_split(long M, int N, int Kw, int phases) {
-  if (g_dma != 0 || g_big_tile < 0 || g_dma_split2 < 0 || N % 128 != 0) return 1;
+  if (g_dma != 0 || N % 128 != 0) return 1;
   const long t256 = ((M + 255) / 256) * (N / 128) * phases;
-  if (t256 >= 224 || t256 < 16) return 1;
+  if (t256 >= CHIP_TILES || t256 < 16) return 1;
   long S = (256 + t256 - 1) / t256;
   if (S < 2) S = 2;
   if (S > 8) S = 8;
@@ -511,7 +510,7 @@ int launch_igemm_dma(IGemmP& p, size_t ws_bytes, hipStream_t st) {
   const int phases = p.convT ? 4 : 1;
   // tile and split-K factor: the register engine's own rules (conv_igemm_f32), so that the two engines agree bit for bit
   const long t256 = (((long)p.M + 255) / 256) * (p.N / 128) * phases;
-  if (g_big_tile >= 0 && (g_dma == 2 || t256 >= (g_big_tile > 0 ? g_big_tile : 224)))
+  if (g_dma == 2 || t256 >= CHIP_TILES)
     return g_dma_shape == 32 ? launch_dma_cfg<256, 128, 4, 2, 3, 32>(p, 1, st) : launch_dma_cfg<256, 128, 4, 2, 3, 16>(p, 1, st);
   // half the chip's worth of 256 x 128 tiles and a long reduction (the fourth encoder stage at the benchmark batch: 128 tiles,
   // K = 4096): two K-halves per tile into split-K slabs + the ordered reduce kernel

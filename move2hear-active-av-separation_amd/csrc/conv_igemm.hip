@@ -1236,25 +1236,10 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const IGemmP p) {
   }
 }
 
-// Debug/tuning knobs (m2h_tuning_set): 0 = automatic.
-// (tuning knob g_force_splitk: thread-local, m2h_internal.h) >0: force this split-K factor (when workspace allows), -1: never split
-// (tuning knob g_force_stages: thread-local, m2h_internal.h) 1 | 2: force the LDS stage count of the narrow-N configs
-// (tuning knob g_wide_stages: thread-local, m2h_internal.h) 1 | 2: LDS stage count of the 128x128 config (0 = 2)
-// (tuning knob g_skinny: thread-local, m2h_internal.h) -1: never use the 32/64-row tiles
-// (tuning knob g_extra_lds: thread-local, m2h_internal.h) tuning experiment: dynamic LDS bytes added to every launch (lowers blocks/CU)
-// (tuning knob g_phase_major: thread-local, m2h_internal.h) -1: transposed-conv phases as grid z (four passes over the input) instead of interleaved
 static constexpr int M2H_FMT_LAYOUT_BITS = M2H_FMT_SRC_SPLIT | M2H_FMT_W_SPLIT | M2H_FMT_DST_SPLIT;   // operand_format minus the M2H_FMT_MATH_* bits
 thread_local int tl_math_mode = 0;   // m2h_set_math_mode: the calling thread's arithmetic (0 fp32 MFMA, 1 bf16x3 split products)
 std::atomic<long long> g_launch_count{0};   // M2H_LAUNCH (m2h_internal.h)
 thread_local int tl_hi_only = 0;     // m2h_set_math_mode(M2H_MATH_BF16): tl_math_mode = 1 for every dispatch decision, and the engines listed in m2h.h drop the two cross products
-// (tuning knob g_tapshare: thread-local, m2h_internal.h) -1: never use the tap-sharing transposed-conv kernel
-// (tuning knob g_tap_bm: thread-local, m2h_internal.h) 128: 128-output tiles only in the tap-sharing kernel
-// (tuning knob g_fast_loader: thread-local, m2h_internal.h) -1: always use the generic (per-lane k decode) loader
-// (tuning knob g_narrow16: thread-local, m2h_internal.h) -1: never use the 16-wide (v_mfma_f32_16x16x4_f32) tile for N <= 16
-// (tuning knob g_skinny_linear: thread-local, m2h_internal.h) -1: never use the skinny dense kernel for M <= 16
-// (tuning knob g_skinny_gather: thread-local, m2h_internal.h) -1: never use the skinny gather kernel for 16 < M <= 256
-// (tuning knob g_row3x3: thread-local, m2h_internal.h) -1: never use the image-row 3x3 kernel
-// (tuning knob g_tap_window: thread-local, m2h_internal.h) -1: walk every tap even where a whole kernel row / column lies in the zero padding
 
 // Tap window (see IGemmP): the contiguous range of kernel rows / columns that reach inside the image for at least one output
 // pixel.  conv: ih = q*stride + off + t*mul, q in [0, Q); transposed conv: both sub-pixel phases (mul = -1, +1, off = 0) must agree.
@@ -1296,25 +1281,26 @@ static void tap_window(const m2h_conv_args& a, int& th0, int& thn, int& tw0, int
 // Reduction length the launch will walk: the tap window applies to the scalar-decode loader only.
 static int walked_K(const m2h_conv_args& a) {
   const int Ctot = a.C0 + a.C1;
-  const bool fast = g_fast_loader >= 0 && a.C0 % BK == 0 && a.C1 % BK == 0 && a.C0 > 0;
+  const bool fast = a.C0 % BK == 0 && a.C1 % BK == 0 && a.C0 > 0;
   if (!fast) return a.nth * a.ntw * Ctot;
   int th0, thn, tw0, twn;
   tap_window(a, th0, thn, tw0, twn);
   return thn * twn * Ctot;
 }
 
-// waves per block of the skinny kernels: keep a wave's chain of 16-float steps at about 16
 // waves per block of the skinny kernels: they split the walked reduction, and a wave's share is a chain of dependent load rounds
 // (runs of at most Ctot / 16 steps between tap changes), so short shares win: more than 32 steps -> 16 waves, more than 16 -> 8
 // (A/B on one box, tools/train_ab.sh: rollout 74.2 -> 71.6 ms per cycle against the round-2 thresholds 160 / 80)
 static int skinny_waves(int steps) { return steps > 32 ? 16 : (steps > 16 ? 8 : 4); }
+// fewer blocks than this leave most CUs without one: the skinny kernels then take their smaller blocks (16 rows / two columns)
+constexpr long SKINNY_MIN_BLOCKS = 192;
 
 // Tile choice: N picks the width; skinny M (rollout batches, GRU steps: weight-streaming bound, nothing to re-use along M)
 // gets 32- or 64-row tiles so that four times as many blocks stream the weights.
 static void pick_tile(long M, int N, int& BM, int& BN) {
   BN = N > 64 ? 128 : (N > 32 ? 64 : (N > 16 ? 32 : 16));
   BM = 128;
-  if (BN == 128 && g_skinny >= 0) {
+  if (BN == 128) {
     if (M <= 32) BM = 32;
     else if (M <= 64) BM = 64;
   }
@@ -1342,7 +1328,7 @@ static int splitk_for(long M, int N, int K, int phases, int BM, int BN) {
 int choose_splitk(const IGemmP& p, int BM, int BN, size_t ws_bytes) {
   if (p.ws == nullptr || g_force_splitk < 0 || (p.N & 3) != 0) return 1;
   const int phases = p.convT ? 4 : 1;
-  const int Kw = (g_fast_loader >= 0 && p.fast_ok) ? p.Kw : p.K;
+  const int Kw = p.fast_ok ? p.Kw : p.K;
   int S = splitk_for(p.M, p.N, Kw, phases, BM, BN);
   if (g_force_splitk > 0) {
     S = g_force_splitk;
@@ -1353,7 +1339,17 @@ int choose_splitk(const IGemmP& p, int BM, int BN, size_t ws_bytes) {
   return S < 1 ? 1 : S;
 }
 
-// (tuning knob g_big_tile: thread-local, m2h_internal.h) -1: never use the 256 x 128 eight-wave tile; > 0: minimum tile count for it (m2h_tuning_set 26)
+// the ordered reduce + epilogue over the split-K slabs of a register-engine / LDS-DMA / shared-patch launch (p.S slabs per phase);
+// `label` names the pair of launches for m2h_last_kernel
+static int launch_splitk_reduce(const IGemmP& p, hipStream_t st, const char* label) {
+  const long total = (long)p.M * (p.N >> 2);
+  long g = (total + 255) / 256;
+  if (g > 4096) g = 4096;
+  M2H_LAUNCH(splitk_epilogue_kernel, dim3((unsigned)g, p.convT ? 4 : 1), dim3(256), 0, st, p);
+  const int rc = launch_status("conv_igemm_f32 split-K epilogue");
+  tl_last_launch = label;
+  return rc;
+}
 
 // 256 x BN tile, 8 waves, two LDS stages, bf16x3 math on scalar-loader shapes only (no split-K: chosen when the tiles fill the chip)
 template <int BN>
@@ -1367,7 +1363,7 @@ static int launch_big(IGemmP& p, size_t ws_bytes, hipStream_t st) {
   const long nblk = mtpad * p.NT;
   if (nblk * 4 > 0x7fffffffL) return fail(-1, "conv_igemm: grid too large (%ld blocks)", nblk);
   const int phases = p.convT ? 4 : 1;
-  p.pmaj = (p.convT && g_phase_major >= 0) ? 1 : 0;
+  p.pmaj = p.convT ? 1 : 0;
   dim3 grid((unsigned)(p.pmaj ? nblk * 4 : nblk), 1, p.pmaj ? 1 : phases);
   if (p.presplit)
     M2H_LAUNCH((igemm_f32_kernel<BM, BN, 4, 2, 2, 32, 1, 2>), grid, dim3(512), 0, st, p);
@@ -1378,7 +1374,7 @@ static int launch_big(IGemmP& p, size_t ws_bytes, hipStream_t st) {
 
 template <int BM, int BN, int WM, int WN, int NSTAGE, int FR = 32>
 static int launch_cfg(IGemmP& p, size_t ws_bytes, hipStream_t st) {
-  const bool fast = g_fast_loader >= 0 && p.fast_ok;
+  const bool fast = p.fast_ok;
   p.MT = (p.M + BM - 1) / BM;
   p.NT = (p.N + BN - 1) / BN;
   p.S = choose_splitk(p, BM, BN, ws_bytes);
@@ -1386,28 +1382,22 @@ static int launch_cfg(IGemmP& p, size_t ws_bytes, hipStream_t st) {
   const long nblk = mtpad * p.NT;
   if (nblk > 0x7fffffffL) return fail(-1, "conv_igemm: grid too large (%ld blocks)", nblk);
   const int phases = p.convT ? 4 : 1;
-  p.pmaj = (p.convT && g_phase_major >= 0 && nblk * 4 <= 0x7fffffffL) ? 1 : 0;
+  p.pmaj = (p.convT && nblk * 4 <= 0x7fffffffL) ? 1 : 0;   // (phases as grid z where the interleaved grid would overflow)
   dim3 grid((unsigned)(p.pmaj ? nblk * 4 : nblk), (unsigned)p.S, p.pmaj ? 1 : phases);
   const dim3 blk(64 * WM * WN);
   if (fast && p.math == 1 && p.presplit)
-    M2H_LAUNCH((igemm_f32_kernel<BM, BN, WM, WN, NSTAGE, FR, 1, 2>), grid, blk, (size_t)g_extra_lds, st, p);
+    M2H_LAUNCH((igemm_f32_kernel<BM, BN, WM, WN, NSTAGE, FR, 1, 2>), grid, blk, 0, st, p);
   else if (fast && p.math == 1)
-    M2H_LAUNCH((igemm_f32_kernel<BM, BN, WM, WN, NSTAGE, FR, 1, 1>), grid, blk, (size_t)g_extra_lds, st, p);
+    M2H_LAUNCH((igemm_f32_kernel<BM, BN, WM, WN, NSTAGE, FR, 1, 1>), grid, blk, 0, st, p);
   else if (fast)
-    M2H_LAUNCH((igemm_f32_kernel<BM, BN, WM, WN, NSTAGE, FR, 1>), grid, blk, (size_t)g_extra_lds, st, p);
+    M2H_LAUNCH((igemm_f32_kernel<BM, BN, WM, WN, NSTAGE, FR, 1>), grid, blk, 0, st, p);
   else
-    M2H_LAUNCH((igemm_f32_kernel<BM, BN, WM, WN, NSTAGE, FR, 0>), grid, blk, (size_t)g_extra_lds, st, p);
+    M2H_LAUNCH((igemm_f32_kernel<BM, BN, WM, WN, NSTAGE, FR, 0>), grid, blk, 0, st, p);
   static const std::string label = "igemm_f32<" + std::to_string(BM) + "," + std::to_string(BN) + ">";   // one per instantiation
-  int rc = launch_status(label.c_str());
-  if (rc != 0 || p.S == 1) return rc;
-  const long total = (long)p.M * (p.N >> 2);
-  long g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
-  M2H_LAUNCH(splitk_epilogue_kernel, dim3((unsigned)g, phases), dim3(256), 0, st, p);
   static const std::string label_sk = label + " + split-K reduce";
-  rc = launch_status("conv_igemm_f32 split-K epilogue");
-  tl_last_launch = label_sk.c_str();
-  return rc;
+  const int rc = launch_status(label.c_str());
+  if (rc != 0 || p.S == 1) return rc;
+  return launch_splitk_reduce(p, st, label_sk.c_str());
 }
 
 #ifdef M2H_CLOCK_DIAG
@@ -1415,15 +1405,6 @@ extern "C" int m2h_diag_read_clocks(unsigned long long* host_out, int nblocks) {
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_clock_dbg), (size_t)nblocks * 6 * sizeof(unsigned long long));
 }
 #endif
-
-// the ordered reduce + epilogue over the split-K slabs of an LDS-DMA / shared-patch launch (p.S slabs per phase)
-static int launch_splitk_reduce(const IGemmP& p, hipStream_t st) {
-  const long total = (long)p.M * (p.N >> 2);
-  long g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
-  M2H_LAUNCH(splitk_epilogue_kernel, dim3((unsigned)g, p.convT ? 4 : 1), dim3(256), 0, st, p);
-  return launch_status("conv_igemm_f32 split-K epilogue");
-}
 
 size_t conv_igemm_workspace_bytes(const m2h_conv_args& a) {
   // the exact split-K scratch of the automatic choice for these arguments: phases * S * M * N floats
@@ -1439,8 +1420,7 @@ size_t conv_igemm_workspace_bytes(const m2h_conv_args& a) {
   // same fp32 summation order) as the whole-network runner, whose scratch is the maximum over its stages
   const int both = M2H_FMT_SRC_SPLIT | M2H_FMT_W_SPLIT;
   const int math = (a.operand_format & M2H_FMT_MATH_BF16X3) ? 1 : (a.operand_format & M2H_FMT_MATH_FP32) ? 0 : tl_math_mode;
-  if (math == 1 && (a.operand_format & both) == both && a.head_w == nullptr && a.C0 % BK == 0 && a.C1 % BK == 0 && M > 64 && g_force_splitk <= 0 &&
-      g_fast_loader >= 0) {
+  if (math == 1 && (a.operand_format & both) == both && a.head_w == nullptr && a.C0 % BK == 0 && a.C1 % BK == 0 && M > 64 && g_force_splitk <= 0) {
     const size_t need = (size_t)phases * 2 * M * a.N * sizeof(float);
     if (dma_split2_rule(M, a.N, K, phases, true, need)) {
       if (need > bytes) bytes = need;
@@ -1451,6 +1431,17 @@ size_t conv_igemm_workspace_bytes(const m2h_conv_args& a) {
     }
   }
   return bytes;
+}
+
+// Shapes of the image-row 3x3 kernels, common to the fp32 and the bf16x3 one: a 3x3 / stride 1 / pad 1 conv (either tap direction) of
+// one plain fp32 source over 32-pixel-wide images whose height is a multiple of 4, at least 512 four-row chunks, N <= 32 without BN
+// scale, class plane or fused head.  The channel counts each kernel is built for are its own rule's.
+static bool row3x3_geometry(const m2h_conv_args& a) {
+  return g_row3x3 >= 0 && !a.conv_transpose && a.nth == 3 && a.ntw == 3 && a.stride == 1 && a.os == 1 && a.ph == 0 && a.pw == 0 &&
+         (a.mulh == 1 || a.mulh == -1) && a.offh == -a.mulh && a.mulw == a.mulh && a.offw == a.offh && a.C1 == 0 && a.Wq == 32 && a.Wi == 32 &&
+         a.Hq == a.Hi && a.Ho == a.Hq && a.Wo == a.Wq && a.Hq % 4 == 0 && a.N <= 32 && a.N % 4 == 0 && a.scale == nullptr && a.cls_table == nullptr &&
+         a.head_w == nullptr && (a.operand_format & M2H_FMT_LAYOUT_BITS) == 0 && (long)a.B * (a.Hq / 4) >= 512 &&
+         (a.out_mode == M2H_OUT_NHWC || a.N % 16 == 0);
 }
 
 // l1: optional fused L1 loss (m2h_conv3x3_l1_nhwc16): honoured by the image-row 3x3 kernels' 16-channel instantiations only -- any other
@@ -1532,54 +1523,48 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
   p.ws = static_cast<float*>(a.workspace);
   const size_t wsb = a.workspace != nullptr ? a.workspace_bytes : 0;
   // split32 operands, 4x4/s2 conv or transposed conv, N a multiple of 64, a chip's worth of tiles: the shared-patch engine (conv_patch.hip)
-  if (p.presplit && g_fast_loader >= 0 && g_force_splitk <= 0 && g_phase_major >= 0) {
+  if (p.presplit && g_force_splitk <= 0) {
     const int rc = launch_igemm_patch(p, wsb, st);
     if (rc != -2) {
       if (rc != 0 || p.S == 1) return rc;
-      const int rc2 = launch_splitk_reduce(p, st);
-      tl_last_launch = "igemm_patch<256,128> + split-K reduce";
-      return rc2;
+      return launch_splitk_reduce(p, st, "igemm_patch<256,128> + split-K reduce");
     }
   }
   // narrow transposed convs on split32 operands: all four phases from one staged patch (convt_quad.hip)
-  if (p.convT && p.presplit && g_force_splitk <= 0 && g_phase_major >= 0) {
+  if (p.convT && p.presplit && g_force_splitk <= 0) {
     const int rc = launch_convT_quad(p, st);
     if (rc != -2) return rc;
   }
   // narrow transposed convs in bf16x3 math: the four taps of a phase share one staged input image (convT_tap_kernel)
-  if (p.convT && p.math == 1 && g_tapshare >= 0 && p.fast_ok && p.N <= (g_tapshare == 2 ? 32 : 64) && a.Wq >= 32 && 128 % a.Wq == 0 &&
-      a.Hq % (128 / a.Wq) == 0 && g_force_splitk <= 0 && g_phase_major >= 0 && M >= 128L * 256) {
-    // 256-output tiles when the image geometry and the block count allow (bytes per output: see the kernel)
-    // eight-wave blocks (one per CU): 256-output tiles for N = 64 by default (pair_ab, headline pair: 3.392 -> 3.364 ms); the
-    // 512-output tiles for N <= 32 measured no gain (3.388 / 3.388) and stay behind m2h_tuning_set 16 = 512 (128 / 256 = the
-    // four-wave tiles only)
-    const int bm8 = p.N <= 32 ? 512 : 256;
-    const bool wave8 = (g_tap_bm == 512 || (g_tap_bm == 0 && p.N > 32)) && bm8 / a.Wq >= 1 && a.Hq % (bm8 / a.Wq) == 0 && M >= (long)bm8 * 512;
-    const bool big = !wave8 && g_tap_bm != 128 && p.N <= 32 && a.Hq % (256 / a.Wq) == 0 && M >= 256L * 512;   // N = 64, 4 waves: 93 KB LDS, one block per CU
-    const int bm = wave8 ? bm8 : big ? 256 : 128;
+  if (p.convT && p.math == 1 && p.fast_ok && p.N <= 64 && a.Wq >= 32 && 128 % a.Wq == 0 && a.Hq % (128 / a.Wq) == 0 && g_force_splitk <= 0 &&
+      M >= 128L * 256) {
+    // 256-output tiles when the image geometry and the block count allow (bytes per output: see the kernel): eight-wave blocks (one
+    // per CU) for N = 64 (pair_ab, headline pair: 3.392 -> 3.364 ms), four-wave blocks for N <= 32 (512-output tiles measured no
+    // gain there: 3.388 / 3.388); 128-output tiles otherwise
+    const bool big = a.Hq % (256 / a.Wq) == 0 && M >= 256L * 512;
+    const int bm = big ? 256 : 128, waves = (big && p.N > 32) ? 8 : 4;
     p.MT = (int)((M + bm - 1) / bm);
     p.NT = 1;
     p.S = 1;
     const long nblk = ((long)p.MT + 7) / 8 * 8 * 4;
     // measured (layer_bench, B=256, 512x256, 128-output tiles): N=16 368 -> 308 us, N=64 277 -> 249 us; N=32 no change, so the
-    // 32-wide stage uses this kernel only with split32 operands (runner) or when forced
-    const int w = (p.N <= 16 && g_narrow16 >= 0) ? 16 : (p.N <= 32 ? 32 : 64);
-    if (nblk <= 0x7fffffffL && (w != 32 || g_tapshare > 0 || p.presplit)) {
-      const dim3 grid((unsigned)nblk), blk(wave8 ? 512 : 256);
-#define M2H_TAP_P(BN_, FR_, PRE_)                                                                                  \
-  do {                                                                                                             \
-    if (wave8) M2H_LAUNCH((convT_tap_kernel<BN_, FR_, PRE_, (BN_ <= 32 ? 512 : 256), 8>), grid, blk, 0, st, p); \
-    else if (big) M2H_LAUNCH((convT_tap_kernel<BN_, FR_, PRE_, 256>), grid, blk, 0, st, p);               \
-    else M2H_LAUNCH((convT_tap_kernel<BN_, FR_, PRE_, 128>), grid, blk, 0, st, p);                        \
+    // 32-wide stage uses this kernel only with split32 operands (runner)
+    const int w = p.N <= 16 ? 16 : (p.N <= 32 ? 32 : 64);
+    if (nblk <= 0x7fffffffL && (w != 32 || p.presplit)) {
+      const dim3 grid((unsigned)nblk), blk(64 * waves);
+#define M2H_TAP_P(BN_, FR_, PRE_, WM256_)   /* WM256_: waves of the 256-output tile's block */                  \
+  do {                                                                                                         \
+    if (big) M2H_LAUNCH((convT_tap_kernel<BN_, FR_, PRE_, 256, WM256_>), grid, blk, 0, st, p);                 \
+    else M2H_LAUNCH((convT_tap_kernel<BN_, FR_, PRE_, 128>), grid, blk, 0, st, p);                             \
   } while (0)
-#define M2H_TAP(BN_, FR_)                       \
-  do {                                          \
-    if (p.presplit) M2H_TAP_P(BN_, FR_, 1);     \
-    else M2H_TAP_P(BN_, FR_, 0);                \
+#define M2H_TAP(BN_, FR_, WM256_)                       \
+  do {                                                  \
+    if (p.presplit) M2H_TAP_P(BN_, FR_, 1, WM256_);     \
+    else M2H_TAP_P(BN_, FR_, 0, WM256_);                \
   } while (0)
-      if (w == 16) M2H_TAP(16, 16);
-      else if (w == 32) M2H_TAP(32, 32);
-      else M2H_TAP(64, 32);
+      if (w == 16) M2H_TAP(16, 16, 4);
+      else if (w == 32) M2H_TAP(32, 32, 4);
+      else M2H_TAP(64, 32, 8);
 #undef M2H_TAP
 #undef M2H_TAP_P
       return launch_status(w == 16 ? "igemm_convT_tap<16>" : (w == 32 ? "igemm_convT_tap<32>" : "igemm_convT_tap<64>"));
@@ -1587,10 +1572,10 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
   }
   // M <= 16 rows that are each one contiguous run of floats: Linear; a conv whose tap window covers the whole image and gives
   // one output pixel; a transposed conv over a 1 x 1 image (one tap per phase).  Weight streaming on the skinny kernel.
-  if (p.math == 0 && g_skinny_linear >= 0 && g_fast_loader >= 0 && p.fast_ok && M <= 16 && a.C1 == 0 && a.Hq == 1 && a.Wq == 1 && a.os >= 1 && a.N % 4 == 0 &&
+  if (p.math == 0 && g_skinny_linear >= 0 && p.fast_ok && M <= 16 && a.C1 == 0 && a.Hq == 1 && a.Wq == 1 && a.os >= 1 && a.N % 4 == 0 &&
       a.out_mode == M2H_OUT_NHWC && a.cls_table == nullptr && a.head_w == nullptr && (a.operand_format & M2H_FMT_LAYOUT_BITS) == 0 &&
-      (size_t)a.N * p.Kw * (p.convT ? 4 : 1) >= ((size_t)1 << (g_skinny_tiny >= 0 ? 14 : 18))) {   // (round 5: from 16 K weights, was 256 K: the fused audio pair's
-    // third conv and Linear at the rollout batch took a tiled launch + split-K reduce / a 32-row tile for 14 rows; knob 33 = -1: the old limit)
+      (size_t)a.N * p.Kw * (p.convT ? 4 : 1) >= ((size_t)1 << 14)) {   // (round 5: from 16 K weights, was 256 K: the fused audio pair's
+    // third conv and Linear at the rollout batch took a tiled launch + split-K reduce / a 32-row tile for 14 rows)
     bool dense;
     if (p.convT) dense = a.Hi == 1 && a.Wi == 1 && p.thn == 1 && p.twn == 1 && p.th0 == 0 && p.tw0 == 0 && a.Ho == 2 && a.Wo == 2;
     else dense = a.Ho == 1 && a.Wo == 1 && a.ph == 0 && a.pw == 0 && p.thn == a.Hi && p.twn == a.Wi && a.mulh == 1 && a.mulw == 1 &&
@@ -1601,7 +1586,7 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
       const bool wide = a.N * phases >= 64 * 16;
       // two columns per block where four would leave most CUs without a block (N = 512 of one phase: 128 blocks): as the skinny gather
       // kernel's 16-row blocks, the weights stream at a per-CU rate.  Same values (a column's sum does not depend on its neighbours).
-      const bool two = !wide && g_skinny_mgb >= 0 && a.N % 2 == 0 && (long)phases * ((a.N + 3) / 4) < 192;
+      const bool two = !wide && a.N % 2 == 0 && (long)phases * ((a.N + 3) / 4) < SKINNY_MIN_BLOCKS;
       const dim3 grid((unsigned)(phases * (wide ? (a.N + 15) / 16 : two ? (a.N + 1) / 2 : (a.N + 3) / 4))), blk(64 * nw);
 #define M2H_SKINNY_ROWS(NW_)                                                                       \
   do {                                                                                             \
@@ -1619,12 +1604,12 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
   // small pixel counts per phase (<= 1024; knob 24 > 0 overrides the limit): 32 x 16 tiles without LDS staging or split-K.
   // Also 1024 < M <= 4096 pixels against TINY weights (< 64 K elements: the rollout batch's first encoder stage, 3584 pixels x 512 x 64, and the
   // visual encoder's second and third convs): the tiled engine fills the chip there only through split-K slabs + a reduce launch (10 + 5 us
-  // for 0.2 GFLOP); knob 33 = -1: off
+  // for 0.2 GFLOP)
   const bool tiny_w = (size_t)a.N * p.Kw * (p.convT ? 4 : 1) < ((size_t)1 << 16);
-  const long skinny_lim = g_skinny_gather > 0 ? g_skinny_gather : (tiny_w && g_skinny_tiny >= 0 ? 4096 : 1024);
-  if (p.math == 0 && g_skinny_gather >= 0 && g_fast_loader >= 0 && p.fast_ok && M > 16 && M <= skinny_lim &&
+  const long skinny_lim = g_skinny_gather > 0 ? g_skinny_gather : (tiny_w ? 4096 : 1024);
+  if (p.math == 0 && g_skinny_gather >= 0 && p.fast_ok && M > 16 && M <= skinny_lim &&
       a.N % 16 == 0 && a.out_mode == M2H_OUT_NHWC && a.head_w == nullptr && (a.operand_format & M2H_FMT_LAYOUT_BITS) == 0 &&
-      p.Ctot % 16 == 0 && (tiny_w ? (M > 1024 && g_skinny_tiny >= 0) : a.cls_table == nullptr)) {
+      p.Ctot % 16 == 0 && (tiny_w ? M > 1024 : a.cls_table == nullptr)) {
     const int phases = p.convT ? 4 : 1;
     p.MT = (int)((M + 15) / 16);
     const long blocks2 = (long)phases * (a.N / 16) * ((p.MT + 1) / 2);
@@ -1632,7 +1617,7 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
     // 32 pixel rows per block where that fills the chip; 16 where it would leave most CUs without a block (the deep U-Net stages at the
     // rollout batch: 56 rows x 512 channels = 64 blocks of 32 rows): the weights stream at a per-CU rate, so twice the blocks stream them
     // twice as fast, and their second read comes out of L2.  Same values: a row's sum does not depend on the rows beside it.
-    const bool one = g_skinny_mgb >= 0 && p.MT >= 2 && (g_skinny_mgb == 1 || blocks2 < (g_skinny_mgb > 1 ? g_skinny_mgb : 192));   // (knob 38 > 1: the block-count threshold, A/B)
+    const bool one = p.MT >= 2 && blocks2 < SKINNY_MIN_BLOCKS;
     // 64 rows x 32 columns per block (eight waves) where that still gives the chip a block per CU (the update batch's 280-row Linear layers
     // against 1536 / 4608 columns: 864 / 2592 blocks of 32 x 16): such a launch is bound by the L2 -> CU operand stream -- the weights
     // pass once per row block, the activations once per column block -- and both shares halve
@@ -1640,9 +1625,9 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
     // (both wide forms for ONE-pixel outputs only -- nn.Linear and the encoders' full-spatial convs over the update batch, where they were measured:
     // 38 -> 25, 35 -> 31, 37 -> 26, 55 -> 41 us per policy epoch; on the passive step's U-Net stages of 256-1024 pixels they measured 2 % slower)
     const bool dense = a.Hq == 1 && a.Wq == 1 && !p.convT;
-    const bool four = dense && !one && g_skinny_mgb == 0 && p.MT >= 8 && blocks4 >= 240;
+    const bool four = dense && !one && p.MT >= 8 && blocks4 >= 240;
     const long blocks2w = (long)phases * ((a.N + 31) / 32) * ((p.MT + 1) / 2);   // 32 rows x 32 columns (the 280-row layers against 512 columns)
-    const bool wide2 = dense && !one && !four && g_skinny_mgb == 0 && p.MT >= 8 && blocks2w >= 128;
+    const bool wide2 = dense && !one && !four && p.MT >= 8 && blocks2w >= 128;
     const long blocks = four ? blocks4 : (wide2 ? blocks2w : (one ? (long)phases * (a.N / 16) * p.MT : blocks2));
 #define M2H_SKINNY_GATHER(NW_)                                                                              \
   do {                                                                                                      \
@@ -1658,11 +1643,7 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
     return launch_status("conv_igemm_f32 (skinny gather)");
   }
   // 3x3 / stride 1 / pad 1 over 16- or 32-channel, 32-pixel-wide images in fp32 math, many rows (AcousticMem in update_sep)
-  if (p.math == 0 && g_row3x3 >= 0 && !p.convT && a.nth == 3 && a.ntw == 3 && a.stride == 1 && a.os == 1 && a.ph == 0 && a.pw == 0 &&
-      (a.mulh == 1 || a.mulh == -1) && a.offh == -a.mulh && a.mulw == a.mulh && a.offw == a.offh && a.C1 == 0 && (a.C0 == 16 || a.C0 == 32) &&
-      a.Wq == 32 && a.Wi == 32 && a.Hq == a.Hi && a.Ho == a.Hq && a.Wo == a.Wq && a.Hq % 4 == 0 && a.N <= 32 && a.N % 4 == 0 &&
-      a.scale == nullptr && a.cls_table == nullptr && a.head_w == nullptr && (a.operand_format & M2H_FMT_LAYOUT_BITS) == 0 && (long)a.B * (a.Hq / 4) >= 512 &&
-      (a.out_mode == M2H_OUT_NHWC || a.N % 16 == 0)) {
+  if (p.math == 0 && row3x3_geometry(a) && (a.C0 == 16 || a.C0 == 32)) {
     const long chunks = (long)a.B * (a.Hq / 4);
     const dim3 grid((unsigned)(chunks < 512 ? chunks : 512)), blk(256);
     if (a.N <= 16 && a.C0 == 32) M2H_LAUNCH((conv3x3_row_kernel<16, 32>), grid, blk, 0, st, p);
@@ -1676,11 +1657,7 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
     return launch_status("conv_igemm_f32 (image-row 3x3)");
   }
   // the same image-row shapes in bf16x3 math (update_sep with sep_update_math / the far-target leg): split operands in LDS, bf16 MFMAs
-  if (p.math == 1 && !p.presplit && !p.dst_split && g_row3x3 >= 0 && !p.convT && a.nth == 3 && a.ntw == 3 && a.stride == 1 && a.os == 1 && a.ph == 0 &&
-      a.pw == 0 && (a.mulh == 1 || a.mulh == -1) && a.offh == -a.mulh && a.mulw == a.mulh && a.offw == a.offh && a.C1 == 0 &&
-      ((a.C0 == 32 && a.N <= 32) || (a.C0 == 16 && a.N > 16 && a.N <= 32)) && a.Wq == 32 && a.Wi == 32 && a.Hq == a.Hi && a.Ho == a.Hq && a.Wo == a.Wq &&
-      a.Hq % 4 == 0 && a.N % 4 == 0 && a.scale == nullptr && a.cls_table == nullptr && a.head_w == nullptr &&
-      (a.operand_format & M2H_FMT_LAYOUT_BITS) == 0 && (long)a.B * (a.Hq / 4) >= 512 && (a.out_mode == M2H_OUT_NHWC || a.N % 16 == 0)) {
+  if (p.math == 1 && row3x3_geometry(a) && (a.C0 == 32 || (a.C0 == 16 && a.N > 16))) {
     const long chunks = (long)a.B * (a.Hq / 4);
     const long cap = (a.N > 16 && a.C0 == 32) ? 512 : 768;      // resident blocks: two / three per CU (LDS)
     const dim3 grid((unsigned)(chunks < cap ? chunks : cap)), blk(256);
@@ -1700,35 +1677,27 @@ int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1) {
   // (PMC: ~8.5 TB/s of L2 reads with the matrix pipe 36 % and the LDS 39 % busy; one block per CU is only 7 % slower than two);
   // the larger tile reads 384 operand rows per 256 x 128 outputs instead of 512.  (A 256 x 64 tile for the 64-wide first encoder
   // stage measured slower: 252 vs 235 us.)
-  if (g_fast_loader >= 0 && g_force_splitk <= 0) {   // split32 operands, wide N: the LDS-DMA engine (conv_dma.hip)
+  if (g_force_splitk <= 0) {   // split32 operands, wide N: the LDS-DMA engine (conv_dma.hip)
     const int rc = launch_igemm_dma(p, wsb, st);
     if (rc != -2) {
       if (rc != 0 || p.S == 1) return rc;
-      const int rc2 = launch_splitk_reduce(p, st);
-      tl_last_launch = "igemm_dma<256,128> + split-K reduce";
-      return rc2;
+      return launch_splitk_reduce(p, st, "igemm_dma<256,128> + split-K reduce");
     }
   }
-  if (p.math == 1 && g_big_tile >= 0 && g_fast_loader >= 0 && p.fast_ok && p.N % 128 == 0 && g_force_splitk <= 0) {
+  if (p.math == 1 && p.fast_ok && p.N % 128 == 0 && g_force_splitk <= 0) {
     const long tiles = ((M + 255) / 256) * (p.N / 128) * (p.convT ? 4 : 1);
-    if (tiles >= (g_big_tile > 0 ? g_big_tile : 224)) return launch_big<128>(p, wsb, st);
+    if (tiles >= CHIP_TILES) return launch_big<128>(p, wsb, st);
   }
   int BM, BN;
   pick_tile(M, p.N, BM, BN);
   if (BM == 32) return launch_cfg<32, 128, 1, 4, 2>(p, wsb, st);
   if (BM == 64) return launch_cfg<64, 128, 2, 2, 2>(p, wsb, st);
-  if (p.N > 64) {
-    return g_wide_stages == 1 ? launch_cfg<128, 128, 2, 2, 1>(p, wsb, st) : launch_cfg<128, 128, 2, 2, 2>(p, wsb, st);
-  }
+  if (p.N > 64) return launch_cfg<128, 128, 2, 2, 2>(p, wsb, st);
   // narrow-N tiles: one LDS stage doubles the resident blocks; measured better on every 64- and 32-wide layer once the loader
   // became scalar (layer_bench.py: down0 345 vs 382 us, up3 588 vs 618 us)
-  if (p.N > 32) {
-    const bool one_stage = g_force_stages != 2;
-    return one_stage ? launch_cfg<128, 64, 2, 2, 1>(p, wsb, st) : launch_cfg<128, 64, 2, 2, 2>(p, wsb, st);
-  }
-  const bool one_stage = g_force_stages != 2;
-  if (p.N <= 16 && g_narrow16 >= 0) return launch_cfg<128, 16, 4, 1, 1, 16>(p, wsb, st);  // 16-wide MFMA: no half-empty tile
-  return one_stage ? launch_cfg<128, 32, 4, 1, 1>(p, wsb, st) : launch_cfg<128, 32, 4, 1, 2>(p, wsb, st);
+  if (p.N > 32) return launch_cfg<128, 64, 2, 2, 1>(p, wsb, st);
+  if (p.N > 16) return launch_cfg<128, 32, 4, 1, 1>(p, wsb, st);
+  return launch_cfg<128, 16, 4, 1, 1, 16>(p, wsb, st);  // 16-wide MFMA: no half-empty tile
 }
 
 }  // namespace m2h
@@ -1737,9 +1706,19 @@ using namespace m2h;
 
 extern "C" {
 
-// (1 iff the launch below would take an image-row 3x3 kernel for this shape: the rule of conv_igemm_f32's dispatch)
+// the conv of m2h_conv3x3_l1_nhwc16 as conv_igemm_f32 sees it (pointers left null)
+static m2h_conv_args l1_conv_args(int B, int H, int T, int C) {
+  m2h_conv_args a = {};
+  a.C0 = C; a.B = B; a.Hi = H; a.Wi = T; a.Hq = H; a.Wq = T;
+  a.stride = 1; a.nth = 3; a.ntw = 3; a.mulh = 1; a.offh = -1; a.mulw = 1; a.offw = -1;
+  a.N = 16; a.slope = 1.f;
+  a.Ho = H; a.Wo = T; a.os = 1; a.ldc = 16; a.out_mode = M2H_OUT_NHWC;
+  return a;
+}
+
+// (1 iff the launch below would take an image-row 3x3 kernel for this shape: the rule of conv_igemm_f32's dispatch, on 32-channel 32 x 32 images)
 int m2h_conv3x3_l1_nhwc16_supported(int B, int H, int T, int C) {
-  return (g_row3x3 >= 0 && B > 0 && H == 32 && T == 32 && C == 32 && (long)B * (H / 4) >= 512) ? 1 : 0;
+  return (B > 0 && H == 32 && C == 32 && row3x3_geometry(l1_conv_args(B, H, T, C))) ? 1 : 0;
 }
 
 int m2h_conv3x3_l1_nhwc16(const float* h, const float* wp, const float* gt_plane, float* dy, float* loss, float* partials, int B, int H, int T, int C,
@@ -1747,11 +1726,8 @@ int m2h_conv3x3_l1_nhwc16(const float* h, const float* wp, const float* gt_plane
   M2H_REQUIRE(h && wp && gt_plane && dy && loss && partials, "conv3x3_l1_nhwc16: null pointer");
   M2H_REQUIRE(m2h_conv3x3_l1_nhwc16_supported(B, H, T, C), "conv3x3_l1_nhwc16: needs 32-channel, 32 x 32-pixel images and B >= 64 (the image-row kernels' shapes); "
               "use m2h_conv_igemm_f32 + m2h_l1_loss_nhwc16 otherwise");
-  m2h_conv_args a = {};
-  a.src0 = h; a.C0 = C; a.B = B; a.Hi = H; a.Wi = T; a.Hq = H; a.Wq = T;
-  a.stride = 1; a.nth = 3; a.ntw = 3; a.mulh = 1; a.offh = -1; a.mulw = 1; a.offw = -1;
-  a.wp = wp; a.N = 16; a.slope = 1.f;
-  a.dst = dy; a.Ho = H; a.Wo = T; a.os = 1; a.ldc = 16; a.out_mode = M2H_OUT_NHWC;
+  m2h_conv_args a = l1_conv_args(B, H, T, C);
+  a.src0 = h; a.wp = wp; a.dst = dy;
   ConvL1 l1 = {gt_plane, partials, loss, 1.f / ((float)B * 16.f * (float)H * (float)T)};
   return conv_igemm_f32(a, as_stream(stream), &l1);
 }

@@ -653,9 +653,9 @@ static int launch_patch_cfg(IGemmP& p, const PatchGeo& g, int S, hipStream_t st)
   const long nblk = ((long)p.MT + 7) / 8 * 8 * p.NT * (p.convT ? 4 : 1);
   if (nblk > 0x7fffffffL) return -2;
   // every tile index is a tile (MT a multiple of 8): a workgroup per CU walks them; otherwise one workgroup per index
-  // m2h_tuning_set 36 = 8: one workgroup per tile (A/B); m2h_tuning_set 10 = n >= 8: n workgroups (a multiple of 8; tests: other tile sequences per
+  // m2h_tuning_set 10 = n >= 8: n workgroups (a multiple of 8; tests: other tile sequences per
   // workgroup than this chip's CU count gives -- phase and n-tile changing from one tile of a workgroup to its next, many tiles per workgroup)
-  const long lim = g_patch == 8 ? nblk : (g_patch_grid >= 8 ? g_patch_grid / 8 * 8 : patch_grid_limit());
+  const long lim = g_patch_grid >= 8 ? g_patch_grid / 8 * 8 : patch_grid_limit();
   const long gx = (p.MT % 8 == 0 && nblk > lim) ? lim : nblk;
   const dim3 grid((unsigned)gx, (unsigned)S), blk(64 * PNW);
   const int ntiles = (int)nblk;
@@ -695,7 +695,7 @@ int launch_igemm_patch(IGemmP& p, size_t ws_bytes, hipStream_t st) {
   // half a chip's worth of 256 x 128 tiles and a long reduction (the fourth encoder stage at the benchmark batch): the two class
   // halves of the window as split-K slabs + the ordered reduce kernel (the shape rule of the LDS-DMA engine's two-K-halves launch)
   int S = 1;
-  if ((g_patch < 2 || g_patch >= 8) && tiles < 224) {
+  if (g_patch < 2 && tiles < CHIP_TILES) {
     if (!wide || p.convT || !dma_split2_rule(p.M, p.N, p.Kw, 1, p.ws != nullptr, ws_bytes)) return -2;
     S = 2;
   }

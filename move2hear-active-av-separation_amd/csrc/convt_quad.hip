@@ -372,7 +372,7 @@ int launch_convT_quad(IGemmP& p, hipStream_t st) {
   if (p.head_w != nullptr && p.N > 32) return -2;      // the fused head lives on the 32-wide tile
   if (g_quad == 0) {
     if (p.N <= 16) return -2;                                            // padded to 32 columns: 290 vs 254 us on the tap-sharing kernel
-    if ((long)p.M * ((p.N + 31) / 32) < 256L * 224) return -2;           // too few output blocks to fill the chip
+    if ((long)p.M * ((p.N + 31) / 32) < 256L * CHIP_TILES) return -2;           // too few output blocks to fill the chip
   }
   p.MT = p.M / 256;
   p.NT = (p.N + 31) / 32;   // 64 wide: two 32-wide n-tiles per output block (four phases x 64 x 32 accumulators per wave do not fit)

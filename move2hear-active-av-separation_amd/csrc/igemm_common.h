@@ -68,6 +68,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 32;   // k-tile depth (floats)
 constexpr int LDK = 36;  // padded LDS row (floats): 144 B, keeps 16-B alignment, conflict-free b128 reads
+constexpr long CHIP_TILES = 224;   // a chip's worth of 256 x 128 tiles (host dispatch: from this many, the one-block-per-CU engines take the layer whole)
 
 // Row bookkeeping shared by the main kernel and the split-K epilogue: output pixel offset and class id of GEMM row m.
 __device__ __forceinline__ void decode_row(const IGemmP& p, int m, int ph, int pw, int& q, int& rr, int& b, int& out, int& bc) {
@@ -461,6 +462,6 @@ int launch_convT_quad(IGemmP& p, hipStream_t st);
 
 // conv_dma.hip: shape rule of the engine's two-way split-K launch (the fourth encoder stage at the benchmark batch)
 bool dma_split2_rule(long M, int N, int Kw, int phases, bool ws_present, size_t ws_bytes);
-int dma_deep_split(long M, int N, int Kw, int phases);   // K-parts of the engine's launch on a layer of 16 .. 223 tiles (1 = none)
+int dma_deep_split(long M, int N, int Kw, int phases);   // K-parts of the engine's launch on a layer of 16 .. CHIP_TILES - 1 tiles (1 = none)
 
 }  // namespace m2h

@@ -29,34 +29,26 @@ struct Tuning {
   int v[M2H_TUNING_KNOBS];
 };
 extern thread_local Tuning tl_tuning;
+// Live knobs, in number order (values and the test that holds each: include/m2h_tuning.h):
 #define g_force_splitk (::m2h::tl_tuning.v[0])
-#define g_force_stages (::m2h::tl_tuning.v[1])
-#define g_wide_stages (::m2h::tl_tuning.v[2])
-#define g_skinny (::m2h::tl_tuning.v[3])
-#define g_narrow16 (::m2h::tl_tuning.v[4])
-#define g_extra_lds (::m2h::tl_tuning.v[7])
-#define g_phase_major (::m2h::tl_tuning.v[8])
-#define g_fast_loader (::m2h::tl_tuning.v[9])
+#define g_patch_grid (::m2h::tl_tuning.v[10])
 #define g_wgrad_blocks (::m2h::tl_tuning.v[11])
-#define g_tapshare (::m2h::tl_tuning.v[15])
-#define g_tap_bm (::m2h::tl_tuning.v[16])
+// (12: read as tl_tuning.v[12] in conv_bwd.hip; 14: m2h_set_math_mode, api.hip)
 #define g_tap_window (::m2h::tl_tuning.v[18])
 #define g_wgrad_row3x3 (::m2h::tl_tuning.v[21])
 #define g_row3x3 (::m2h::tl_tuning.v[22])
 #define g_skinny_linear (::m2h::tl_tuning.v[23])
 #define g_skinny_gather (::m2h::tl_tuning.v[24])
-#define g_big_tile (::m2h::tl_tuning.v[26])
+#define g_wgrad_small_m (::m2h::tl_tuning.v[25])
 #define g_dma (::m2h::tl_tuning.v[27])
 #define g_dma_shape (::m2h::tl_tuning.v[28])
 #define g_quad (::m2h::tl_tuning.v[30])
-#define g_dma_split2 (::m2h::tl_tuning.v[34])
 #define g_strip (::m2h::tl_tuning.v[35])
 #define g_patch (::m2h::tl_tuning.v[36])
-#define g_skinny_mgb (::m2h::tl_tuning.v[38])
+// (37: g_bn_small, bn.hip)
 #define g_strip_rev (::m2h::tl_tuning.v[39])
-#define g_skinny_tiny (::m2h::tl_tuning.v[33])
-#define g_wgrad_small_m (::m2h::tl_tuning.v[25])
-#define g_patch_grid (::m2h::tl_tuning.v[10])
+// Retired (measured, result recorded in DESIGN.md, removed; accepted by m2h_tuning_set and read by nothing):
+// 1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 15, 16, 17, 19, 20, 26, 29, 31, 32, 33, 34, 38 (and value 8 of knob 36).
 
 // Label of the calling thread's most recent kernel launch (the `what` of launch_status: every launch site names its kernel family):
 // read back by m2h_last_kernel / m2h_unet_fwd_stage_kernel, so that benchmark tables name the kernel that really ran.

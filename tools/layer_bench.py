@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer A/B micro-benchmark of the igemm conv engine on the GPU (tuning tool, not a test).
-usage: python tools/layer_bench.py [--batch 256] [--tm 256] [--reps 20]"""
+usage: python tools/layer_bench.py [--batch 256] [--tm 256] [--reps 20] [--variants "auto;splitk=-1"]"""
 import argparse
 import os
 import sys
@@ -13,6 +13,7 @@ from m2h import ops  # noqa: E402
 
 
 GRAPH = False
+KNOBS = {"splitk": 0, "math": 14, "gather": 24}   # names of the live knobs this tool sets (include/m2h_tuning.h)
 
 
 def time_fn(fn, reps):
@@ -46,7 +47,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--tm", type=int, default=256)
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--variants", default="auto;splitk=-1;stages=2;splitk=-1,stages=2")
+    ap.add_argument("--variants", default="auto;splitk=-1")
     ap.add_argument("--graph", action="store_true", help="time a HIP-graph replay of the repetitions (launch-bound shapes)")
     a = ap.parse_args()
     global GRAPH
@@ -77,11 +78,11 @@ def main():
 
     variants = []
     for v in a.variants.split(";"):
-        kn = {i: 0 for i in list(range(25)) + [26]}
+        kn = {i: 0 for i in KNOBS.values()}
         if v != "auto":
             for kv in v.split(","):
                 k, val = kv.split("=")
-                kn[{"splitk": 0, "stages": 1, "wide": 2, "skinny": 3, "n16": 4, "stagger": 5, "pp": 6, "lds": 7, "pmaj": 8, "fast": 9, "math": 14, "tap": 15, "tapbm": 16, "gather": 24, "big": 26}[k]] = int(val)
+                kn[KNOBS[k]] = int(val)
         variants.append((v, kn))
 
     print("%-12s %10s %8s %6s | " % ("layer", "M", "K", "N") + " | ".join("%22s" % v for v, _ in variants))
@@ -119,7 +120,7 @@ def main():
             tot[vi] += us
             cells.append("%9.1f us %6.1f TF/s" % (us, flops / us / 1e6))
         print("%-12s %10d %8d %6d | " % (name, M, K, co) + " | ".join(cells))
-    for k in list(range(25)) + [26]:
+    for k in KNOBS.values():
         ops.debug_set(k, 0)
     print("%-12s %26s | " % ("total(us)", "") + " | ".join("%22.1f" % t for t in tot))
 

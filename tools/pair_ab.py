@@ -3,7 +3,7 @@
 
 Two bench.py runs land on different boxes and clock states (+-5 %); here every variant's HIP graph is captured once and the
 variants are replayed round-robin, so a difference of a per cent or two between them is visible.
-usage: python tools/pair_ab.py --variants "16=256;auto" [--rounds 8] [--steps 10]      (variant = knob=value[,knob=value...])"""
+usage: python tools/pair_ab.py --variants "36=-1;auto" [--rounds 8] [--steps 10]      (variant = knob=value[,knob=value...])"""
 import argparse
 import os
 import sys
