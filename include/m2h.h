@@ -627,6 +627,19 @@ int m2h_sep_istft_pre(const float* P, const float* phasor, float* rows, int N, m
  * y[r][s*16000 .. ) of y [R][L] and cut at L. */
 int m2h_sep_istft_ola(const float* frames, const float* window, float* y, int R, long long L, int s0, int nseg, m2h_stream stream);
 
+/* Overlapped segments (m2h/separate.py, overlap = k): segment s covers samples [s * hop, s * hop + 16000) of the recording,
+ * hop = 16000 / k in {16000, 8000, 4000}, and there are ceil(L / hop) of them; [s0, s0 + nseg) must lie inside.
+ * m2h_sep_frames_hop: m2h_sep_frames with the segment base at (s0 + sl) * hop (hop = 16000 gives m2h_sep_frames' rows). */
+int m2h_sep_frames_hop(const float* wave, const float* window, float* frames, int R, long long L, int hop, int s0, int nseg, m2h_stream stream);
+
+/* Inverse overlap-add of the chunk's segments (frames, window as m2h_sep_istft_ola: v_s) and their cross-fade into y [R][L]:
+ * y[r][n] = sum_s xwin[n - s * hop] * v_s[n - s * hop] / W[n], W[n] = sum of xwin[n - s * hop] over ALL segments of the recording that
+ * cover n.  xwin: 16000 floats, strictly positive, 16-byte aligned.  A chunk adds its segments in ascending order, onto zero where it
+ * holds the sample's first covering segment and onto y[n] elsewhere: call the chunks of a recording in ascending order on one stream;
+ * y needs no clearing, and the result does not depend on where the chunks are cut. */
+int m2h_sep_istft_xfade(const float* frames, const float* window, const float* xwin, float* y, int R, long long L, int hop, int s0, int nseg,
+                        m2h_stream stream);
+
 /* Rational-rate conversion (m2h/audio/resample.py, csrc/resample.hip): a polyphase FIR over every row of x [rows][L_in], one launch.
  * For the reduced ratio up / down = f_out / f_in: half = 10 * max(up, down), taps h[0 .. 2 * half] designed on the host
  * (c = 1 / max(up, down), h = c * sinc(c * m) * kaiser(2 * half + 1, 5.0) over m = -half .. half, normalised to sum up), and

@@ -25,8 +25,9 @@ constexpr int SEP_KT = 32;        // bins per workgroup of the two transposing k
 // frames[((sl*R + r)*2 + c)*32 + t][n] = window[n] * seg[t*512 + n - 511] (reflected inside the segment), n < 1023; 0 at n = 1023.
 // seg[j] = wave[r][c][(s0 + sl)*16000 + j] below L, 0 from L on.  One thread = four consecutive n = one 16-byte store; the source
 // offsets are odd by construction (n - 511), so the reads are scalar and coalesced across the wave.
-__global__ __launch_bounds__(256) void sep_frames_kernel(const float* __restrict__ wave, const float* __restrict__ window /* [1024], [1023] = 0 */,
-                                                         float* __restrict__ frames, int R, long long L, int s0, int nseg) {
+// Segment s starts at sample s * hop: 16000 for the plain path, 16000 / k for overlapped segments (sep_frames_hop_kernel).
+__device__ __forceinline__ void sep_frames_body(const float* __restrict__ wave, const float* __restrict__ window /* [1024], [1023] = 0 */,
+                                                float* __restrict__ frames, int R, long long L, int hop, int s0, int nseg) {
   const size_t total = (size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int n0 = (int)(i % (SEP_LD / 4)) * 4;
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(256) void sep_frames_kernel(const float* __restrict
     const size_t nrow = sig >> 1;
     const int r = (int)(nrow % R);
     const int sl = (int)(nrow / R);
-    const long long base = (long long)(s0 + sl) * SEP_SEG;
+    const long long base = (long long)(s0 + sl) * hop;
     const float* src = wave + ((size_t)r * 2 + c) * (size_t)L;
     const float4 w = *reinterpret_cast<const float4*>(window + n0);
     const float wv[4] = {w.x, w.y, w.z, w.w};
@@ -57,6 +58,16 @@ __global__ __launch_bounds__(256) void sep_frames_kernel(const float* __restrict
     }
     *reinterpret_cast<float4*>(frames + row * SEP_LD + n0) = make_float4(v[0], v[1], v[2], v[3]);
   }
+}
+
+__global__ __launch_bounds__(256) void sep_frames_kernel(const float* __restrict__ wave, const float* __restrict__ window, float* __restrict__ frames, int R,
+                                                         long long L, int s0, int nseg) {
+  sep_frames_body(wave, window, frames, R, L, SEP_SEG, s0, nseg);
+}
+
+__global__ __launch_bounds__(256) void sep_frames_hop_kernel(const float* __restrict__ wave, const float* __restrict__ window, float* __restrict__ frames, int R,
+                                                             long long L, int hop, int s0, int nseg) {
+  sep_frames_body(wave, window, frames, R, L, hop, s0, nseg);
 }
 
 // spec rows [(n*2 + c)*32 + t][1024] = [Re(512) | Im(512)]  ->  mag [n][512][32][2] = log1p|X_c|, phasor [n][512][32][2] = D / |D|
@@ -147,6 +158,22 @@ __global__ __launch_bounds__(256) void sep_istft_pre_kernel(const float* __restr
   }
 }
 
+// Sample j of one segment's inverse transform: fr = the segment's 32 rows of the inverse GEMM, at most two frames cover a sample.
+__device__ __forceinline__ float sep_ola_sample(const float* __restrict__ fr, const float* __restrict__ window /* [1022] */, int j) {
+  const int jj = j + SEP_NIFFT / 2;
+  float acc = 0.f, wss = 0.f;
+  int t1 = jj / SEP_HOP;
+  if (t1 > SEP_T - 1) t1 = SEP_T - 1;
+  for (int t = t1; t >= 0; --t) {
+    const int n = jj - t * SEP_HOP;
+    if (n >= SEP_NIFFT) break;
+    const float w = window[n];
+    acc += fr[(size_t)t * SEP_LD + n] * w;
+    wss += w * w;
+  }
+  return wss > 1.1754944e-38f ? acc / wss : acc;
+}
+
 // Windowed overlap-add as a gather (istft_ola_kernel's arithmetic), every segment written at its offset of y [R][L] and cut at L:
 // y[r][(s0 + sl)*16000 + j] = (sum_t frames[(sl*R + r)*32 + t][jj - 512 t] * window[jj - 512 t]) / wss(jj), jj = j + 511.
 // One thread = four consecutive j: one 16-byte store where the destination is aligned (always when L % 4 == 0) and inside L.
@@ -163,20 +190,7 @@ __global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restr
     const float* fr = frames + nrow * SEP_T * SEP_LD;
     float v[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int jj = j0 + e + SEP_NIFFT / 2;
-      float acc = 0.f, wss = 0.f;
-      int t1 = jj / SEP_HOP;
-      if (t1 > SEP_T - 1) t1 = SEP_T - 1;
-      for (int t = t1; t >= 0; --t) {
-        const int n = jj - t * SEP_HOP;
-        if (n >= SEP_NIFFT) break;
-        const float w = window[n];
-        acc += fr[(size_t)t * SEP_LD + n] * w;
-        wss += w * w;
-      }
-      v[e] = wss > 1.1754944e-38f ? acc / wss : acc;
-    }
+    for (int e = 0; e < 4; ++e) v[e] = sep_ola_sample(fr, window, j0 + e);
     float* dst = y + (size_t)r * (size_t)L + g0;
     if (g0 + 4 <= L && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
       *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
@@ -184,6 +198,68 @@ __global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restr
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (g0 + e < L) dst[e] = v[e];
+    }
+  }
+}
+
+// Overlapped segments (segment s covers samples [s*hop, s*hop + 16000), hop = 16000 / k) cross-faded into y [R][L]:
+// y[r][n] = sum_s xwin[n - s*hop] * v_s[n - s*hop] / W[n], W[n] = sum_s xwin[n - s*hop] over all segments 0 <= s < S of the recording
+// that cover n, v_s = the segment's inverse transform (sep_ola_sample).  A gather: one thread = four consecutive n of the span
+// [s0*hop, min(L, (s0 + nseg - 1)*hop + 16000)) the chunk's segments cover; hop % 4 == 0, so the four share their covering segments.
+// The chunk's covering segments are added in ascending order onto 0 when the chunk holds the sample's first covering segment and
+// onto y[n] otherwise: chunks come in ascending order, y needs no clearing, and the order of the additions is the same for any chunking.
+__global__ __launch_bounds__(256) void sep_istft_xfade_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                              const float* __restrict__ xwin /* [16000] */, float* y, int R, long long L, int hop,
+                                                              int s0, int nseg, long long S) {
+  const long long n_first = (long long)s0 * hop;
+  long long n_end = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
+  if (n_end > L) n_end = L;
+  const size_t quads = (size_t)((n_end - n_first + 3) / 4);
+  const size_t total = quads * R;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / quads);
+    const long long n0 = n_first + (long long)(i % quads) * 4;
+    // segments of the recording that cover n0 .. n0 + 3: s*hop <= n < s*hop + 16000
+    const long long a = n0 < SEP_SEG ? 0 : (n0 - SEP_SEG) / hop + 1;
+    long long b = n0 / hop;
+    if (b > S - 1) b = S - 1;
+    float W[4] = {0.f, 0.f, 0.f, 0.f};
+    for (long long s = a; s <= b; ++s) {
+      const float4 w = *reinterpret_cast<const float4*>(xwin + (n0 - s * hop));
+      W[0] += w.x;
+      W[1] += w.y;
+      W[2] += w.z;
+      W[3] += w.w;
+    }
+    float* dst = y + (size_t)r * (size_t)L + n0;
+    const bool wide = n0 + 4 <= L && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (a < s0) {                                           // earlier chunks have added their segments already
+      if (wide) {
+        const float4 p = *reinterpret_cast<const float4*>(dst);
+        acc[0] = p.x, acc[1] = p.y, acc[2] = p.z, acc[3] = p.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (n0 + e < L) acc[e] = dst[e];
+      }
+    }
+    const int lo = a < s0 ? s0 : (int)a;
+    const int hi = b > s0 + nseg - 1 ? s0 + nseg - 1 : (int)b;
+    for (int s = lo; s <= hi; ++s) {
+      const int j0 = (int)(n0 - (long long)s * hop);        // in [0, 16000), a multiple of 4
+      const float* fr = frames + ((size_t)(s - s0) * R + r) * SEP_T * SEP_LD;
+      const float4 w = *reinterpret_cast<const float4*>(xwin + j0);
+      const float wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] += sep_ola_sample(fr, window, j0 + e) * (wv[e] / W[e]);
+    }
+    if (wide) {
+      *reinterpret_cast<float4*>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (n0 + e < L) dst[e] = acc[e];
     }
   }
 }
@@ -199,6 +275,16 @@ static inline unsigned sep_grid(size_t total) {
 static inline bool sep_chunk_ok(int R, long long L, int s0, int nseg) {
   if (R <= 0 || L <= 0 || s0 < 0 || nseg <= 0) return false;
   const long long S = (L + SEP_SEG - 1) / SEP_SEG;
+  if ((long long)s0 + nseg > S) return false;
+  return (long long)nseg * R <= (1 << 20);
+}
+
+// the same for overlapped segments: hop = 16000 / k for k in {1, 2, 4}, ceil(L / hop) segments
+static inline bool sep_hop_ok(int hop) { return hop == SEP_SEG || hop == SEP_SEG / 2 || hop == SEP_SEG / 4; }
+
+static inline bool sep_chunk_hop_ok(int R, long long L, int hop, int s0, int nseg) {
+  if (R <= 0 || L <= 0 || s0 < 0 || nseg <= 0) return false;
+  const long long S = (L + hop - 1) / hop;
   if ((long long)s0 + nseg > S) return false;
   return (long long)nseg * R <= (1 << 20);
 }
@@ -241,6 +327,30 @@ int m2h_sep_istft_ola(const float* frames, const float* window, float* y, int R,
   M2H_REQUIRE(sep_chunk_ok(R, L, s0, nseg), "sep_istft_ola: bad sizes (R %d, L %lld, segments [%d, %d + %d))", R, L, s0, s0, nseg);
   M2H_LAUNCH(sep_istft_ola_kernel, dim3(sep_grid((size_t)nseg * R * (SEP_SEG / 4))), dim3(256), 0, as_stream(stream), frames, window, y, R, L, s0, nseg);
   return launch_status("sep_istft_ola");
+}
+
+int m2h_sep_frames_hop(const float* wave, const float* window, float* frames, int R, long long L, int hop, int s0, int nseg, m2h_stream stream) {
+  M2H_REQUIRE(wave && window && frames, "sep_frames_hop: null pointer");
+  M2H_REQUIRE(sep_hop_ok(hop), "sep_frames_hop: hop must be 16000, 8000 or 4000, got %d", hop);
+  M2H_REQUIRE(sep_chunk_hop_ok(R, L, hop, s0, nseg), "sep_frames_hop: bad sizes (R %d, L %lld, hop %d, segments [%d, %d + %d))", R, L, hop, s0, s0, nseg);
+  M2H_REQUIRE(aligned16(window) && aligned16(frames), "sep_frames_hop: window / frames must be 16-byte aligned");
+  M2H_LAUNCH(sep_frames_hop_kernel, dim3(sep_grid((size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4))), dim3(256), 0, as_stream(stream), wave, window, frames, R,
+             L, hop, s0, nseg);
+  return launch_status("sep_frames_hop");
+}
+
+int m2h_sep_istft_xfade(const float* frames, const float* window, const float* xwin, float* y, int R, long long L, int hop, int s0, int nseg,
+                        m2h_stream stream) {
+  M2H_REQUIRE(frames && window && xwin && y, "sep_istft_xfade: null pointer");
+  M2H_REQUIRE(sep_hop_ok(hop), "sep_istft_xfade: hop must be 16000, 8000 or 4000, got %d", hop);
+  M2H_REQUIRE(sep_chunk_hop_ok(R, L, hop, s0, nseg), "sep_istft_xfade: bad sizes (R %d, L %lld, hop %d, segments [%d, %d + %d))", R, L, hop, s0, s0, nseg);
+  M2H_REQUIRE(aligned16(xwin), "sep_istft_xfade: the cross-fade window must be 16-byte aligned");
+  const long long S = (L + hop - 1) / hop;
+  long long n_end = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
+  if (n_end > L) n_end = L;
+  const size_t quads = (size_t)((n_end - (long long)s0 * hop + 3) / 4);
+  M2H_LAUNCH(sep_istft_xfade_kernel, dim3(sep_grid(quads * R)), dim3(256), 0, as_stream(stream), frames, window, xwin, y, R, L, hop, s0, nseg, S);
+  return launch_status("sep_istft_xfade");
 }
 
 }  // extern "C"

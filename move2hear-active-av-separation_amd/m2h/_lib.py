@@ -274,6 +274,8 @@ SIGNATURES = {
     "m2h_sep_stft_post": [_P, _P, _P, _I, _P],
     "m2h_sep_istft_pre": [_P, _P, _P, _I, _P],
     "m2h_sep_istft_ola": [_P, _P, _P, _I, _L, _I, _I, _P],
+    "m2h_sep_frames_hop": [_P, _P, _P, _I, _L, _I, _I, _I, _P],
+    "m2h_sep_istft_xfade": [_P, _P, _P, _P, _I, _L, _I, _I, _I, _P],
     "m2h_resample_poly": [_P, _P, _P, _I, _L, _L, _I, _I, _I, _P],
     "m2h_split32": [_P, _P, ctypes.c_size_t, _P],
     "m2h_feeder_round_mix": [_P, _I, _I, _P, _P, _I, _I, _I, _F, _P],

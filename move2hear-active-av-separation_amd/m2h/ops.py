@@ -1140,6 +1140,61 @@ def sep_istft_ola(frames, window, y, s0, nseg):
     return y
 
 
+SEP_HOPS = (16000, 8000, 4000)
+
+
+def _sep_chunk_hop(name, R, L, hop, s0, nseg):
+    if hop not in SEP_HOPS:
+        raise RuntimeError("m2h.%s: hop must be one of %s, got %s" % (name, SEP_HOPS, hop))
+    S = -(-L // hop)
+    if R < 1 or L < 1 or s0 < 0 or nseg < 1 or s0 + nseg > S:
+        raise RuntimeError("m2h.%s: segments [%d, %d) do not lie inside a [%d, 2, %d] recording of %d segments at hop %d" % (name, s0, s0 + nseg, R, L, S, hop))
+
+
+def sep_frames_hop(wave, window, hop, s0, nseg, out=None):
+    """sep_frames for overlapped segments: segment s covers samples [s*hop, s*hop + 16000) of the recording, hop in SEP_HOPS, and
+    there are ceil(L / hop) of them (m2h_sep_frames_hop)."""
+    _chk(wave, "sep_frames_hop(wave)")
+    _chk(window, "sep_frames_hop(window)")
+    if wave.dim() != 3 or wave.shape[1] != 2:
+        raise RuntimeError("m2h.sep_frames_hop: expected a [R, 2, L] recording, got %s" % (tuple(wave.shape),))
+    if window.numel() != SEP_LD:
+        raise RuntimeError("m2h.sep_frames_hop: window must hold %d floats, got %d" % (SEP_LD, window.numel()))
+    R, _, L = wave.shape
+    _sep_chunk_hop("sep_frames_hop", R, L, hop, s0, nseg)
+    rows = nseg * R * 2 * SEP_FRAMES
+    if out is None:
+        out = torch.empty((rows, SEP_LD), device=wave.device, dtype=torch.float32)
+    else:
+        _chk(out, "sep_frames_hop(out)")
+        if tuple(out.shape) != (rows, SEP_LD):
+            raise RuntimeError("m2h.sep_frames_hop: out must be [%d, %d], got %s" % (rows, SEP_LD, tuple(out.shape)))
+    with torch.cuda.device(wave.device):
+        _lib.check(_lib.load().m2h_sep_frames_hop(_ptr(wave), _ptr(window), _ptr(out), R, L, hop, s0, nseg, _stream(wave)), "m2h_sep_frames_hop")
+    return out
+
+
+def sep_istft_xfade(frames, window, xwin, y, hop, s0, nseg):
+    """The inverse GEMM's rows [nseg*R*32, 1024] of the overlapped segments [s0, s0+nseg) -> their windowed overlap-add, weighted with
+    xwin / (the sum of xwin over every segment of the recording that covers the sample) and added into y [R, L]
+    (m2h_sep_istft_xfade).  The chunks of a recording are called in ascending order; y needs no clearing.  window: periodic
+    Hann(1022); xwin: the [16000] cross-fade window, strictly positive."""
+    _chk(frames, "sep_istft_xfade(frames)")
+    _chk(window, "sep_istft_xfade(window)")
+    _chk(xwin, "sep_istft_xfade(xwin)")
+    _chk(y, "sep_istft_xfade(y)")
+    if y.dim() != 2:
+        raise RuntimeError("m2h.sep_istft_xfade: y must be [R, L], got %s" % (tuple(y.shape),))
+    R, L = y.shape
+    _sep_chunk_hop("sep_istft_xfade", R, L, hop, s0, nseg)
+    if tuple(frames.shape) != (nseg * R * SEP_FRAMES, SEP_LD) or window.numel() < 1022 or xwin.numel() != SEP_SEGMENT:
+        raise RuntimeError("m2h.sep_istft_xfade: expected frames [%d, %d], a 1022-point window and a %d-point cross-fade window, got %s, %d and %d points"
+                           % (nseg * R * SEP_FRAMES, SEP_LD, SEP_SEGMENT, tuple(frames.shape), window.numel(), xwin.numel()))
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().m2h_sep_istft_xfade(_ptr(frames), _ptr(window), _ptr(xwin), _ptr(y), R, L, hop, s0, nseg, _stream(y)), "m2h_sep_istft_xfade")
+    return y
+
+
 # ---- rational-rate conversion (csrc/resample.hip; designed and driven by m2h/audio/resample.py) ----
 RESAMPLE_MAX_RATIO = 1024
 

@@ -3,6 +3,7 @@
     sep = Separator("ckpt.pth", torch.device("cuda", 0))
     mono = sep.separate(wave, target_class)          # wave [R, 2, L] (or [2, L]) fp32 at 16 kHz  ->  [R, L]
     mono = sep.separate(wave, target_class, sample_rate=44100)     # any supported rate in, the same rate and length out
+    mono = sep.separate(wave, target_class, overlap=2)             # one-second segments every half second, cross-faded
 
 Semantics (the CPU statement of the same thing is tests/separate_ref.py):
   * the recording is cut into S = ceil(L / 16000) non-overlapping one-second segments -- the agent's steps; samples at or past L are zero;
@@ -14,7 +15,20 @@ Semantics (the CPU statement of the same thing is tests/separate_ref.py):
     P_s = mem(pred_mono_s, P_{s-1}) (eval()'s recurrence without an episode boundary), without it P_s = pred_mono_s;
   * the networks work on log1p magnitudes: the inverse transform gets expm1(max(P, 0)) times the phasor, then the evaluation
     path's iSTFT (n_fft 1022 inferred from 512 bins, length 16000); the segments are concatenated and cut at L.
-Overlapping or cross-faded segments are not part of this.
+
+Overlapped segments (``overlap=k``, k in {1, 2, 4}, H = 16000 / k; k = 1 is the above, unchanged):
+  * segment s covers samples [s * H, s * H + 16000) for every s >= 0 with s * H < L: S' = ceil(L / H) segments, zeros from L on; each
+    is transformed, separated and inverted exactly as above, which gives v_s[t], t = 0 .. 15999;
+  * the memory runs k interleaved chains: segment s belongs to chain s mod k, its predecessor is segment s - k, the first segment
+    of every chain starts from zeros -- each chain is the recurrence above over consecutive, non-overlapping seconds, started
+    c * H samples late.  Batch rows are segment-major, so step g of all chains is the contiguous batch of the rows of segments
+    [g * k, min(g * k + k, S')): one memory call of up to k * R rows per second of audio, and no more dependent steps than k = 1;
+  * the cross-fade window is w[t] = sin^2(pi (t + 1/2) / 16000) (``crossfade_window``: float64 on the host, rounded once to fp32),
+    strictly positive, its k shifts summing to k / 2; W[n] = sum_s w[n - s * H] over the segments that cover n, and
+    y[n] = sum_s w[n - s * H] * v_s[n - s * H] / W[n] for n < L (m2h_sep_istft_xfade; where one segment covers n, y[n] = v_s);
+  * so chain c is the k = 1 path applied to wave[:, :, c * H:], and the CPU statement is the cross-fade of tests/separate_ref.py on
+    k shifted recordings (tests/separate_overlap_ref.py); spectrograms come back in segment order, P [R, S', 512, 32].
+Lead-in segments before sample 0, other windows and other overlap factors are not part of this.
 
 Other sample rates (``sample_rate=f``): the recording is converted to 16 kHz, separated exactly as above, converted back with the
 reversed ratio and cut at L.  The conversion is the polyphase FIR of m2h/audio/resample.py (csrc/resample.hip): for the reduced ratio
@@ -41,6 +55,7 @@ MEMORY_ROOT = "acoustic_mem."
 # 282 K seconds of audio per second -- below a few hundred rows of 512 x 32 the U-Nets' 22 launches are bound by their boundaries.
 # 1024 rows hold 0.5 GB of transform buffers and half the activations of the benchmark's batch (256 spectrograms of 512 x 256).
 DEFAULT_MAX_SEGMENTS = 1024
+OVERLAPS = (1, 2, 4)
 
 
 def segment_plan(L, max_segments):
@@ -53,6 +68,31 @@ def segment_plan(L, max_segments):
         raise ValueError("segment_plan: max_segments must be at least 1, got %d" % max_segments)
     S = -(-L // SEGMENT)
     return [(s0, min(max_segments, S - s0)) for s0 in range(0, S, max_segments)]
+
+
+def overlap_plan(L, overlap, max_segments):
+    """segment_plan for overlapped segments: (first_segment, n_segments) chunks covering the ceil(L / (16000 / overlap)) segments in
+    order.  A chunk holds max(overlap, max_segments) segments rounded down to a multiple of overlap, so that a memory step (the
+    `overlap` segments of one second) never straddles two chunks; only the last chunk may hold fewer.  overlap = 1 is segment_plan.
+    Pure Python."""
+    L, overlap, max_segments = int(L), int(overlap), int(max_segments)
+    if overlap not in OVERLAPS:
+        raise ValueError("overlap_plan: overlap must be one of %s, got %d" % (OVERLAPS, overlap))
+    if L < 1:
+        raise ValueError("overlap_plan: a recording needs at least one sample, got L = %d" % L)
+    if max_segments < 1:
+        raise ValueError("overlap_plan: max_segments must be at least 1, got %d" % max_segments)
+    hop = SEGMENT // overlap
+    S = -(-L // hop)
+    per = max(overlap, max_segments) // overlap * overlap
+    return [(s0, min(per, S - s0)) for s0 in range(0, S, per)]
+
+
+def crossfade_window(dtype=np.float32):
+    """w[t] = sin^2(pi (t + 1/2) / 16000), t = 0 .. 15999, computed in float64 and rounded once to dtype: strictly positive (its
+    minimum is 9.64e-9), symmetric, and its shifts by 16000 / k sum to k / 2 for k = 2 and 4."""
+    t = np.arange(SEGMENT, dtype=np.float64)
+    return (np.sin(np.pi * (t + 0.5) / SEGMENT) ** 2).astype(dtype)
 
 
 def split_checkpoint(ckpt):
@@ -115,6 +155,7 @@ class Separator:
         self._W_fwd, self._W_inv = fwd.W, inv.W
         self._win_fwd = torch.cat((fwd.window, torch.zeros(ops.SEP_LD - fwd.n_fft, device=self.device)))
         self._win_inv = inv.window
+        self._win_xfade = None   # the cross-fade window, on the device from the first overlap > 1 call on
         self._timing = None    # tools/separate_bench.py: a list that takes (stage, event) marks
         self._resamplers = {}  # sample rate -> (Resampler to 16 kHz, Resampler back)
 
@@ -139,12 +180,16 @@ class Separator:
         return self._resamplers[key]
 
     @torch.no_grad()
-    def separate(self, wave, target_class, use_memory=None, return_spectrograms=False, sample_rate=SAMPLE_RATE):
+    def separate(self, wave, target_class, use_memory=None, return_spectrograms=False, sample_rate=SAMPLE_RATE, overlap=1):
         """wave [R, 2, L] or [2, L] fp32 on this separator's device, L >= 1; target_class: an int or one per recording.
         Returns the separated waveform [R, L] ([L] for a [2, L] input); with return_spectrograms also P [R, S, 512, 32] (the
         log1p magnitude the inverse transform was given) and the phasor [R, S, 512, 32, 2].  sample_rate: the recording's rate;
         other than 16000 the recording is converted to 16 kHz and the result back (module docstring), the output has the
-        input's rate and length, and S counts the seconds of the 16 kHz recording."""
+        input's rate and length, and S counts the seconds of the 16 kHz recording.  overlap: 1, 2 or 4 one-second segments over
+        every sample, cross-faded (module docstring); S is then ceil(L / (16000 / overlap)), in segment order."""
+        if isinstance(overlap, bool) or overlap not in OVERLAPS:
+            raise ValueError("m2h.Separator: overlap must be one of %s, got %r" % (OVERLAPS, overlap))
+        overlap = int(overlap)
         if not torch.is_tensor(wave):
             raise RuntimeError("m2h.Separator: wave must be a torch tensor, got %s" % type(wave).__name__)
         single = wave.dim() == 2
@@ -180,12 +225,18 @@ class Separator:
         y = torch.empty((R, L), device=self.device, dtype=torch.float32)
         keep_P, keep_ph = [], []
         prev = None
+        hop = SEGMENT // overlap
+        if overlap > 1 and self._win_xfade is None:
+            self._win_xfade = torch.from_numpy(crossfade_window()).to(self.device)
         with torch.cuda.device(self.device), ops.math_scope(self.math):
             if to16 is None:
                 self._mark("start")
-            for s0, ns in segment_plan(L, max(1, self.max_segments // R)):
+            for s0, ns in overlap_plan(L, overlap, max(1, self.max_segments // R)):
                 N = ns * R
-                frames = ops.sep_frames(wave, self._win_fwd, s0, ns)
+                if overlap == 1:
+                    frames = ops.sep_frames(wave, self._win_fwd, s0, ns)
+                else:
+                    frames = ops.sep_frames_hop(wave, self._win_fwd, hop, s0, ns)
                 spec = ops.linear(frames, self._W_fwd, None, name="separate.dft")
                 mag, phasor = ops.sep_stft_post(spec, N)
                 del frames, spec
@@ -196,16 +247,21 @@ class Separator:
                 self._mark("unets")
                 if use_memory:
                     steps = []
-                    with self._memory_scope(R):
-                        for sl in range(ns):
-                            pm = P[sl * R:(sl + 1) * R]
-                            prev = self.memory(pm, prev if prev is not None else torch.zeros_like(pm))
+                    with self._memory_scope(overlap * R):
+                        # one step = the `overlap` segments of one second, one per chain; a chunk starts at a multiple of `overlap`,
+                        # and only the recording's last step may hold fewer chains
+                        for sl in range(0, ns, overlap):
+                            pm = P[sl * R:min(sl + overlap, ns) * R]
+                            prev = self.memory(pm, prev[:pm.shape[0]] if prev is not None else torch.zeros_like(pm))
                             steps.append(prev)
-                    P = torch.cat(steps) if ns > 1 else steps[0]
+                    P = torch.cat(steps) if len(steps) > 1 else steps[0]
                     self._mark("memory")
                 rows = ops.sep_istft_pre(P, phasor)
                 out_frames = ops.linear(rows, self._W_inv, None, name="separate.idft")
-                ops.sep_istft_ola(out_frames, self._win_inv, y, s0, ns)
+                if overlap == 1:
+                    ops.sep_istft_ola(out_frames, self._win_inv, y, s0, ns)
+                else:
+                    ops.sep_istft_xfade(out_frames, self._win_inv, self._win_xfade, y, hop, s0, ns)
                 self._mark("istft")
                 if return_spectrograms:
                     keep_P.append(P.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES))

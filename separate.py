@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Separate one sound class out of a binaural recording of any length:
 
-    python separate.py --ckpt F --in mix.wav --target-class K --out out.wav [--no-memory] [--math fp32|bf16x3] [--resample]
+    python separate.py --ckpt F --in mix.wav --target-class K --out out.wav [--no-memory] [--math fp32|bf16x3] [--resample] [--overlap 1|2|4]
 
 ``--ckpt``: a passive-separator checkpoint or a PPO checkpoint (``{"state_dict", "config"}`` file or a bare state dict, with or
 without the ``actor_critic.`` root).  ``--in``: a two-channel WAV at 16 kHz, int16 or float32.  The output is a mono WAV of the
 same length and sample format.  The acoustic memory is used when the checkpoint has one, unless ``--no-memory``.
 ``--resample``: accept a file at another rate (44.1 kHz, 48 kHz, ...): it is converted to 16 kHz on the GPU, separated, and converted
 back, and the output has the input's rate, length and sample format.  Without the flag any other rate is an error.
-Semantics and the conversion's definition: m2h/separate.py.
+``--overlap k``: k one-second segments over every sample (a segment every 1/k second), cross-faded with a sin^2 window, instead of
+non-overlapping seconds; the default 1 is the plain path.
+Semantics, the conversion's and the cross-fade's definition: m2h/separate.py.
 """
 import argparse
 import os
@@ -55,6 +57,7 @@ def main():
     parser.add_argument("--math", choices=["fp32", "bf16x3"], default="bf16x3")
     parser.add_argument("--max-segments", type=int, default=None, help="largest U-Net batch in one-second segments")
     parser.add_argument("--resample", action="store_true", help="accept an input at another sample rate: convert to 16 kHz, separate, convert back")
+    parser.add_argument("--overlap", type=int, choices=[1, 2, 4], default=1, help="one-second segments over every sample, cross-faded (1: non-overlapping)")
     args = parser.parse_args()
     wave, dtype, rate = read_wav(args.inp, args.resample)
     if rate != SAMPLE_RATE:
@@ -70,10 +73,12 @@ def main():
     dev = torch.device("cuda", 0)
     sep = Separator(args.ckpt, dev, math=ops.MATH_FP32 if args.math == "fp32" else ops.MATH_BF16X3,
                     max_segments=args.max_segments or DEFAULT_MAX_SEGMENTS)
-    y = sep.separate(torch.from_numpy(wave).to(dev), args.target_class, use_memory=False if args.no_memory else None, sample_rate=rate)
+    y = sep.separate(torch.from_numpy(wave).to(dev), args.target_class, use_memory=False if args.no_memory else None, sample_rate=rate,
+                     overlap=args.overlap)
     wavfile.write(args.out, rate, to_wav_samples(y.cpu().numpy(), dtype))
-    print("separate.py: wrote %s (%d samples at %d Hz, %.2f s, class %d, memory %s, %s)" % (
-        args.out, y.numel(), rate, y.numel() / rate, args.target_class, "on" if (sep.memory is not None and not args.no_memory) else "off", args.math))
+    print("separate.py: wrote %s (%d samples at %d Hz, %.2f s, class %d, memory %s, %s, overlap %d)" % (
+        args.out, y.numel(), rate, y.numel() / rate, args.target_class, "on" if (sep.memory is not None and not args.no_memory) else "off", args.math,
+        args.overlap))
 
 
 if __name__ == "__main__":

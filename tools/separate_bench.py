@@ -2,7 +2,7 @@
 """End-to-end rate of m2h.separate: seconds of audio separated per second, and each stage's share of the time.
 
     python tools/separate_bench.py --out profiles/separate_bench.json          # every case, each in a child process under a timeout
-    python tools/separate_bench.py --case 16x600 --math bf16x3 [--path new|composed|both] [--sample-rate 44100]   # one case in this process
+    python tools/separate_bench.py --case 16x600 --math bf16x3 [--path new|composed|both] [--sample-rate 44100] [--overlap 2]   # one case in this process
 
 Cases: R=1, L=60 s and R=16, L=600 s, in fp32 and bf16x3 arithmetic, acoustic memory on.  Stages: "stft" (framing + DFT + post),
 "unets" (the U-Net pair), "memory", "istft" (inverse pre + DFT + overlap-add).  Timing: HIP events on the stream at the stage
@@ -19,6 +19,12 @@ Separator.separate(..., sample_rate=f) with the two extra stages "resample_in" /
 converts with torch -- one strided conv1d per direction with `up` output channels built from the same polyphase table, the channels
 interleaved into the output -- around composed_separate.  The case also times the conversion alone, kernel against conv1d
 (conv1d, kernel, conv1d), and reports the kernel's achieved HBM bytes per second (input read once + output written once).
+
+--overlap k (driver mode: --overlaps, default 1; 16 kHz only): k one-second segments over every sample, cross-faded.  The new path is
+Separator.separate(..., overlap=k) (csrc/separate.hip: framing with a hop, inverse overlap-add and cross-fade in one kernel).  The
+composed path is what a user could do before it: k calls of Separator.separate on contiguous copies of the recording shifted by
+16000 / k samples, then the weighting with the tiled window and the division by the weights' sum in torch (stage "xfade"; the
+weights are built once, outside the timed window).  Its shifted copies are counted with the "stft" stage of their call.
 
 Weights are synthetic.policy_shapes() with the acoustic memory's weights scaled by 0.25: as generated they are not contractive,
 and a recurrence over 600 steps would overflow expm1.  Every GPU step runs under its own timeout and the driver stops at the
@@ -106,7 +112,7 @@ def composed_separate(sep, stft, istft, wave, tc, mark):
     return y[:, :L].contiguous()
 
 
-def run_case(case, math_name, path, max_segments=None, sample_rate=SEG):
+def run_case(case, math_name, path, max_segments=None, sample_rate=SEG, overlap=1):
     import numpy as np
     import torch
     from m2h import ops, synthetic
@@ -138,7 +144,22 @@ def run_case(case, math_name, path, max_segments=None, sample_rate=SEG):
         marks.append((stage, ev))
 
     resampled = sample_rate != SEG
-    stages = STAGES + (RESAMPLE_STAGES if resampled else ())
+    if overlap != 1 and resampled:
+        raise SystemExit("separate_bench: --overlap is measured at 16 kHz only")
+    stages = STAGES + (RESAMPLE_STAGES if resampled else ()) + (("xfade",) if overlap != 1 else ())
+    if overlap != 1:
+        from m2h.separate import crossfade_window
+        H = SEG // overlap
+        w = torch.from_numpy(crossfade_window()).to(dev)
+        chain_w = [w.repeat(-(-(L - c * H) // SEG))[:L - c * H].contiguous() for c in range(overlap)]
+        W = torch.zeros(L, device=dev)
+        for c in range(overlap):
+            W[c * H:] += chain_w[c]
+
+    class ChainMarks(list):                                   # a chain's own "start" would hide its shifted copy from the stage sums
+        def append(self, item):
+            if item[0] != "start":
+                marks.append(item)
     if resampled:
         to16, back = sep.resamplers(sample_rate)
         c_to16, c_back = ComposedResampler(to16), ComposedResampler(back)
@@ -146,11 +167,27 @@ def run_case(case, math_name, path, max_segments=None, sample_rate=SEG):
     def new_path():
         sep._timing = marks
         try:
-            return sep.separate(wave, tc, use_memory=True, **({"sample_rate": sample_rate} if resampled else {}))
+            return sep.separate(wave, tc, use_memory=True, **({"sample_rate": sample_rate} if resampled else {}), **({"overlap": overlap} if overlap != 1 else {}))
         finally:
             sep._timing = None
 
+    def composed_overlap_path():
+        mark("start")
+        sep._timing = ChainMarks()
+        try:
+            y = torch.zeros((R, L), device=dev)
+            for c in range(overlap):
+                yc = sep.separate(wave[:, :, c * H:].contiguous(), tc, use_memory=True)
+                y[:, c * H:] += chain_w[c] * yc
+            y /= W
+        finally:
+            sep._timing = None
+        mark("xfade")
+        return y
+
     def composed_path():
+        if overlap != 1:
+            return composed_overlap_path()
         with torch.no_grad(), ops.math_scope(math):
             if not resampled:
                 return composed_separate(sep, stft, istft, wave, tc, mark)
@@ -179,7 +216,7 @@ def run_case(case, math_name, path, max_segments=None, sample_rate=SEG):
         return {"audio_s_per_s": R * seconds * reps / (total * 1e-3), "ms_per_run": total / reps,
                 "stage_share": {k: v / total for k, v in stage_ms.items()}}
 
-    res = {"case": case, "R": R, "audio_seconds_per_recording": seconds, "sample_rate": sample_rate, "math": math_name, "reps": reps, "max_segments": sep.max_segments, "chunk_rows": max(1, sep.max_segments // R) * R}
+    res = {"case": case, "R": R, "audio_seconds_per_recording": seconds, "sample_rate": sample_rate, "overlap": overlap, "math": math_name, "reps": reps, "max_segments": sep.max_segments, "chunk_rows": max(1, sep.max_segments // R) * R}
     order = {"new": ("new",), "composed": ("composed",), "both": ("composed", "new", "composed")}[path]
     fns = {"new": new_path, "composed": composed_path}
     outs = {}
@@ -243,22 +280,25 @@ def main():
     ap.add_argument("--max-segments", type=int, default=None, help="the Separator's max_segments (default: its own)")
     ap.add_argument("--sample-rate", type=int, default=SEG, help="the recording's sample rate (one case)")
     ap.add_argument("--sample-rates", type=int, nargs="+", default=[SEG, 44100, 48000], help="driver mode: the rates every case is run at")
+    ap.add_argument("--overlap", type=int, choices=[1, 2, 4], default=1, help="segments over every sample (one case; 16 kHz)")
+    ap.add_argument("--overlaps", type=int, nargs="+", choices=[1, 2, 4], default=[1], help="driver mode: the overlaps every 16 kHz case is run at")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=240, help="driver mode: seconds per case")
     args = ap.parse_args()
     if args.case is not None:
-        run_case(args.case, args.math, args.path, args.max_segments, args.sample_rate)
+        run_case(args.case, args.math, args.path, args.max_segments, args.sample_rate, args.overlap)
         return
     results = []
-    for case, math, rate in [(c, m, r) for r in args.sample_rates for c in ("1x60", "16x600") for m in ("fp32", "bf16x3")]:
+    for case, math, rate, overlap in [(c, m, r, k) for r in args.sample_rates for k in (args.overlaps if r == SEG else [1]) for c in ("1x60", "16x600")
+                                      for m in ("fp32", "bf16x3")]:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case, "--math", math, "--path", args.path,
-               "--sample-rate", str(rate)]
+               "--sample-rate", str(rate), "--overlap", str(overlap)]
         if args.max_segments:
             cmd += ["--max-segments", str(args.max_segments)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             print(r.stdout[-4000:])
-            raise SystemExit("separate_bench: case %s / %s at %d Hz failed with status %d; stopping" % (case, math, rate, r.returncode))
+            raise SystemExit("separate_bench: case %s / %s at %d Hz, overlap %d failed with status %d; stopping" % (case, math, rate, overlap, r.returncode))
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
         results.append(json.loads(line))
         print(line, flush=True)
