@@ -1,21 +1,16 @@
-// extern "C" surface of libm2h.so (see include/m2h.h).  Argument adapters only; kernels live in
-// conv_igemm.hip / layout.hip.
-#include "m2h_internal.h"
+// extern "C" surface of libm2h.so (see include/m2h.h).  Argument adapters only; the conv dispatch lives in
+// conv_dispatch.hip, the kernels in the engines' units (igemm_common.h) / layout.hip.
+#include "igemm_common.h"
 
 namespace m2h {
 thread_local char g_err[512] = {0};
 thread_local const char* tl_last_launch = "";
 thread_local const char* tl_unet_stage[11] = {"", "", "", "", "", "", "", "", "", "", ""};
-struct ConvL1;
-int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1 = nullptr);
 int launch_strip_conv1(const float* mix, const float* masks, const void* wreg, const float* scale, const float* shift, const float* cls_table,
                        const float* cls_val, float* dst, int B, int T, float slope, hipStream_t st, int cls_kind);
 int sep_slice_input_cls(const float* mix, const float* masks, float* out, int B, int F, int T, int split_out, const void* cls_raw, int cls_kind,
                         float* cls_out, hipStream_t st);
-size_t conv_igemm_workspace_bytes(const m2h_conv_args& a);
 thread_local Tuning tl_tuning = {};   // every knob 0 = automatic (m2h_internal.h)
-extern thread_local int tl_math_mode;
-extern thread_local int tl_hi_only;
 }  // namespace m2h
 
 using namespace m2h;

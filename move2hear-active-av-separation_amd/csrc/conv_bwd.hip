@@ -2,7 +2,7 @@
 //
 //   wgrad   dW[n][k] = sum_m dY[m][n] * A[m][k]      (reduction over output pixels m; A gathered exactly as in the forward)
 //           = the weight gradient of Conv2d / Linear in the packed [N][K] layout, K = (tap, channel).
-//   dgrad   runs on the FORWARD engine (conv_igemm.hip): the input gradient of a stride-s conv is s*s sub-pixel phase
+//   dgrad   runs on the FORWARD engines (conv_dispatch.hip): the input gradient of a stride-s conv is s*s sub-pixel phase
 //           convolutions of dY with the (ci <-> co)-transposed, tap-strided weights; m2h_pack_dgrad_weight lays those out.
 //   act_bwd dY * (y > 0 ? 1 : slope)  for the fused ReLU / LeakyReLU epilogues;  bias_grad = column sums of dY.
 //
@@ -15,8 +15,6 @@
 #include "m2h_internal.h"
 
 namespace m2h {
-
-extern thread_local int tl_math_mode;   // conv_igemm.hip: the calling thread's arithmetic
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

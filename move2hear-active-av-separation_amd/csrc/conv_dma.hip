@@ -458,7 +458,7 @@ static int launch_dma_cfg(IGemmP& p, int S, hipStream_t st) {
   const long mtpad = ((long)p.MT + 7) / 8 * 8;
   const long nblk = mtpad * p.NT;
   const int phases = p.convT ? 4 : 1;
-  if (nblk * phases > 0x7fffffffL) return -2;
+  if (nblk * phases > 0x7fffffffL) return NOT_THIS_ENGINE;
   p.pmaj = p.convT ? 1 : 0;
   const dim3 grid((unsigned)(nblk * phases), (unsigned)S, 1);
 #ifdef M2H_CLOCK_DIAG
@@ -503,12 +503,12 @@ static bool dma_split2_applies(const IGemmP& p, size_t ws_bytes) {
 // else -- fewer tiles, 64-wide layers -- is faster on the register engine's two blocks per CU (round 2: down3 125 vs 147 us on this
 // engine's 128 x 128 tile, the first encoder stage 218 vs 251 us on its 256 x 64 tile; both tiles removed).
 int launch_igemm_dma(IGemmP& p, size_t ws_bytes, hipStream_t st) {
-  if (g_dma < 0 || p.math != 1 || !p.presplit || !p.fast_ok || p.head_w != nullptr || p.N % 128 != 0 || p.Kw % BK != 0) return -2;
-  if (p.out_mode != M2H_OUT_NHWC || p.cls_table != nullptr || p.ldc % 4 != 0 || (reinterpret_cast<size_t>(p.dst) & 15) != 0) return -2;   // whole rows through LDS (nhwc_tile_store_T)
-  if ((size_t)(p.C0 > p.C1 ? p.C0 : p.C1) * 4 > 8192) return -2;   // zero page covers one pixel's channels
-  if (p.M <= 64) return -2;        // skinny M: the 32- / 64-row weight-streaming tiles of the register engine
+  if (g_force_splitk > 0 || g_dma < 0 || p.math != 1 || !p.presplit || !p.fast_ok || p.head_w != nullptr || p.N % 128 != 0 || p.Kw % BK != 0) return NOT_THIS_ENGINE;
+  if (p.out_mode != M2H_OUT_NHWC || p.cls_table != nullptr || p.ldc % 4 != 0 || (reinterpret_cast<size_t>(p.dst) & 15) != 0) return NOT_THIS_ENGINE;   // whole rows through LDS (nhwc_tile_store_T)
+  if ((size_t)(p.C0 > p.C1 ? p.C0 : p.C1) * 4 > 8192) return NOT_THIS_ENGINE;   // zero page covers one pixel's channels
+  if (p.M <= 64) return NOT_THIS_ENGINE;        // skinny M: the 32- / 64-row weight-streaming tiles of the register engine
   const int phases = p.convT ? 4 : 1;
-  // tile and split-K factor: the register engine's own rules (conv_igemm_f32), so that the two engines agree bit for bit
+  // tile and split-K factor: the register engine's own rules (launch_igemm_reg / choose_splitk, conv_igemm.hip), so that the two engines agree bit for bit
   const long t256 = (((long)p.M + 255) / 256) * (p.N / 128) * phases;
   if (g_dma == 2 || t256 >= CHIP_TILES)
     return g_dma_shape == 32 ? launch_dma_cfg<256, 128, 4, 2, 3, 32>(p, 1, st) : launch_dma_cfg<256, 128, 4, 2, 3, 16>(p, 1, st);
@@ -521,7 +521,7 @@ int launch_igemm_dma(IGemmP& p, size_t ws_bytes, hipStream_t st) {
   const int S = dma_deep_split(p.M, p.N, p.Kw, phases);
   if (S > 1 && p.ws != nullptr && (size_t)phases * S * p.M * p.N * sizeof(float) <= ws_bytes)
     return g_dma_shape == 32 ? launch_dma_cfg<256, 128, 4, 2, 3, 32>(p, S, st) : launch_dma_cfg<256, 128, 4, 2, 3, 16>(p, S, st);
-  return -2;
+  return NOT_THIS_ENGINE;
 }
 
 #ifdef M2H_CLOCK_DIAG

@@ -651,7 +651,7 @@ static int launch_patch_cfg(IGemmP& p, const PatchGeo& g, int S, hipStream_t st)
   p.S = S;
   p.pmaj = p.convT ? 1 : 0;
   const long nblk = ((long)p.MT + 7) / 8 * 8 * p.NT * (p.convT ? 4 : 1);
-  if (nblk > 0x7fffffffL) return -2;
+  if (nblk > 0x7fffffffL) return NOT_THIS_ENGINE;
   // every tile index is a tile (MT a multiple of 8): a workgroup per CU walks them; otherwise one workgroup per index
   // m2h_tuning_set 10 = n >= 8: n workgroups (a multiple of 8; tests: other tile sequences per
   // workgroup than this chip's CU count gives -- phase and n-tile changing from one tile of a workgroup to its next, many tiles per workgroup)
@@ -676,17 +676,17 @@ static int launch_patch_cfg(IGemmP& p, const PatchGeo& g, int S, hipStream_t st)
 
 // Shapes: what launch_igemm_dma takes at split-K 1 (plus 64-wide layers), restricted to the two window geometries above with the
 // whole window reached and power-of-two pixel grids: whole images per tile (any width), or -- 256 x 128 tile -- some rows of an
-// image 16 / 32 / 64 pixels wide with a patch of at most 384 rows.  Returns -2 otherwise (the caller falls through).
+// image 16 / 32 / 64 pixels wide with a patch of at most 384 rows.  Returns NOT_THIS_ENGINE otherwise (the caller falls through).
 int launch_igemm_patch(IGemmP& p, size_t ws_bytes, hipStream_t st) {
-  if (g_patch < 0 || p.math != 1 || !p.presplit || !p.fast_ok || p.head_w != nullptr || p.N % 64 != 0 || p.N > (p.N % 128 == 0 ? 1024 : 448) || p.Kw != p.K || !(p.slope >= 0.f && p.slope <= 1.f)) return -2;
-  if (p.out_mode != M2H_OUT_NHWC || p.cls_table != nullptr || p.ldc % 4 != 0 || (reinterpret_cast<size_t>(p.dst) & 15) != 0) return -2;
-  if ((size_t)(p.C0 > p.C1 ? p.C0 : p.C1) * 4 > 8192 || p.M <= 64 || p.wq_sh < 0 || p.hq_sh < 0 || p.Hi >= 32768 || p.Wi >= 32768) return -2;
+  if (g_force_splitk > 0 || g_patch < 0 || p.math != 1 || !p.presplit || !p.fast_ok || p.head_w != nullptr || p.N % 64 != 0 || p.N > (p.N % 128 == 0 ? 1024 : 448) || p.Kw != p.K || !(p.slope >= 0.f && p.slope <= 1.f)) return NOT_THIS_ENGINE;
+  if (p.out_mode != M2H_OUT_NHWC || p.cls_table != nullptr || p.ldc % 4 != 0 || (reinterpret_cast<size_t>(p.dst) & 15) != 0) return NOT_THIS_ENGINE;
+  if ((size_t)(p.C0 > p.C1 ? p.C0 : p.C1) * 4 > 8192 || p.M <= 64 || p.wq_sh < 0 || p.hq_sh < 0 || p.Hi >= 32768 || p.Wi >= 32768) return NOT_THIS_ENGINE;
   if (p.convT) {
-    if (p.ntap != 4 || p.ntw != 2 || p.thn != 2 || p.twn != 2 || p.Hq != p.Hi || p.Wq != p.Wi) return -2;
+    if (p.ntap != 4 || p.ntw != 2 || p.thn != 2 || p.twn != 2 || p.Hq != p.Hi || p.Wq != p.Wi) return NOT_THIS_ENGINE;
   } else {
     if (p.ntap != 16 || p.ntw != 4 || p.thn != 4 || p.twn != 4 || p.stride != 2 || p.mulh != 1 || p.mulw != 1 || p.offh != -1 || p.offw != -1 ||
         p.os != 1 || p.ph != 0 || p.pw != 0 || p.Hi != 2 * p.Hq || p.Wi != 2 * p.Wq || p.src1 != nullptr)
-      return -2;
+      return NOT_THIS_ENGINE;
   }
   const int phases = p.convT ? 4 : 1;
   const bool wide = p.N % 128 == 0;
@@ -696,7 +696,7 @@ int launch_igemm_patch(IGemmP& p, size_t ws_bytes, hipStream_t st) {
   // halves of the window as split-K slabs + the ordered reduce kernel (the shape rule of the LDS-DMA engine's two-K-halves launch)
   int S = 1;
   if (g_patch < 2 && tiles < CHIP_TILES) {
-    if (!wide || p.convT || !dma_split2_rule(p.M, p.N, p.Kw, 1, p.ws != nullptr, ws_bytes)) return -2;
+    if (!wide || p.convT || !dma_split2_rule(p.M, p.N, p.Kw, 1, p.ws != nullptr, ws_bytes)) return NOT_THIS_ENGINE;
     S = 2;
   }
   PatchGeo g;
@@ -712,7 +712,7 @@ int launch_igemm_patch(IGemmP& p, size_t ws_bytes, hipStream_t st) {
     g.seg_sh = p.hq_sh + p.wq_sh;
     return wide ? launch_patch_cfg<4, 2, 1>(p, g, S, st) : launch_patch_cfg<8, 1, 1>(p, g, S, st);
   }
-  if (!halo_ok) return -2;
+  if (!halo_ok) return NOT_THIS_ENGINE;
   g.nseg = img >= BM ? 1 : BM / img;
   g.rows = hrows;
   g.W1 = p.Wq + 1;

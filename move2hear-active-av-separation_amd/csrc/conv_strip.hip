@@ -33,8 +33,6 @@
 
 namespace m2h {
 
-extern thread_local int tl_hi_only;   // conv_igemm.hip: M2H_MATH_BF16
-
 // (tuning knob g_strip: thread-local, m2h_internal.h) m2h_tuning_set 35: -1 = the runner never takes the strip-walker kernels (A/B against the tiled engines)
 
 #ifndef M2H_STRIP_DEPTH

@@ -367,12 +367,12 @@ __global__ __launch_bounds__(512, 1) void convT_quad_kernel(const IGemmP p) {
 }
 
 int launch_convT_quad(IGemmP& p, hipStream_t st) {
-  if (g_quad < 0 || !p.convT || p.math != 1 || !p.presplit || !p.fast_ok || p.N > 64) return -2;
-  if (p.Wq < 32 || p.Wq > 128 || 256 % p.Wq != 0 || p.Hq % (256 / p.Wq) != 0 || p.Ctot % 32 != 0 || p.M % 256 != 0) return -2;
-  if (p.head_w != nullptr && p.N > 32) return -2;      // the fused head lives on the 32-wide tile
+  if (g_force_splitk > 0 || g_quad < 0 || !p.convT || p.math != 1 || !p.presplit || !p.fast_ok || p.N > 64) return NOT_THIS_ENGINE;
+  if (p.Wq < 32 || p.Wq > 128 || 256 % p.Wq != 0 || p.Hq % (256 / p.Wq) != 0 || p.Ctot % 32 != 0 || p.M % 256 != 0) return NOT_THIS_ENGINE;
+  if (p.head_w != nullptr && p.N > 32) return NOT_THIS_ENGINE;      // the fused head lives on the 32-wide tile
   if (g_quad == 0) {
-    if (p.N <= 16) return -2;                                            // padded to 32 columns: 290 vs 254 us on the tap-sharing kernel
-    if ((long)p.M * ((p.N + 31) / 32) < 256L * CHIP_TILES) return -2;           // too few output blocks to fill the chip
+    if (p.N <= 16) return NOT_THIS_ENGINE;                                            // padded to 32 columns: 290 vs 254 us on the tap-sharing kernel
+    if ((long)p.M * ((p.N + 31) / 32) < 256L * CHIP_TILES) return NOT_THIS_ENGINE;           // too few output blocks to fill the chip
   }
   p.MT = p.M / 256;
   p.NT = (p.N + 31) / 32;   // 64 wide: two 32-wide n-tiles per output block (four phases x 64 x 32 accumulators per wave do not fit)

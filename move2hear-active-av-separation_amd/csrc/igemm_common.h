@@ -1,5 +1,6 @@
-// Declarations shared by the implicit-GEMM translation units (conv_igemm.hip: the register-staged engine and its dispatch;
-// conv_dma.hip: the LDS-DMA engine for split32 operands): launch parameters, row decode and the fused epilogue.
+// Declarations shared by the implicit-GEMM translation units -- the forward dispatch (conv_dispatch.hip) and its engines (conv_patch.hip,
+// convt_quad.hip, convt_tap.hip, conv_skinny.hip, conv_row3x3.hip, conv_dma.hip, conv_igemm.hip) and the strip walkers (conv_strip.hip):
+// launch parameters, row decode, the fused epilogue and the launcher interface.
 #pragma once
 #include <type_traits>
 
@@ -448,17 +449,39 @@ __device__ __forceinline__ void fused_epilogue(const IGemmP& p, AccT (&acc)[BM /
   }
 }
 
-// conv_igemm.hip: split-K factor of a launch on BM x BN tiles (the one rule of both engines: equal factors keep their results bit-identical)
-int choose_splitk(const IGemmP& p, int BM, int BN, size_t ws_bytes);
+// ---- the forward dispatch (conv_dispatch.hip) and its engines ----
+// conv_igemm_f32 validates the arguments, fills IGemmP and offers the launch to the engines below in the order they are declared; the
+// first one whose shape rule holds takes it.  An engine's unit holds its kernels, their launch code and the rule; the rule reads IGemmP
+// and the tuning knobs only.  A launcher returns NOT_THIS_ENGINE when the launch is not one of its shapes (nothing was launched, the
+// caller goes on down the list; the fields of p that launchers own -- MT, NT, S, pmaj -- are unspecified then, and the engine that takes
+// the launch sets the ones it reads), 0 after a launch, an error code otherwise.
+constexpr int NOT_THIS_ENGINE = -2;
 
-// conv_dma.hip: LDS-DMA engine; returns -2 when the launch is not one of its shapes (the caller falls through), 0 / error otherwise
-int launch_igemm_dma(IGemmP& p, size_t ws_bytes, hipStream_t st);
+int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1 = nullptr);
+size_t conv_igemm_workspace_bytes(const m2h_conv_args& a);   // split-K scratch such a launch can use
 
-// conv_patch.hip: shared-patch LDS-DMA engine (4x4/s2 convs and transposed-conv phases, N % 128 == 0); -2 when not one of its shapes
-int launch_igemm_patch(IGemmP& p, size_t ws_bytes, hipStream_t st);   // p.S == 2 on return: the caller runs splitk_epilogue_kernel
-
-// convt_quad.hip: four-phase transposed-conv kernel (split32 operands, N <= 64); -2 when the launch is not one of its shapes
+// conv_patch.hip: shared-patch LDS-DMA engine (split32 operands, 4x4/s2 convs and transposed-conv phases, N % 64 == 0)
+int launch_igemm_patch(IGemmP& p, size_t ws_bytes, hipStream_t st);   // p.S == 2 on return: the caller runs finish_splitk
+// convt_quad.hip: four-phase transposed-conv kernel (split32 operands, N <= 64)
 int launch_convT_quad(IGemmP& p, hipStream_t st);
+// convt_tap.hip: tap-sharing transposed-conv kernel (bf16x3 math, N <= 64)
+int launch_convT_tap(IGemmP& p, hipStream_t st);
+// conv_skinny.hip: weight-streaming kernels of the small batches (fp32 math): M <= 16 contiguous rows / small pixel counts
+int launch_skinny_rows(IGemmP& p, hipStream_t st);
+int launch_skinny_gather(IGemmP& p, hipStream_t st);
+// conv_row3x3.hip: image-row 3x3 kernels in either arithmetic; l1_loss != nullptr: with the fused L1 loss (p.l1_gt / l1_part / l1_inv set)
+int launch_row3x3(IGemmP& p, float* l1_loss, hipStream_t st);
+// conv_dma.hip: LDS-DMA engine (split32 operands, N % 128 == 0); p.S > 1 on return: the caller runs finish_splitk
+int launch_igemm_dma(IGemmP& p, size_t ws_bytes, hipStream_t st);
+// conv_igemm.hip: register-staged engine; takes every launch (never NOT_THIS_ENGINE) and runs its own split-K reduce
+int launch_igemm_reg(IGemmP& p, size_t ws_bytes, hipStream_t st);
+
+// conv_igemm.hip: tile and split-K factor of the register engine (the one rule of the engines with split-K: equal factors keep their results
+// bit-identical; conv_igemm_workspace_bytes sizes the slabs by it), and the reduce launch that ends a split launch
+void pick_tile(long M, int N, int& BM, int& BN);
+int splitk_for(long M, int N, int K, int phases, int BM, int BN);
+int choose_splitk(const IGemmP& p, int BM, int BN, size_t ws_bytes);
+int finish_splitk(int rc, const IGemmP& p, hipStream_t st, const char* label);
 
 // conv_dma.hip: shape rule of the engine's two-way split-K launch (the fourth encoder stage at the benchmark batch)
 bool dma_split2_rule(long M, int N, int Kw, int phases, bool ws_present, size_t ws_bytes);

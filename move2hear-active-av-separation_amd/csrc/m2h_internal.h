@@ -50,6 +50,11 @@ extern thread_local Tuning tl_tuning;
 // Retired (measured, result recorded in DESIGN.md, removed; accepted by m2h_tuning_set and read by nothing):
 // 1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 15, 16, 17, 19, 20, 26, 29, 31, 32, 33, 34, 38 (and value 8 of knob 36).
 
+// The calling thread's arithmetic (m2h_set_math_mode; defined in conv_dispatch.hip): tl_math_mode 0 fp32 MFMA, 1 bf16x3 split products;
+// tl_hi_only: M2H_MATH_BF16 -- tl_math_mode = 1 for every dispatch decision, and the engines listed in m2h.h drop the two cross products
+extern thread_local int tl_math_mode;
+extern thread_local int tl_hi_only;
+
 // Label of the calling thread's most recent kernel launch (the `what` of launch_status: every launch site names its kernel family):
 // read back by m2h_last_kernel / m2h_unet_fwd_stage_kernel, so that benchmark tables name the kernel that really ran.
 extern thread_local const char* tl_last_launch;

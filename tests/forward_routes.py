@@ -1,10 +1,12 @@
-"""Route table of the forward dispatch (conv_igemm_f32 in csrc/conv_igemm.hip): one row per shape that sits on one side of a threshold
-the dispatch reads, with what the library did with it under default knobs -- the label of m2h_last_kernel, the number of launches
-the call made and the split-K workspace m2h_conv_igemm_workspace_bytes asked for.  The facts are OBSERVED, not derived: they were
+"""Route table of the forward dispatch (conv_igemm_f32 in csrc/conv_dispatch.hip, the engines' shape rules in their own units): one row
+per shape that sits on one side of a threshold the dispatch reads, with what the library did with it under default knobs -- the label of
+m2h_last_kernel, the number of launches the call made, the split-K workspace m2h_conv_igemm_workspace_bytes asked for and the SHA-256 of
+the output's bytes (the inputs are an integer formula, every kernel sums in a fixed order).  The facts are OBSERVED, not derived: they were
 recorded once on an MI355X from the library as it stood before the retired tuning knobs (include/m2h_tuning.h) were removed, and a
 refactor of the dispatch must leave every one of them as it is.  Never regenerate them from the code under test; a pull request
-that means to change a route changes its row by hand and says why.  The recording run, with the SHA-256 of every row's output and the
-kernel trace at both commits, is profiles/forward_routes_parent_vs_branch.txt.
+that means to change a route changes its row by hand and says why.  The recording run, with the kernel trace at both commits, is
+profiles/forward_routes_parent_vs_branch.txt; profiles/forward_split_isa.txt has the run that checked the hashes again before they
+were added here.
 
 Row geometry (kind):
   down  Conv2d(4, 2, 1) as the U-Net runner issues it (down_args in csrc/api.hip); H x W is the OUTPUT pixel grid
@@ -92,68 +94,68 @@ _ROWS = [
     ("row.b60.n32.x3", "c3", 60, 32, 32, 32, 0, 32, "bf16x3", 0),
 ]
 
-# id -> (label of m2h_last_kernel, launches of the call, workspace bytes): as observed, see the module docstring
+# id -> (label of m2h_last_kernel, launches of the call, workspace bytes, SHA-256 of the output bytes): as observed, see the module docstring
 FACTS = {
-    "m16.lin": ("conv_igemm_f32 (skinny rows)", 1, 0),
-    "m17.lin": ("conv_igemm_f32 (skinny gather)", 1, 0),
-    "m14.lin1536": ("conv_igemm_f32 (skinny rows)", 1, 0),
-    "m14.full": ("conv_igemm_f32 (skinny rows)", 1, 14336),
-    "m280.lin512": ("conv_igemm_f32 (skinny gather)", 1, 2293760),
-    "m280.lin1536": ("conv_igemm_f32 (skinny gather)", 1, 6881280),
-    "m32.x3": ("igemm_f32<32,128>", 1, 0),
-    "m33.x3": ("igemm_f32<64,128>", 1, 0),
-    "m64.x3": ("igemm_f32<64,128>", 1, 0),
-    "m65.x3": ("igemm_f32<128,128> + split-K reduce", 2, 133120),
-    "m1024.lin": ("conv_igemm_f32 (skinny gather)", 1, 2097152),
-    "m1025.lin": ("igemm_f32<128,128> + split-K reduce", 2, 2099200),
-    "m4096.tiny": ("conv_igemm_f32 (skinny gather)", 1, 4194304),
-    "m4097.tiny": ("igemm_f32<128,64> + split-K reduce", 2, 4195328),
-    "m4096.w64k": ("igemm_f32<128,128> + split-K reduce", 2, 8388608),
-    "m4097.w64k": ("igemm_f32<128,128> + split-K reduce", 2, 8390656),
-    "n16.t64": ("igemm_f32<128,16> + split-K reduce", 2, 2097152),
-    "n20.t64": ("igemm_f32<128,32> + split-K reduce", 2, 2621440),
-    "n32.t64": ("igemm_f32<128,32> + split-K reduce", 2, 4194304),
-    "n36.t64": ("igemm_f32<128,64> + split-K reduce", 2, 4718592),
-    "n64.t64": ("igemm_f32<128,64> + split-K reduce", 2, 8388608),
-    "n72.t64": ("igemm_f32<128,128> + split-K reduce", 2, 9437184),
-    "n128.t64": ("igemm_f32<128,128> + split-K reduce", 2, 16777216),
-    "n16.t256": ("igemm_f32<128,16>", 1, 0),
-    "n20.t256": ("igemm_f32<128,32>", 1, 0),
-    "n32.t256": ("igemm_f32<128,32>", 1, 0),
-    "n36.t256": ("igemm_f32<128,64>", 1, 0),
-    "n64.t256": ("igemm_f32<128,64>", 1, 0),
-    "n72.t256": ("igemm_f32<128,128>", 1, 0),
-    "n128.t256": ("igemm_f32<128,128>", 1, 0),
-    "t255.lin": ("igemm_f32<128,128> + split-K reduce", 2, 33423360),
-    "t256.lin": ("igemm_f32<128,128>", 1, 0),
-    "x3.t208.plain": ("igemm_f32<128,128>", 1, 0),
-    "x3.t224.plain": ("igemm_f32<256,128> (eight waves)", 1, 0),
-    "x3.t208.split": ("igemm_dma<256,128> + split-K reduce", 2, 54525952),
-    "x3.t224.split": ("igemm_patch<256,128>", 1, 0),
-    "x3.t208.c3": ("igemm_f32<128,128>", 1, 0),
-    "x3.t224.c3": ("igemm_dma<256,128>", 1, 0),
-    "x3.khalves": ("igemm_patch<256,128> + split-K reduce", 2, 33554432),
-    "up.patch64.t220": ("igemm_f32<128,64>", 1, 0),
-    "up.patch64.t224": ("igemm_patch<512,64>", 1, 0),
-    "x3.n64.img4096": ("igemm_f32<128,64>", 1, 0),
-    "up.n16.m32k": ("igemm_convT_tap<16>", 1, 0),
-    "up.n16.m57k": ("igemm_convT_tap<16>", 1, 0),
-    "up.n64.m32k": ("igemm_convT_tap<64>", 1, 0),
-    "up.n64.m57k": ("igemm_convT_tap<64>", 1, 0),
-    "up.n32.m32k.split": ("igemm_convT_tap<32>", 1, 0),
-    "up.n32.m57k.split": ("igemm_convT_quad<32>", 1, 0),
-    "up.n64.m32k.split": ("igemm_convT_quad<64>", 1, 0),
-    "up.n64.m57k.split": ("igemm_convT_quad<64>", 1, 0),
-    "up.n64.m57k.h28": ("igemm_convT_quad<64>", 1, 0),
-    "up.n64.m57k.skip": ("igemm_convT_quad<64>", 1, 0),
-    "row.b64.n16.fp32": ("conv_igemm_f32 (image-row 3x3)", 1, 0),
-    "row.b60.n16.fp32": ("igemm_f32<128,16>", 1, 0),
-    "row.b64.n32.fp32": ("conv_igemm_f32 (image-row 3x3)", 1, 0),
-    "row.b60.n32.fp32": ("igemm_f32<128,32>", 1, 0),
-    "row.b64.n16.x3": ("conv_igemm_bf16x3 (image-row 3x3)", 1, 0),
-    "row.b60.n16.x3": ("igemm_f32<128,16>", 1, 0),
-    "row.b64.n32.x3": ("conv_igemm_bf16x3 (image-row 3x3)", 1, 0),
-    "row.b60.n32.x3": ("igemm_f32<128,32>", 1, 0),
+    "m16.lin": ("conv_igemm_f32 (skinny rows)", 1, 0, "3ae5f1a1d39151e77b8e56961dca24b1453787ccb551b530d09633f5898672ec"),
+    "m17.lin": ("conv_igemm_f32 (skinny gather)", 1, 0, "cce281c1fccae991871c36a1cd70fae6f9a9d5764c04a6f2d0fd17fa51c84fe9"),
+    "m14.lin1536": ("conv_igemm_f32 (skinny rows)", 1, 0, "cee128ade3adf6702deeb141c8b55312c5d502b7bf18f9aa7d2d3ba426c6281e"),
+    "m14.full": ("conv_igemm_f32 (skinny rows)", 1, 14336, "2c2cb32e095b1edbd654321ff04930c65092950e8e49f4a603962e19762e0cf2"),
+    "m280.lin512": ("conv_igemm_f32 (skinny gather)", 1, 2293760, "5b282c46cec9c58ab76db74daaff34593fa87e184d4599fd2a80333aa31338b5"),
+    "m280.lin1536": ("conv_igemm_f32 (skinny gather)", 1, 6881280, "8c453a86673221fdb4bf1b342a2d1b9b63725281d2b68d7b46ee0b4d56f28fa9"),
+    "m32.x3": ("igemm_f32<32,128>", 1, 0, "bacb9bb3d4eeb7f8782df772327c5bc54a4dd11a33d64ed3af6ef7d8eccb075c"),
+    "m33.x3": ("igemm_f32<64,128>", 1, 0, "9f81fb1ae1aa8326aa4882346d803122410336cb2e51b20e7e0a77922c4eaa59"),
+    "m64.x3": ("igemm_f32<64,128>", 1, 0, "ac9f9a76d701e4b9521249cfeaffffdbe0500d06d6d4a50b6d0bd589a562885d"),
+    "m65.x3": ("igemm_f32<128,128> + split-K reduce", 2, 133120, "9c060c206d7c468932ce6449247e4e19f8bf3a9a85cfc990a7b4de984b7fc144"),
+    "m1024.lin": ("conv_igemm_f32 (skinny gather)", 1, 2097152, "19b0ad90f64d1a9cb9396f7db2aaffb2d7817f966330892e666e617a33fc3110"),
+    "m1025.lin": ("igemm_f32<128,128> + split-K reduce", 2, 2099200, "32e5399d12b2679b0aefbfacb54ffa9b734becee28eb7f46a0bfcbf286ddaeb6"),
+    "m4096.tiny": ("conv_igemm_f32 (skinny gather)", 1, 4194304, "98d5a85c4eed2015e3eaf35f430592a5ce0b03bab79bbdb41680186916567fa6"),
+    "m4097.tiny": ("igemm_f32<128,64> + split-K reduce", 2, 4195328, "18a2852b9c67cdd5fea721d5e308ed73cc21a8662ae3f50cc5036f4b400c0278"),
+    "m4096.w64k": ("igemm_f32<128,128> + split-K reduce", 2, 8388608, "d882b6ad1a0c5f7ead6c59f960e3add994c6567dd0771060111a7205e607a943"),
+    "m4097.w64k": ("igemm_f32<128,128> + split-K reduce", 2, 8390656, "0cd2d8113d26724ac1668887a86f88c557e1cca2a3359d3fd3b0c6b7fec6af47"),
+    "n16.t64": ("igemm_f32<128,16> + split-K reduce", 2, 2097152, "caae61b1d0fc3f953d560dca2b7c90531a7174c9cc4109bd8b2fe84e105be735"),
+    "n20.t64": ("igemm_f32<128,32> + split-K reduce", 2, 2621440, "2c3ba2d843a39f0598d22fc47f53966256d254eed1d4d30f58c842931b541aae"),
+    "n32.t64": ("igemm_f32<128,32> + split-K reduce", 2, 4194304, "c56bae346969f916f31e95d03b88cfe9f8c848da02a45e60aef56511347cb124"),
+    "n36.t64": ("igemm_f32<128,64> + split-K reduce", 2, 4718592, "fb642c886023757b49a2d2d3f287f4a2210a4c4e3806c6d3c447707b806cb34e"),
+    "n64.t64": ("igemm_f32<128,64> + split-K reduce", 2, 8388608, "3fe111d3c56c58ec4246e5465aa288cd9e824b752c502a561415101b684c68de"),
+    "n72.t64": ("igemm_f32<128,128> + split-K reduce", 2, 9437184, "652f05c245d7177276de5752e97caeb677f77eb7fcd00cacc3546862dadb81fc"),
+    "n128.t64": ("igemm_f32<128,128> + split-K reduce", 2, 16777216, "c5f94c4f99f10d9b3d5c77450b851ef0e3b02e9e6b64a778374b96786fc35cfd"),
+    "n16.t256": ("igemm_f32<128,16>", 1, 0, "ade8d47ef2590cd5aebb02ebee26e324001a15c2fffddf71d468087823b05b7e"),
+    "n20.t256": ("igemm_f32<128,32>", 1, 0, "251eb887f368bcc1044a309dc7f8bac50e61b175c6ddfa31e3e94ef3575d9316"),
+    "n32.t256": ("igemm_f32<128,32>", 1, 0, "17f18cefab4d7439853e4442a8befc5c1bd79d0e6d4ace7a268e3eb15b41ca06"),
+    "n36.t256": ("igemm_f32<128,64>", 1, 0, "212e61613bcc1d58a31ea5ec0d63f05f23b12be0fa324a91484110d740848215"),
+    "n64.t256": ("igemm_f32<128,64>", 1, 0, "d75fac1be2927dc79f39e7e9e60b0e1b2285d03b913496a3923fa16d936c2e1d"),
+    "n72.t256": ("igemm_f32<128,128>", 1, 0, "b9a0d8e671c63fddff533b5589a9c40855583f01e37f222123239b907279c541"),
+    "n128.t256": ("igemm_f32<128,128>", 1, 0, "9ce0b2f219754a8f313584ed8754419286d07fe419bb3b6f5ac7e9ab508ab2d7"),
+    "t255.lin": ("igemm_f32<128,128> + split-K reduce", 2, 33423360, "c4b238462dc43c006f855c86c1a3a51ac0280193070f2c838cd054aeade876e3"),
+    "t256.lin": ("igemm_f32<128,128>", 1, 0, "09531b88324fbd14cd3199357ffc0b5adcb2746a2a16441764dffa623e76ee1b"),
+    "x3.t208.plain": ("igemm_f32<128,128>", 1, 0, "16f69c58c386ddfab39972128ae11039a514f677f7b29d431f5fcdcbe32dec50"),
+    "x3.t224.plain": ("igemm_f32<256,128> (eight waves)", 1, 0, "74c17fce36f955dc5910091b48312459287d497207398bd03942b98feea44356"),
+    "x3.t208.split": ("igemm_dma<256,128> + split-K reduce", 2, 54525952, "0c9505671045e3dd74e4d4f5526d2a7916aa2078fc380342675fdd2b0eadf3d4"),
+    "x3.t224.split": ("igemm_patch<256,128>", 1, 0, "882398d57af8d6bdeac43f8aee20b774d9c7b4cec31b9abd18635def25133cdb"),
+    "x3.t208.c3": ("igemm_f32<128,128>", 1, 0, "6fda195351ba401f52a53ab8d1155d178cbbd961ea9ae92923e862b14e8ecbe9"),
+    "x3.t224.c3": ("igemm_dma<256,128>", 1, 0, "56699d4fdfff6b2abf09d6c65e0daf611ea220a651108e39620bc7899b457171"),
+    "x3.khalves": ("igemm_patch<256,128> + split-K reduce", 2, 33554432, "9e661ec3507106d94673254a222765b9343e3a308bfe450bedcbd8744eef46a5"),
+    "up.patch64.t220": ("igemm_f32<128,64>", 1, 0, "35775e60854098a1a917e5e0a2cc02fd1fadddb037d5629676bcd5051d245ee5"),
+    "up.patch64.t224": ("igemm_patch<512,64>", 1, 0, "93cf52004fbbe6fb5d7cc87a769d3987fc853037ef613d05c433bc74606e1f72"),
+    "x3.n64.img4096": ("igemm_f32<128,64>", 1, 0, "3ff76e736be055bb06dd1b47de5e341afe12e708d862dde7255a77e881cc0ef3"),
+    "up.n16.m32k": ("igemm_convT_tap<16>", 1, 0, "d1e8ca48b5cd635a52321c32a8b557f977255bbf953e2420b6ebad8b9c1322e7"),
+    "up.n16.m57k": ("igemm_convT_tap<16>", 1, 0, "0e7c1ce27b2e4393edc37c2075c45103775813d488681c44d565f0849385fea1"),
+    "up.n64.m32k": ("igemm_convT_tap<64>", 1, 0, "8dcae0d73bddc5012909f2f8432a6237cb3850e69b196e6c6d368cda42c6bc15"),
+    "up.n64.m57k": ("igemm_convT_tap<64>", 1, 0, "ef055d665f069830b642340f587341f589d2f004033c8cac1e1a47d376eb01e3"),
+    "up.n32.m32k.split": ("igemm_convT_tap<32>", 1, 0, "2d2b1ac3abc4fc1ee29a824dc824c3e216e711d788a7516b1827cd5871d33ae0"),
+    "up.n32.m57k.split": ("igemm_convT_quad<32>", 1, 0, "d259343b5f83d522707414e3035a54e020064db166459e213214a24056971218"),
+    "up.n64.m32k.split": ("igemm_convT_quad<64>", 1, 0, "038daf45d70612f4f8c472e6070e60746451093c83c8dce18f84a7d0e9b98b44"),
+    "up.n64.m57k.split": ("igemm_convT_quad<64>", 1, 0, "510c86cb3ac74aaa18345db58bc374f1f4ed2b5998dd5a3458334083d20ce701"),
+    "up.n64.m57k.h28": ("igemm_convT_quad<64>", 1, 0, "3e3f6339ee718546c718377277d7184f87090b8b815d2dcff7f4f0a90f9fce9c"),
+    "up.n64.m57k.skip": ("igemm_convT_quad<64>", 1, 0, "ddeaeea3bf2a8d0278331057fe1115b2cd13143754e0b7de0e1cd0fe08a396b4"),
+    "row.b64.n16.fp32": ("conv_igemm_f32 (image-row 3x3)", 1, 0, "f7b963aa12dcd6d72ea601c8448e5b56f7fbd5420c6b79595761cfea4add4238"),
+    "row.b60.n16.fp32": ("igemm_f32<128,16>", 1, 0, "3f9a1c126fca1b64be7b0d28fb9bc9142a9cf9ed239fd455e2f7aec5790aea1e"),
+    "row.b64.n32.fp32": ("conv_igemm_f32 (image-row 3x3)", 1, 0, "6012989d549b7b7025792e5500040951822269def54909f7349f089ab43c4b34"),
+    "row.b60.n32.fp32": ("igemm_f32<128,32>", 1, 0, "385a1dcf383ac20ccfdc4b49f35c0c4433017a3130a7e853854226edeb08b02c"),
+    "row.b64.n16.x3": ("conv_igemm_bf16x3 (image-row 3x3)", 1, 0, "8d3da345547bf6ef89527fc30f9a5d4f1f2082b282499f246f8ebce4da576fee"),
+    "row.b60.n16.x3": ("igemm_f32<128,16>", 1, 0, "c288170748e2742a80ed164e4ca0be308d1466b6b0bb38b6a31e90b3e57da366"),
+    "row.b64.n32.x3": ("conv_igemm_bf16x3 (image-row 3x3)", 1, 0, "f1f489694d49f5bb060a36ff627bd809c78da483b2392d6ebc9a4d49937c11c5"),
+    "row.b60.n32.x3": ("igemm_f32<128,32>", 1, 0, "6ce7197771b620d21d806f130b42644a8cfa52945e8a7de5bc21d6271cebb04b"),
 }
 
 KEYS = ("id", "kind", "B", "H", "W", "C0", "C1", "N", "math", "split")

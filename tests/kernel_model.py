@@ -1,4 +1,4 @@
-"""numpy model of the index arithmetic of csrc/conv_igemm.hip + csrc/layout.hip (TEST INFRASTRUCTURE).
+"""numpy model of the index arithmetic of the forward conv units (csrc/conv_dispatch.hip, conv_igemm.hip, conv_row3x3.hip) + csrc/layout.hip (TEST INFRASTRUCTURE).
 
 It restates, in vectorised numpy, exactly the address/tap/phase/de-slice formulas the HIP kernels use, so
 that the *algorithm* (sub-pixel phase decomposition of the transposed conv, in-place skip concat, class
@@ -208,7 +208,7 @@ def convT_tap_phase(x, wp_phase, ph, pw, bm=128):
 
 
 def tap_range(ntaps, Q, stride, off, mul, extent):
-    """Mirror of tap_range() in csrc/conv_igemm.hip: first tap and count of the contiguous run of kernel rows (columns) that reach
+    """Mirror of tap_range() in csrc/conv_dispatch.hip: first tap and count of the contiguous run of kernel rows (columns) that reach
     inside the image for at least one of the Q output rows (columns)."""
     valid = [t for t in range(ntaps) if any(0 <= q * stride + off + t * mul < extent for q in range(Q))]
     if not valid:
@@ -238,7 +238,7 @@ def conv_with_tap_window(x, wp, N, stride, nth, ntw, off, Hq, Wq):
 
 
 def conv3x3_row(x, wp, N, mul):
-    """Mirror of conv3x3_row_kernel's indexing (csrc/conv_igemm.hip): chunks of four image rows staged as a zero-padded 6 x 34
+    """Mirror of conv3x3_row_kernel's indexing (csrc/conv_row3x3.hip): chunks of four image rows staged as a zero-padded 6 x 34
     patch; tap t = (th, tw) reads the patch at the output pixel's own position shifted by (off + th*mul, off + tw*mul),
     off = -mul (forward: mul 1; input gradient: mul -1).  x NHWC [B,H,32,C], wp [N][9*C]."""
     B, H, W, C = x.shape

@@ -10,7 +10,8 @@ def test_every_row_has_facts_and_every_route_a_row():
     assert not missing, missing
     reduced = {lab for lab in labels if lab.startswith("igemm_f32<") and lab.endswith(" + split-K reduce")}
     assert len(reduced) >= 2, reduced
-    for label, launches, wsb in R.FACTS.values():
+    for label, launches, wsb, sha in R.FACTS.values():
+        assert len(sha) == 64 and set(sha) <= set("0123456789abcdef"), sha
         assert launches == (2 if label.endswith(" + split-K reduce") else 1) and wsb >= 0
         assert wsb > 0 or not label.endswith(" + split-K reduce")   # slabs come out of the workspace
 
