@@ -37,6 +37,9 @@
  *                         one launch per direction, > 0: layers of at most that many rows (up to 4 096) -- tests/test_gpu_passive_train.py
  *   39  g_strip_rev       walking direction of the strip kernels' images (bit 0: the masked first stage downwards, bit 1: the last
  *                         stage upwards, bit 2: the unmasked first stage downwards; same values either way) -- tests/test_gpu_unet.py
+ *   40  g_patch_skip      -1: the shared-patch engine's whole-image 256 x 128 tile keeps the MFMAs of pixel fragments that are
+ *                         all top / bottom padding (0: pixel grids 2 x 16, 4 x 16, 2 x 32 skip them; the same bits either way)
+ *                         -- tests/test_gpu_patch_padding.py
  * Retired -- experiments that were measured (results in DESIGN.md) and removed; m2h_tuning_set accepts and stores these numbers, and
  * nothing reads them: 1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 15, 16, 17, 19, 20, 26, 29, 31, 32, 33, 34, 38 (and value 8 of knob 36). */
 #ifndef M2H_TUNING_H
@@ -44,7 +47,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-#define M2H_TUNING_KNOBS 40
+#define M2H_TUNING_KNOBS 41
 int m2h_tuning_set(int knob, int value);
 int m2h_tuning_snapshot(int* out, int n /* == M2H_TUNING_KNOBS */);
 int m2h_tuning_restore(const int* in, int n /* == M2H_TUNING_KNOBS */);

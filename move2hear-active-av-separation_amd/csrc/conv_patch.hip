@@ -60,6 +60,7 @@
 namespace m2h {
 
 // (tuning knob g_patch: thread-local, m2h_internal.h) m2h_tuning_set 36: -1 never use this engine; 2 = also below its tile-count threshold (tests); 3 = as 2, and the whole-image patch wherever it fits
+// (tuning knob g_patch_skip) m2h_tuning_set 40: -1 = the whole-image 256 x 128 tile keeps the MFMAs of fragments that are all padding (SKIP = 0 everywhere)
 
 __device__ __attribute__((aligned(128))) float g_zero_page_patch[2048 + 32];   // 8 KiB + one row: source of padding rows at any channel offset
 
@@ -114,7 +115,14 @@ struct PatchCfg {
 // are the MFMA's A operand, so a lane holds four consecutive channels of one pixel; v_permlane16_swap pairs two fragments into
 // 16-byte pieces of the split32 row).  Stores count in vmcnt in issue order with the DMAs: the two waits that follow an epilogue
 // are for DMAs OLDER than its stores and leave the stores in flight too (+ PST); the third wait is for a DMA issued after them.
-template <int WM, int WN, int WHOLE, int CONVT, int DBG>   // CONVT: a transposed-conv phase (one class per tile); DBG: 9 = the bf16 hi halves only (M2H_MATH_BF16); diagnostic builds only: 4 no MFMAs, 5 no loads, 6 no loads and no k-loop barrier, 7 no k-loop barrier
+// SKIP (WHOLE = 1, image rows of at least 16 pixels, whole images per wave: the launcher's rule): a 16-pixel fragment is (part of) ONE
+// image row, so for the taps that reach over the image's top / bottom edge all 16 of its lanes read the zero rows.  Such a (tap,
+// fragment) pair issues no MFMAs: a wave-uniform bit per pair (`dead`, rebuilt with the address table), a scalar branch around the
+// fragment's MFMAs -- ONE loop body (two compile-time copies of it spilled: DESIGN appendix A).  Its pixel reads stay: conditional
+// ds_reads cost the compiler its exact lgkmcnt counts and measured slower than reading the zeros.  The skipped
+// products have an all-zero operand: for finite weights the accumulators keep their bits.  Left / right padding is per lane and
+// keeps reading the zero rows.
+template <int WM, int WN, int WHOLE, int CONVT, int DBG, int SKIP = 0>   // CONVT: a transposed-conv phase (one class per tile); DBG: 9 = the bf16 hi halves only (M2H_MATH_BF16); diagnostic builds only: 4 no MFMAs, 5 no loads, 6 no loads and no k-loop barrier, 7 no k-loop barrier; SKIP: 1 = no MFMAs for all-padding (tap, fragment) pairs
 __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p, const PatchGeo g, const int ntiles) {
   using Cfg = PatchCfg<WM, WN, WHOLE>;
   constexpr int BM = Cfg::BM, BN = Cfg::BN, A_BYTES = Cfg::A_BYTES, B_BYTES = Cfg::B_BYTES;
@@ -122,6 +130,7 @@ __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p
   constexpr int A_STRIDE = Cfg::A_STRIDE, B_OFF = 2 * A_STRIDE;
   constexpr int PST = FM * FN;   // store instructions of one epilogue (per wave)
   static_assert(WM * WN == PNW && (WHOLE || BM == 256), "tile shape");
+  static_assert(SKIP == 0 || (WHOLE == 1 && WM == 4 && SKIP == 1), "all-padding fragments: whole-image 256 x 128 tile only");
   static_assert(AG == 4 || AG == 6 || AG == 8, "patch DMA groups per wave");
   static_assert(BG == 1 || BG == 2, "weight DMA groups per wave");
   static_assert(BG + AG + PST < 64, "vmcnt field");
@@ -320,12 +329,14 @@ __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p
   // when the class changes (a transposed conv: when the next tile is another phase): the k-loop adds the buffer base and reads.
   // (Computed per read, the whole-image form's edge tests were 60 VALU instructions per k-tile against 18 of the halo form.)
   int atab[4][FM];
+  int dead = 0;   // SKIP: bit 4 tt + mi = fragment mi reads only zero rows at tap tt of the current class (wave-uniform)
   const int W1 = g.W1;
   auto build_atab = [&](int gh, int gw) {
     // (the lane's numbers through an opaque copy: otherwise the compiler hoists every lane-invariant subexpression of this rare
     // rebuild out of the k-loop and keeps ~50 registers alive for it)
     int frow_ = frow, half_ = half;
     asm volatile("" : "+v"(frow_), "+v"(half_));
+    int dm = 0;
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt) {
       const int a = tt >> 1, b = tt & 1;
@@ -343,9 +354,12 @@ __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p
         const int row = seg * g.seg_rows + il * g.W1 + jl + shift;
         const int ad = (row << 7) | (((half_ + (row & 6)) & 7) << 4);
         atab[tt][mi] = (edge & kill) ? A_BYTES + (ad & 255) : ad;   // zeros at the bank slot of the row they replace: the lane group stays conflict-free
+        if constexpr (SKIP != 0) dm |= (edge & kill & 3) ? 1 << (4 * tt + mi) : 0;   // over the top / bottom edge: the same on all 16 pixels when they are one image row
       }
     }
+    if constexpr (SKIP != 0) dead = g.w_sh >= 4 ? __builtin_amdgcn_readfirstlane(dm) : 0;
   };
+  auto is_dead = [&](int bits, int tt, int mi) { return SKIP != 0 && ((bits >> (4 * tt + mi)) & 1) != 0; };
   auto load_a = [&](int buf, auto ttc, auto lo, auto hi) {
 #pragma unroll
     for (int mi = decltype(lo)::value; mi < decltype(hi)::value; ++mi) {
@@ -363,15 +377,18 @@ __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p
   auto mfma = [&](const f32x4& a, const f32x4& b, f32x4& c) {
     if constexpr (DBG != 4) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
   };
-  auto mfma_col = [&](auto lo, auto hi, auto nic) {   // weights as the A operand: a lane ends up with four consecutive channels of one pixel
-    constexpr int ni = decltype(nic)::value;
+  auto mfma_frag = [&](int mi, int ni) {   // weights as the A operand: a lane ends up with four consecutive channels of one pixel
+    if constexpr (DBG != 9) {   // (9: M2H_MATH_BF16, the hi halves only)
+      mfma(bh[ni], al[mi], acc[mi][ni]);
+      mfma(bl[ni], ah[mi], acc[mi][ni]);
+    }
+    mfma(bh[ni], ah[mi], acc[mi][ni]);
+  };
+  auto mfma_col = [&](auto lo, auto hi, auto nic, auto ttc, int bits) {   // one weight fragment against pixel fragments lo .. hi - 1 (bits: the k-tile's dead mask)
 #pragma unroll
     for (int mi = decltype(lo)::value; mi < decltype(hi)::value; ++mi) {
-      if constexpr (DBG != 9) {   // (9: M2H_MATH_BF16, the hi halves only)
-        mfma(bh[ni], al[mi], acc[mi][ni]);
-        mfma(bl[ni], ah[mi], acc[mi][ni]);
-      }
-      mfma(bh[ni], ah[mi], acc[mi][ni]);
+      if (is_dead(bits, decltype(ttc)::value, mi)) continue;
+      mfma_frag(mi, decltype(nic)::value);
     }
   };
   using I0 = std::integral_constant<int, 0>;
@@ -385,6 +402,20 @@ __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p
       }
     };
     go(go, I0{});
+  };
+  // an MFMA-only stretch: every weight fragment against pixel fragments lo .. hi - 1 (SKIP: one test per pixel fragment around its FN
+  // weight fragments; each accumulator's own order of products is the same either way)
+  auto mfma_block = [&](auto lo, auto hi, auto ttc, int bits) {
+    if constexpr (SKIP != 0) {
+#pragma unroll
+      for (int mi = decltype(lo)::value; mi < decltype(hi)::value; ++mi) {
+        if (is_dead(bits, decltype(ttc)::value, mi)) continue;
+#pragma unroll
+        for (int ni = 0; ni < FN; ++ni) mfma_frag(mi, ni);
+      }
+    } else {
+      for_ni([&](auto nic) { mfma_col(lo, hi, nic, ttc, 0); });
+    }
   };
   // cnt: this wave's DMA instructions that may stay in flight (compile-time); stores: the PST stores of the previous tile's
   // epilogue are younger than the awaited DMA and may stay in flight as well (uniform)
@@ -512,9 +543,10 @@ __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p
   auto body = [&](auto ttc, auto cnt, bool stores, auto issue_w, auto issue_p) {
     constexpr int TT = decltype(ttc)::value;
     const int ns = cs + 1 == PNSTB ? 0 : cs + 1;
+    const int cur = SKIP != 0 ? __builtin_amdgcn_readfirstlane(dead) : 0;   // this k-tile's bits (TT == 3: the rebuild below belongs to the NEXT k-tile)
     load_a(ab, ttc, IH{}, IF{});
     __builtin_amdgcn_sched_barrier(0);
-    for_ni([&](auto nic) { mfma_col(I0{}, IH{}, nic); });
+    mfma_block(I0{}, IH{}, ttc, cur);
     wait_and_barrier(cnt, stores);
     int nab = ab;
     if constexpr (TT == 3) {   // the next k-tile opens the next patch
@@ -532,7 +564,7 @@ __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p
     load_a(nab, std::integral_constant<int, (TT + 1) & 3>{}, I0{}, IH{});
     __builtin_amdgcn_sched_barrier(0);
     for_ni([&](auto nic) {
-      mfma_col(IH{}, IF{}, nic);
+      mfma_col(IH{}, IF{}, nic, ttc, cur);
       __builtin_amdgcn_sched_barrier(0);
       load_b(ns, nic);
       if constexpr (decltype(nic)::value == M2H_PATCH_W_AT && decltype(issue_w)::value) issue_weights();
@@ -612,7 +644,7 @@ __global__ __launch_bounds__(64 * PNW, 1) void igemm_patch_kernel(const IGemmP p
   body(T1{}, CW{}, false, N{}, P0{});
   body(T2{}, C0{}, false, N{}, P0{});
   load_a(ab, std::integral_constant<int, 3>{}, IH{}, IF{});
-  for_ni([&](auto nic) { mfma_col(I0{}, IF{}, nic); });
+  mfma_block(I0{}, IF{}, std::integral_constant<int, 3>{}, dead);
   store_tile(c_m0, c_n0, c_phase, std::true_type{});
 
 #ifdef M2H_CLOCK_DIAG
@@ -643,6 +675,24 @@ static int patch_grid_limit() {
   return cus[dev];
 }
 
+// The instantiations that skip the MFMAs of all-padding (tap, fragment) pairs: whole-image 256 x 128 tile, pixel grids 2 x 16, 4 x 16, 2 x 32 -- a
+// fragment is (part of) one image row and every wave holds whole images, so all eight waves have the same number of dead fragments
+// in every k-tile and the k-tile's barrier does not hand the saving back (8 x 64 on the 512 x 64 tile: only wave 0 has any).
+// m2h_tuning_set 40 = -1: never (the kernels without the branches).  Returns whether it launched.
+template <int WM, int WN, int WHOLE>
+static bool launch_patch_skip(const IGemmP& p, const PatchGeo& g, dim3 grid, dim3 blk, int ntiles, hipStream_t st) {
+  if constexpr (WM == 4 && WN == 2 && WHOLE == 1) {
+    if (g_patch_skip < 0 || g.w_sh < 4 || g.rows < 2 || (g.rows << g.w_sh) > 64) return false;
+    if (p.hi_only && p.convT) M2H_LAUNCH((igemm_patch_kernel<4, 2, 1, 1, 9, 1>), grid, blk, 0, st, p, g, ntiles);
+    else if (p.hi_only) M2H_LAUNCH((igemm_patch_kernel<4, 2, 1, 0, 9, 1>), grid, blk, 0, st, p, g, ntiles);
+    else if (p.convT) M2H_LAUNCH((igemm_patch_kernel<4, 2, 1, 1, 0, 1>), grid, blk, 0, st, p, g, ntiles);
+    else M2H_LAUNCH((igemm_patch_kernel<4, 2, 1, 0, 0, 1>), grid, blk, 0, st, p, g, ntiles);
+    return true;
+  } else {
+    return false;
+  }
+}
+
 template <int WM, int WN, int WHOLE>
 static int launch_patch_cfg(IGemmP& p, const PatchGeo& g, int S, hipStream_t st) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
@@ -667,7 +717,8 @@ static int launch_patch_cfg(IGemmP& p, const PatchGeo& g, int S, hipStream_t st)
   else if (g_patch == 7) M2H_LAUNCH((igemm_patch_kernel<WM, WN, WHOLE, 0, 7>), grid, blk, 0, st, p, g, ntiles);
   else
 #endif
-  if (p.hi_only && p.convT) M2H_LAUNCH((igemm_patch_kernel<WM, WN, WHOLE, 1, 9>), grid, blk, 0, st, p, g, ntiles);
+  if (launch_patch_skip<WM, WN, WHOLE>(p, g, grid, blk, ntiles, st)) {}
+  else if (p.hi_only && p.convT) M2H_LAUNCH((igemm_patch_kernel<WM, WN, WHOLE, 1, 9>), grid, blk, 0, st, p, g, ntiles);
   else if (p.hi_only) M2H_LAUNCH((igemm_patch_kernel<WM, WN, WHOLE, 0, 9>), grid, blk, 0, st, p, g, ntiles);
   else if (p.convT) M2H_LAUNCH((igemm_patch_kernel<WM, WN, WHOLE, 1, 0>), grid, blk, 0, st, p, g, ntiles);
   else M2H_LAUNCH((igemm_patch_kernel<WM, WN, WHOLE, 0, 0>), grid, blk, 0, st, p, g, ntiles);

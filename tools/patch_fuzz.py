@@ -2,7 +2,8 @@
 """Randomised cross-check of the shared-patch engine (csrc/conv_patch.hip) against the engines it replaces: random batch, power-of-two
 pixel grids, channel counts (multiples of 32), one / two sources, conv / transposed conv, both patch forms (knob 36 = 2 / 3), each
 layer run through m2h_conv_igemm_f32 with the engine forced and with it switched off (knob 36 = -1: LDS-DMA / register engines),
-compared element by element.  usage: python tools/patch_fuzz.py [--cases 200] [--seed 0]"""
+compared element by element; and with the engine's all-padding skip on and off (knob 40 = 0 / -1: the kernels that leave out the MFMAs
+of fragments above / below their image, and the ones that multiply the zeros), which must agree bit for bit.  usage: python tools/patch_fuzz.py [--cases 200] [--seed 0]"""
 import argparse
 import os
 import random
@@ -56,18 +57,22 @@ def main():
             ops.debug_set(36, knob)
             ops.debug_set(10, grid)
             got, label = _layer(*args)
+            ops.debug_set(40, -1)
+            noskip, noskip_label = _layer(*args)
+            ops.debug_set(40, 0)
             ops.debug_set(36, -1)
             ref, ref_label = _layer(*args)
         finally:
             ops.debug_set(36, 0)
             ops.debug_set(10, 0)
+            ops.debug_set(40, 0)
         if not label.startswith("igemm_patch"):   # a shape the engine refuses (tap window, tiny images): nothing to compare
             skipped += 1
             continue
         ran += 1
         err = float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-20))
         worst = max(worst, err)
-        ok = err < 5e-5 and bool(torch.isfinite(got).all())
+        ok = err < 5e-5 and bool(torch.isfinite(got).all()) and noskip_label == label and torch.equal(got, noskip)
         if not ok or case % 20 == 0:
             print("%s case %3d %-5s B=%d grid %dx%d C0=%d C1=%d Co=%d knob=%d %s vs %s: max err %.2e" % (
                 "ok  " if ok else "FAIL", case, "convT" if transposed else "conv", B, Hq, Wq, C0, C1, Co, knob, label, ref_label, err))
