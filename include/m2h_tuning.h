@@ -40,6 +40,12 @@
  *   40  g_patch_skip      -1: the shared-patch engine's whole-image 256 x 128 tile keeps the MFMAs of pixel fragments that are
  *                         all top / bottom padding (0: pixel grids 2 x 16, 4 x 16, 2 x 32 skip them; the same bits either way)
  *                         -- tests/test_gpu_patch_padding.py
+ *   41  (unassigned: read by nothing)
+ *   42  g_splitk_rows     -1: every split-K reduce launch takes the one-item-per-thread kernel with the run-time slab loop (0: the
+ *                         row-owning kernel with all S slab loads of an item in flight and 8 channels per thread; same bits)
+ *                         -- tests/test_gpu_splitk_reduce.py
+ *   43  g_dma_slab_wt     -1: the LDS-DMA engine's split-K slab stores stay plain (0: write-through, `sc1`; same bits)
+ *                         -- tests/test_gpu_splitk_reduce.py
  * Retired -- experiments that were measured (results in DESIGN.md) and removed; m2h_tuning_set accepts and stores these numbers, and
  * nothing reads them: 1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 15, 16, 17, 19, 20, 26, 29, 31, 32, 33, 34, 38 (and value 8 of knob 36). */
 #ifndef M2H_TUNING_H
@@ -47,7 +53,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-#define M2H_TUNING_KNOBS 41
+#define M2H_TUNING_KNOBS 44
 int m2h_tuning_set(int knob, int value);
 int m2h_tuning_snapshot(int* out, int n /* == M2H_TUNING_KNOBS */);
 int m2h_tuning_restore(const int* in, int n /* == M2H_TUNING_KNOBS */);

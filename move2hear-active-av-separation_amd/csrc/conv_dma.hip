@@ -413,7 +413,12 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void igemm_dma_kernel(const IGemmP
 #pragma unroll
         for (int ni = 0; ni < FN; ++ni) {
           const int n = n0 + wn * TN + ni * 16 + 4 * (lane >> 4);
-          if (n < p.N) *reinterpret_cast<f32x4*>(slab + (size_t)m * p.N + n) = acc[mi][ni];
+          if (n >= p.N) continue;
+          // the workgroup writes this one slab tile and exits: write-through (slab_wt), so that the kernel boundary ahead of the reduce
+          // launch does not find the tile dirty in this XCD's L2
+          char* dp = reinterpret_cast<char*>(slab + (size_t)m * p.N + n);
+          if (p.slab_wt) store16<true>(dp, __builtin_bit_cast(u32x4_t, acc[mi][ni]));
+          else store16<false>(dp, __builtin_bit_cast(u32x4_t, acc[mi][ni]));
         }
       }
       return;
@@ -455,6 +460,7 @@ static int launch_dma_cfg(IGemmP& p, int S, hipStream_t st) {
   p.MT = (p.M + BM - 1) / BM;
   p.NT = (p.N + BN - 1) / BN;
   p.S = S;
+  p.slab_wt = (S > 1 && g_dma_slab_wt >= 0) ? 1 : 0;   // m2h_tuning_set 43: -1 = plain slab stores
   const long mtpad = ((long)p.MT + 7) / 8 * 8;
   const long nblk = mtpad * p.NT;
   const int phases = p.convT ? 4 : 1;

@@ -503,6 +503,152 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(const IGemmP p) {
   }
 }
 
+// The same reduce for the headline's deep stages (m2h_tuning_set 42: -1 = the kernel above everywhere).  The kernel above keeps one
+// 16-byte load in flight per thread (run-time S: every load waits behind the previous add) and decodes its row per item.  Here
+//   - S is a template parameter (2, 3, 4, 8; 0 = run-time loop): all S slab loads of an item are issued before the first add;
+//   - an item is VEC = 8 consecutive channels where N % 8 == 0 (two f32x4 loads per slab; split32: ONE 16-byte hi and ONE 16-byte lo
+//     store), VEC = 4 otherwise;
+//   - a block owns 256 >> tsh whole rows (1 << tsh threads per row, the power of two at or above min(N / VEC, 256)): threads
+//     0 .. rows - 1 decode one row each into LDS while the first item's loads are in flight.
+// Sum order (0 + s0 + s1 + ...), class plane, scale / shift, activation and the hi / lo split are those of the kernel above, bit for bit.
+template <int SC, int VEC>
+__global__ __launch_bounds__(256) void splitk_reduce_rows_kernel(const IGemmP p, const int tsh) {
+  constexpr int Q = VEC / 4;
+  constexpr int SMAX = SC > 0 ? SC : 1;
+  __shared__ int r_out[256], r_bc[256];
+  const int tid = threadIdx.x;
+  const int tpr = 1 << tsh, rows = 256 >> tsh;
+  const int ipr = p.N / VEC;
+  const int phase = blockIdx.y;
+  const int ph = p.convT ? (phase >> 1) : p.ph, pw = p.convT ? (phase & 1) : p.pw;
+  const int r = tid >> tsh, c0 = tid & (tpr - 1);
+  const int m = blockIdx.x * rows + r;
+  const bool live = m < p.M;
+  const size_t slab = (size_t)p.M * p.N;   // floats per slab
+  const float* src = p.ws + ((size_t)phase * p.S * p.M + (live ? m : 0)) * p.N;
+  auto ld = [&](const float* q) { return *reinterpret_cast<const f32x4*>(q); };
+  f32x4 t[SMAX][Q], sc[Q], sh[Q];
+  // an item's loads, all issued before anything waits: the S slab pieces and the channels' scale / shift as vectors (the kernel above
+  // loads them channel by channel behind a test of the pointer each, one memory round trip per channel)
+  auto load_item = [&](int c) {
+    if constexpr (SC > 0) {
+#pragma unroll
+      for (int s = 0; s < SC; ++s)
+#pragma unroll
+        for (int h = 0; h < Q; ++h) t[s][h] = ld(src + (size_t)s * slab + c * VEC + 4 * h);
+    }
+    // (no scale / no shift: the loads re-read the item's first slab piece and a select at the use drops them -- no branch around a load)
+    const float* scp = p.scale != nullptr ? p.scale + c * VEC : src + c * VEC;
+    const float* shp = p.shift != nullptr ? p.shift + c * VEC : src + c * VEC;
+#pragma unroll
+    for (int h = 0; h < Q; ++h) {
+      sc[h] = *reinterpret_cast<const f32x4*>(scp + 4 * h);
+      sh[h] = *reinterpret_cast<const f32x4*>(shp + 4 * h);
+    }
+  };
+  const bool first = live && c0 < ipr;
+  if (first) load_item(c0);
+  if (tid < rows) {
+    const int mr = blockIdx.x * rows + tid;
+    int q, rr, b, out = -1, bc = 0;
+    if (mr < p.M) decode_row(p, mr, ph, pw, q, rr, b, out, bc);
+    r_out[tid] = out;
+    r_bc[tid] = bc;
+  }
+  __syncthreads();
+  if (!live) return;
+  const int out = r_out[r], bc = r_bc[r];
+  const size_t plane = (size_t)p.Ho * p.Wo;
+  const int Cc = p.N >> 4;
+  for (int c = c0; c < ipr; c += tpr) {
+    if (c != c0) load_item(c);
+    const int n0 = c * VEC;
+    f32x4 v[Q];
+#pragma unroll
+    for (int h = 0; h < Q; ++h) v[h] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (SC > 0) {
+#pragma unroll
+      for (int s = 0; s < SC; ++s)
+#pragma unroll
+        for (int h = 0; h < Q; ++h) v[h] += t[s][h];
+    } else {
+      for (int s = 0; s < p.S; ++s)
+#pragma unroll
+        for (int h = 0; h < Q; ++h) v[h] += ld(src + (size_t)s * slab + n0 + 4 * h);
+    }
+    if (p.cls_table != nullptr) {
+      const float cv = p.cls_val[bc >> 4];
+      f32x4 ct[Q];
+#pragma unroll
+      for (int h = 0; h < Q; ++h) ct[h] = *reinterpret_cast<const f32x4*>(p.cls_table + (size_t)(bc & 15) * p.N + n0 + 4 * h);
+#pragma unroll
+      for (int h = 0; h < Q; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[h][j] += cv * ct[h][j];
+    }
+#pragma unroll
+    for (int h = 0; h < Q; ++h)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float x = v[h][j];
+        x = x * (p.scale != nullptr ? sc[h][j] : 1.f) + (p.shift != nullptr ? sh[h][j] : 0.f);
+        v[h][j] = x > 0.f ? x : x * p.slope;
+      }
+    if (p.out_mode == M2H_OUT_NHWC) {
+      if (p.dst_split) {
+        char* base = reinterpret_cast<char*>(p.dst + (size_t)out * p.ldc + (n0 & ~31)) + (n0 & 31) * 2;
+        if constexpr (VEC == 8) {
+          bf16x8 hi, lo;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const bf16x4 hh = __builtin_convertvector(v[h], bf16x4);
+            const bf16x4 ll = __builtin_convertvector(v[h] - __builtin_convertvector(hh, f32x4), bf16x4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              hi[4 * h + j] = hh[j];
+              lo[4 * h + j] = ll[j];
+            }
+          }
+          *reinterpret_cast<bf16x8*>(base) = hi;
+          *reinterpret_cast<bf16x8*>(base + 64) = lo;
+        } else {
+          const bf16x4 hi = __builtin_convertvector(v[0], bf16x4);
+          const bf16x4 lo = __builtin_convertvector(v[0] - __builtin_convertvector(hi, f32x4), bf16x4);
+          *reinterpret_cast<bf16x4*>(base) = hi;
+          *reinterpret_cast<bf16x4*>(base + 64) = lo;
+        }
+      } else {
+#pragma unroll
+        for (int h = 0; h < Q; ++h) *reinterpret_cast<f32x4*>(p.dst + (size_t)out * p.ldc + n0 + 4 * h) = v[h];
+      }
+    } else {
+#pragma unroll
+      for (int h = 0; h < Q; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int n = n0 + 4 * h + j;
+          p.dst[((size_t)out + (size_t)(n & 15) * plane) * Cc + (n >> 4)] = v[h][j];
+        }
+    }
+  }
+}
+
+template <int VEC>
+static void launch_reduce_rows(const IGemmP& p, hipStream_t st) {
+  const int ipr = p.N / VEC;
+  int tsh = 0;
+  while ((1 << tsh) < ipr && tsh < 8) ++tsh;
+  const int rows = 256 >> tsh;
+  const dim3 grid((unsigned)((p.M + rows - 1) / rows), p.convT ? 4 : 1), blk(256);
+  switch (p.S) {
+    case 2: M2H_LAUNCH((splitk_reduce_rows_kernel<2, VEC>), grid, blk, 0, st, p, tsh); break;
+    case 3: M2H_LAUNCH((splitk_reduce_rows_kernel<3, VEC>), grid, blk, 0, st, p, tsh); break;
+    case 4: M2H_LAUNCH((splitk_reduce_rows_kernel<4, VEC>), grid, blk, 0, st, p, tsh); break;
+    case 8: M2H_LAUNCH((splitk_reduce_rows_kernel<8, VEC>), grid, blk, 0, st, p, tsh); break;
+    default: M2H_LAUNCH((splitk_reduce_rows_kernel<0, VEC>), grid, blk, 0, st, p, tsh); break;
+  }
+}
+
 // Tile choice: N picks the width; skinny M (rollout batches, GRU steps: weight-streaming bound, nothing to re-use along M)
 // gets 32- or 64-row tiles so that four times as many blocks stream the weights.
 void pick_tile(long M, int N, int& BM, int& BN) {
@@ -551,10 +697,19 @@ int choose_splitk(const IGemmP& p, int BM, int BN, size_t ws_bytes) {
 // its split-K slabs (p.S per phase); `label` names the pair of launches for m2h_last_kernel
 int finish_splitk(int rc, const IGemmP& p, hipStream_t st, const char* label) {
   if (rc != 0 || p.S == 1) return rc;
-  const long total = (long)p.M * (p.N >> 2);
-  long g = (total + 255) / 256;
-  if (g > 4096) g = 4096;
-  M2H_LAUNCH(splitk_epilogue_kernel, dim3((unsigned)g, p.convT ? 4 : 1), dim3(256), 0, st, p);
+  const auto al16 = [](const void* q) { return (reinterpret_cast<size_t>(q) & 15) == 0; };
+  // (the row-owning kernel reads scale / shift / class table as 16-byte vectors)
+  if (g_splitk_rows >= 0 && al16(p.scale) && al16(p.shift) && al16(p.cls_table)) {
+    // 16-byte pieces of the split32 row need what the fp32 row's f32x4 stores need already: ldc % 4 == 0 and a 16-byte aligned base
+    const bool wide = p.N % 8 == 0 && (!p.dst_split || (p.ldc % 4 == 0 && al16(p.dst)));
+    if (wide) launch_reduce_rows<8>(p, st);
+    else launch_reduce_rows<4>(p, st);
+  } else {
+    const long total = (long)p.M * (p.N >> 2);
+    long g = (total + 255) / 256;
+    if (g > 4096) g = 4096;
+    M2H_LAUNCH(splitk_epilogue_kernel, dim3((unsigned)g, p.convT ? 4 : 1), dim3(256), 0, st, p);
+  }
   rc = launch_status("conv_igemm_f32 split-K epilogue");
   tl_last_launch = label;
   return rc;

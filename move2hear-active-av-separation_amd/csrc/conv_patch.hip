@@ -71,16 +71,6 @@ __device__ unsigned long long g_clock_dbg_patch[8192][16];   // [0] k-loop shade
 
 namespace {
 
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-// one 16-byte store per lane; write-through in M2H_PATCH_WT builds (`sc1`: the bytes go to the memory side at once and the line is not kept
-// dirty in the XCD's L2 -- MI355X_MICROARCH.md, stores of each flavour).  The s_nop keeps the data registers until the store has read
-// them (cdna_hip_programming.md 5.7: an asm store of 12 / 16 bytes).  Counted in vmcnt like any store.
-template <bool WT>
-static __device__ __forceinline__ void store16(char* p, u32x4_t v) {
-  if constexpr (WT) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-  else *reinterpret_cast<u32x4_t*>(p) = v;
-}
-
 constexpr int PNW = 8;          // waves per block
 constexpr int PHALO_ROWS = 384;  // WHOLE = 0: rows of a patch buffer
 constexpr int PNSTB = 3;        // weight stages

@@ -46,6 +46,7 @@ struct IGemmP {
   int th0, thn, tw0, twn, Kw;
   int S;       // split-K factor (grid y); S > 1: raw partial sums go to `ws`, the epilogue runs in splitk_epilogue_kernel
   float* ws;   // [phase][S][M][N] fp32 partial slabs (caller-owned workspace)
+  int slab_wt; // conv_dma.hip: the 16-byte slab stores of a split-K launch leave write-through (sc1)
   // fused L1 loss of the image-row 3x3 kernels (N == 16, NHWC; m2h_conv3x3_l1_nhwc16): l1_gt != nullptr -> the epilogue compares the conv's
   // output with the target plane [B][16 * Ho][Wo] (band n of pixel row q = plane row n * Ho + q), adds |y - g| to the block's partial
   // sum (l1_part[block]) and stores sign(y - g) * l1_inv -- d loss / d y -- in place of y
@@ -66,6 +67,16 @@ struct ConvL1 {
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+// one 16-byte store per lane; write-through with WT (conv_patch.hip's M2H_PATCH_WT builds, conv_dma.hip's split-K slabs) (`sc1`: the bytes go to the memory side at once and the line is not kept
+// dirty in the XCD's L2 -- MI355X_MICROARCH.md, stores of each flavour).  The s_nop keeps the data registers until the store has read
+// them (cdna_hip_programming.md 5.7: an asm store of 12 / 16 bytes).  Counted in vmcnt like any store.
+template <bool WT>
+__device__ __forceinline__ void store16(char* p, u32x4_t v) {
+  if constexpr (WT) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+  else *reinterpret_cast<u32x4_t*>(p) = v;
+}
 
 constexpr int BK = 32;   // k-tile depth (floats)
 constexpr int LDK = 36;  // padded LDS row (floats): 144 B, keeps 16-B alignment, conflict-free b128 reads

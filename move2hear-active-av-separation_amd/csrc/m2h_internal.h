@@ -48,6 +48,8 @@ extern thread_local Tuning tl_tuning;
 // (37: g_bn_small, bn.hip)
 #define g_strip_rev (::m2h::tl_tuning.v[39])
 #define g_patch_skip (::m2h::tl_tuning.v[40])
+#define g_splitk_rows (::m2h::tl_tuning.v[42])
+#define g_dma_slab_wt (::m2h::tl_tuning.v[43])
 // Retired (measured, result recorded in DESIGN.md, removed; accepted by m2h_tuning_set and read by nothing):
 // 1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 15, 16, 17, 19, 20, 26, 29, 31, 32, 33, 34, 38 (and value 8 of knob 36).
 

@@ -176,7 +176,7 @@ class PackItem(ctypes.Structure):
 PACK_BATCH_MAX = 48
 PACK_CONV, PACK_CONVT, PACK_DGRAD, PACK_FC_DGRAD = 0, 1, 2, 3
 STEP_STATS_CHUNKS = 16
-TUNING_KNOBS = 41   # include/m2h_tuning.h
+TUNING_KNOBS = 44   # include/m2h_tuning.h
 ROWS_COPY_MAX = 32
 
 
