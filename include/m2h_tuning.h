@@ -13,7 +13,7 @@
  *   10  g_patch_grid      n >= 8: the shared-patch engine's persistent launches take n workgroups instead of one per CU
  *                         -- tests/test_gpu_patch.py (the grid-size test)
  *   11  g_wgrad_blocks    > 0: block-count target of a weight-gradient launch -- tests/grad_routes.py (rows with S = ...)
- *   12  (tl_tuning.v[12]) -1: narrow weight-gradient blocks always take three k sub-tiles when K allows (0: two where that leaves
+ *   12  g_wgrad_kt3       -1: narrow weight-gradient blocks always take three k sub-tiles when K allows (0: two where that leaves
  *                         fewer padding columns) -- tests/grad_routes.py
  *   14  (api.hip)         = m2h_set_math_mode (kept for older callers; thread-local like it)
  *   18  g_tap_window      -1: walk every tap even where a whole kernel row / column lies in the padding -- tests/test_gpu_unet.py

@@ -466,7 +466,6 @@ __device__ __forceinline__ void fused_epilogue(const IGemmP& p, AccT (&acc)[BM /
 // and the tuning knobs only.  A launcher returns NOT_THIS_ENGINE when the launch is not one of its shapes (nothing was launched, the
 // caller goes on down the list; the fields of p that launchers own -- MT, NT, S, pmaj -- are unspecified then, and the engine that takes
 // the launch sets the ones it reads), 0 after a launch, an error code otherwise.
-constexpr int NOT_THIS_ENGINE = -2;
 
 int conv_igemm_f32(const m2h_conv_args& a, hipStream_t st, const ConvL1* l1 = nullptr);
 size_t conv_igemm_workspace_bytes(const m2h_conv_args& a);   // split-K scratch such a launch can use

@@ -33,7 +33,8 @@ extern thread_local Tuning tl_tuning;
 #define g_force_splitk (::m2h::tl_tuning.v[0])
 #define g_patch_grid (::m2h::tl_tuning.v[10])
 #define g_wgrad_blocks (::m2h::tl_tuning.v[11])
-// (12: read as tl_tuning.v[12] in conv_bwd.hip; 14: m2h_set_math_mode, api.hip)
+#define g_wgrad_kt3 (::m2h::tl_tuning.v[12])
+// (14: m2h_set_math_mode, api.hip)
 #define g_tap_window (::m2h::tl_tuning.v[18])
 #define g_wgrad_row3x3 (::m2h::tl_tuning.v[21])
 #define g_row3x3 (::m2h::tl_tuning.v[22])
@@ -85,6 +86,10 @@ inline int launch_status(const char* what) {
   } while (0)
 
 inline hipStream_t as_stream(m2h_stream s) { return reinterpret_cast<hipStream_t>(s); }
+
+// What a launcher of the forward (igemm_common.h) or weight-gradient (wgrad_common.h) dispatch returns for a launch that is not one of its
+// shapes: nothing was launched, the caller goes on down its list.
+constexpr int NOT_THIS_ENGINE = -2;
 
 // log1p(max(m * (exp(x) - 1), 0)) (separator_cnn.py:77-79) on the hardware transcendental units, raw: v_exp_f32 / v_log_f32 /
 // v_rcp_f32 (~1 ulp each) and log1p(z) = log(u) * z / (u - 1), u = fl(1 + z), which gives back the bits that rounding 1 + z loses

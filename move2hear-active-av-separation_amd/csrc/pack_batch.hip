@@ -2,7 +2,7 @@
 // weights, input-gradient packs of both -- produced by ONE launch from a table of items.  After an optimizer step every weight
 // has changed, so a passive pre-training step re-packed 42 tensors with 42 launches of 10-16 us (0.56 ms of a 4.4 ms step) and
 // a DD-PPO policy epoch 30 (0.15 ms of 2.4 ms); the work itself is ~0.5 GB of HBM traffic.  grid = (blocks, items); the
-// index maps are those of the single-tensor kernels (layout.hip, conv_bwd.hip), bit-identical results.
+// index maps are those of the single-tensor kernels (layout.hip, bwd_pointwise.hip), bit-identical results.
 #include "m2h_internal.h"
 
 namespace m2h {

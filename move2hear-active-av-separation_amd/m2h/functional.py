@@ -2,7 +2,7 @@
 
 PyTorch's autograd engine only orders the calls and accumulates ``.grad`` (plumbing); every gradient value is produced by
 a HIP kernel:
-  conv / linear   dgrad = forward igemm engine on m2h_pack_dgrad_weight phase matrices; wgrad = m2h_conv_wgrad_f32;
+  conv / linear   dgrad = forward igemm engine on m2h_pack_dgrad_weight phase matrices; wgrad = m2h_conv_wgrad_f32 (csrc/conv_bwd.hip);
                   bias = m2h_bias_grad; fused ReLU/LeakyReLU = m2h_act_bwd
 Replaces torch's Conv2d/Linear autograd in audio_separation/rl/ppo/ppo.py:159-161 (update_pol) and :228-230 (update_sep).
 """
@@ -540,7 +540,7 @@ class Conv2dNHWC(torch.autograd.Function):
         need_x = ctx.needs_input_grad[0] or (x2 is not None and ctx.needs_input_grad[1])
         # AcousticMem's first conv over the update batch (3x3 / 1 / 1, 32 channels, 32-pixel rows, no bias, no input gradient): the
         # weight gradient is the only reader of dy, and its image-row kernel applies the activation's derivative as it loads dy
-        # (the predicate mirrors EVERY condition of the library's image-row rule, csrc/conv_bwd.hip `row3x3`: 3x3 / 1 / 1, one 32-channel source,
+        # (the predicate mirrors EVERY condition of the library's image-row rule, csrc/wgrad_row3x3.hip `wgrad_row3x3_rule`: 3x3 / 1 / 1, one 32-channel source,
         # 32-pixel rows, output grid == image (Ho x Wo == H x W: "direct"), N <= 32 and N % 4 == 0, dy rows N floats apart (contiguous NHWC: ldy % 4),
         # one weight tile (N <= 32, K = 288 <= one k-tile group) -- a shape that passed here and failed there would raise inside backward)
         gated = (slope != 1.0 and ctx.needs_input_grad[2] and not need_x and not ctx.needs_input_grad[3] and x2 is None and

@@ -58,7 +58,7 @@ def near_target_config(**over):
              #                            kernels wait for the gaps between them instead of running beside them
              sep_update_math=None,      # build-side key: arithmetic of update_sep's launches (AcousticMem over the 1680 stored samples: the one matrix-bound
              #                            phase of the cycle): None = the calling thread's mode; "bf16x3" = split bf16 products, fp32 accumulate (the
-             #                            image-row kernels of csrc/conv_row3x3.hip / conv_bwd.hip: ~6e-6 from the fp32 result, 1.36 -> 0.75 ms per epoch)
+             #                            image-row kernels of csrc/conv_row3x3.hip / wgrad_row3x3.hip: ~6e-6 from the fp32 result, 1.36 -> 0.75 ms per epoch)
              action_sampling="fused")  # build-side key: "fused" = torch.multinomial's single draw with its Exp(1) noise made inside the heads kernel
     #                                     (Philox4x32-10, seed = SEED + rank offset, counter on the device: no generator launch in the step);
     #                                     "device" = the noise from torch's device generator; "cpu_generator" = from the CPU default generator:

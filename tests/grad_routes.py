@@ -1,7 +1,7 @@
-"""Restatement of the weight-gradient dispatch of csrc/conv_bwd.hip (TEST INFRASTRUCTURE) and the table of gradient test rows.
+"""Restatement of the weight-gradient dispatch of csrc/conv_bwd.hip and its kernel families' rules (TEST INFRASTRUCTURE) and the table of gradient test rows.
 
 ``wgrad_cfg`` / ``wgrad_splits`` / ``route`` restate, in plain Python, the block shape, split count and reduce / epilogue kernel the
-library picks for a launch (conv_bwd.hip: wgrad_cfg, wgrad_splits, conv_wgrad_f32).  ``ROWS`` is the table the GPU test
+library picks for a launch (wgrad_tiled.hip: wgrad_cfg; conv_bwd.hip: wgrad_splits, conv_wgrad_f32; wgrad_reduce.hip: wgrad_finish).  ``ROWS`` is the table the GPU test
 tests/test_gpu_grad_routes.py runs against fp64; tests/test_grad_routes_cpu.py checks, without a GPU, that the table reaches every
 route cell below and that the library's workspace sizes agree with the restated split counts (a dispatch change that moves a row to
 another route then fails on a CPU box).
@@ -61,7 +61,7 @@ def geometry(row):
 
 
 def is_row3x3(row):
-    """The image-row 3x3 kernels' shapes (conv_bwd.hip wgrad_row3x3_shape): not a route of this table."""
+    """The image-row 3x3 kernels' shapes (wgrad_row3x3.hip wgrad_row3x3_rule): not a route of this table (tests/wgrad_routes.py pins them)."""
     return (row["op"] != "convT" and row["k"] == 3 and row["s"] == 1 and row["p"] == 1 and row["C0"] == 32 and row["C1"] == 0 and
             row["W"] == 32 and row["Co"] <= 32 and row["Co"] % 4 == 0)
 

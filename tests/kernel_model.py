@@ -263,7 +263,7 @@ def conv3x3_row(x, wp, N, mul):
 
 
 def wgrad3x3_row(x, dy):
-    """Mirror of wgrad3x3_row_kernel's indexing (csrc/conv_bwd.hip): one image row per chunk staged as a zero-padded 3 x 34 patch,
+    """Mirror of wgrad3x3_row_kernel's indexing (csrc/wgrad_row3x3.hip): one image row per chunk staged as a zero-padded 3 x 34 patch,
     each of the four waves takes 8 pixels, tap (ty, tx) reads patch row ty at column pixel + tx; -> dW packed [N][9*C]."""
     B, H, W, C = x.shape
     N = dy.shape[3]
@@ -286,7 +286,7 @@ def wgrad3x3_row(x, dy):
 
 
 def wgrad3x3_row_bf16x3(x, dy, splits):
-    """Mirror of wgrad3x3_row_bf16x3_kernel's indexing (csrc/conv_bwd.hip, round 4), in bf16x3 arithmetic: a split walks its image rows
+    """Mirror of wgrad3x3_row_bf16x3_kernel's indexing (csrc/wgrad_row3x3.hip, round 4), in bf16x3 arithmetic: a split walks its image rows
     c0 .. c1-1 of the flattened (b, row) list; x rows live TRANSPOSED ([channel][32 pixels]) in a ring of four slots (slot = row & 3: step c
     reads slots of rows c-1, c, c+1 while row c+2 arrives), rows outside the image are skipped; the tap's column shift is applied to
     dY -- dW[n][ty][tx][c] += sum_px' dY[px' - tx + 1][n] * x[row + ty - 1][px'][c], zeros shifted in at the row ends -- and one product is
@@ -329,7 +329,7 @@ def wgrad3x3_row_bf16x3(x, dy, splits):
 
 
 def wgrad_reduce_torch(slabs, Ci, KH, KW):
-    """Mirror of conv_wgrad_reduce_torch_kernel (csrc/conv_bwd.hip): the split sum in the reduce kernels' order (S < 16: one running sum;
+    """Mirror of conv_wgrad_reduce_torch_kernel (csrc/wgrad_reduce.hip): the split sum in the reduce kernels' order (S < 16: one running sum;
     else four quarters of eight interleaved running sums, pairwise) and the re-layout packed [n][(tap, c)] -> torch [n][c][kh][kw], channels
     from Ci on dropped."""
     S, N, K = slabs.shape

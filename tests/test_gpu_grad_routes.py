@@ -1,4 +1,4 @@
-"""GPU: every weight-gradient route of csrc/conv_bwd.hip (six block shapes x four split classes, the reduce / re-layout epilogues, the
+"""GPU: every weight-gradient route of csrc/conv_bwd.hip's dispatch (the tiled kernel of wgrad_tiled.hip: six block shapes x four split classes, the reduce / re-layout epilogues, the
 shipped layer shapes of the passive step and of update_pol's encoders) and the input / bias gradients at the same shapes, element by
 element against CPU float64 autograd from the same fp32 inputs.
 
@@ -111,7 +111,7 @@ def _packed(t4):
 
 def _mutants(row, f, x, w, dz, r_w):
     """The fp64 reference after each of three changes the bound must reject: one split's rows removed (the last split, with the ragged tail:
-    chunks [c0, c1) of conv_bwd.hip's split map), the gradient scaled by (1 - 1/S), the largest tap column zeroed."""
+    chunks [c0, c1) of wgrad_tiled.hip's split map), the gradient scaled by (1 - 1/S), the largest tap column zeroed."""
     rt = G.route(row)
     S, M = rt["S"], rt["M"]
     chunks = G.cdiv(M, G.WM)
