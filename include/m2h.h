@@ -622,6 +622,12 @@ int m2h_sep_stft_post(const float* spec, float* mag, float* phasor, int N, m2h_s
  * [512 + k] = expm1(max(P, 0)) * Im. */
 int m2h_sep_istft_pre(const float* P, const float* phasor, float* rows, int N, m2h_stream stream);
 
+/* The binaural target: spec as m2h_sep_stft_post takes it, masks BHWC [N][512][32][2] (the first U-Net's)  ->  rows, the shape and
+ * row order of spec: rows[(n*2 + c)*32 + t][k] = max(masks[n][k][t][c], 0) * spec[...][k], and the same factor on [512 + k] -- the
+ * mixture's own spectrum of channel c scaled by the clamped mask, the inverse GEMM's operand for 2N signals.  All 1024 columns are
+ * written.  rows == spec (the same pointer) is allowed and works in place; any other overlap of the two is the caller's error. */
+int m2h_sep_bin_rows(const float* spec, const float* masks, float* rows, int N, m2h_stream stream);
+
 /* frames [n*32 + t][1024] (the inverse GEMM's output, 1022 samples per row), window: periodic Hann(1022)  ->  windowed
  * overlap-add with window-sum-of-squares normalisation (m2h_istft_ola's arithmetic), segment s written to
  * y[r][s*16000 .. ) of y [R][L] and cut at L. */

@@ -158,6 +158,54 @@ __global__ __launch_bounds__(256) void sep_istft_pre_kernel(const float* __restr
   }
 }
 
+// The binaural target (m2h/separate.py, output="binaural"): the mixture's own spectrum of channel c scaled by the clamped mask of the
+// first U-Net.  spec rows [(n*2 + c)*32 + t][1024] = [Re | Im], masks BHWC [n][512][32][2]  ->  rows, same shape and row order:
+// [k] = max(masks[n][k][t][c], 0) * Re, [512 + k] = max(masks[n][k][t][c], 0) * Im -- the inverse GEMM's operand for 2N signals.
+// Masks are bin-major and rows frame-major: the workgroup's 8 KB of masks are read contiguously and transposed through LDS.
+// rows == spec is allowed (no __restrict__ on either): a workgroup owns the 64 rows x 2 x 32 columns it reads, all of its loads are
+// issued before the barrier and all of its stores after it, and every thread stores to the addresses it loaded from.
+__global__ __launch_bounds__(256) void sep_bin_rows_kernel(const float* spec, const float* __restrict__ masks, float* rows, int N) {
+  __shared__ float tile[2][SEP_KT][SEP_T + 1];              // [c][kk][t]
+  const int ktiles = SEP_NB / SEP_KT;
+  const int n = blockIdx.x / ktiles;
+  const int k0 = (blockIdx.x % ktiles) * SEP_KT;
+  if (n >= N) return;
+  const size_t base = (size_t)n * 2 * SEP_T * SEP_LD;
+  // 64 rows x 2 parts x 8 float4 = 1024 loads, four per thread, kept in registers across the barrier
+  float4 x[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int q = threadIdx.x + i * 256;
+    const int v4 = q % (SEP_KT / 4);
+    const int part = (q / (SEP_KT / 4)) & 1;
+    const int row = q / (2 * (SEP_KT / 4));
+    x[i] = *reinterpret_cast<const float4*>(spec + base + (size_t)row * SEP_LD + part * SEP_NB + k0 + v4 * 4);
+  }
+  // 32 bins x 32 frames x 2 channels, contiguous: two float4 per thread, each = (t, c0), (t, c1), (t + 1, c0), (t + 1, c1) of one bin
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int q = threadIdx.x + i * 256;
+    const float4 m = *reinterpret_cast<const float4*>(masks + (((size_t)n * SEP_NB + k0) * SEP_T * 2 + (size_t)q * 4));
+    const int kk = q / (SEP_T / 2), t = (q % (SEP_T / 2)) * 2;
+    tile[0][kk][t] = fmaxf(m.x, 0.f);
+    tile[1][kk][t] = fmaxf(m.y, 0.f);
+    tile[0][kk][t + 1] = fmaxf(m.z, 0.f);
+    tile[1][kk][t + 1] = fmaxf(m.w, 0.f);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int q = threadIdx.x + i * 256;
+    const int v4 = q % (SEP_KT / 4);
+    const int part = (q / (SEP_KT / 4)) & 1;
+    const int row = q / (2 * (SEP_KT / 4));            // c*32 + t
+    const int c = row / SEP_T, t = row % SEP_T;
+    const float4 y = make_float4(tile[c][v4 * 4][t] * x[i].x, tile[c][v4 * 4 + 1][t] * x[i].y, tile[c][v4 * 4 + 2][t] * x[i].z,
+                                 tile[c][v4 * 4 + 3][t] * x[i].w);
+    *reinterpret_cast<float4*>(rows + base + (size_t)row * SEP_LD + part * SEP_NB + k0 + v4 * 4) = y;
+  }
+}
+
 // Sample j of one segment's inverse transform: fr = the segment's 32 rows of the inverse GEMM, at most two frames cover a sample.
 __device__ __forceinline__ float sep_ola_sample(const float* __restrict__ fr, const float* __restrict__ window /* [1022] */, int j) {
   const int jj = j + SEP_NIFFT / 2;
@@ -320,6 +368,14 @@ int m2h_sep_istft_pre(const float* P, const float* phasor, float* rows, int N, m
   M2H_REQUIRE(aligned16(P) && aligned16(phasor) && aligned16(rows), "sep_istft_pre: buffers must be 16-byte aligned");
   M2H_LAUNCH(sep_istft_pre_kernel, dim3((unsigned)N * (SEP_NB / SEP_KT)), dim3(256), 0, as_stream(stream), P, phasor, rows, N);
   return launch_status("sep_istft_pre");
+}
+
+int m2h_sep_bin_rows(const float* spec, const float* masks, float* rows, int N, m2h_stream stream) {
+  M2H_REQUIRE(spec && masks && rows, "sep_bin_rows: null pointer");
+  M2H_REQUIRE(N > 0 && N <= (1 << 20), "sep_bin_rows: bad sizes (N %d)", N);
+  M2H_REQUIRE(aligned16(spec) && aligned16(masks) && aligned16(rows), "sep_bin_rows: buffers must be 16-byte aligned");
+  M2H_LAUNCH(sep_bin_rows_kernel, dim3((unsigned)N * (SEP_NB / SEP_KT)), dim3(256), 0, as_stream(stream), spec, masks, rows, N);
+  return launch_status("sep_bin_rows");
 }
 
 int m2h_sep_istft_ola(const float* frames, const float* window, float* y, int R, long long L, int s0, int nseg, m2h_stream stream) {

@@ -273,6 +273,7 @@ SIGNATURES = {
     "m2h_sep_frames": [_P, _P, _P, _I, _L, _I, _I, _P],
     "m2h_sep_stft_post": [_P, _P, _P, _I, _P],
     "m2h_sep_istft_pre": [_P, _P, _P, _I, _P],
+    "m2h_sep_bin_rows": [_P, _P, _P, _I, _P],
     "m2h_sep_istft_ola": [_P, _P, _P, _I, _L, _I, _I, _P],
     "m2h_sep_frames_hop": [_P, _P, _P, _I, _L, _I, _I, _I, _P],
     "m2h_sep_istft_xfade": [_P, _P, _P, _P, _I, _L, _I, _I, _I, _P],

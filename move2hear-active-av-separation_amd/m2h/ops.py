@@ -1122,6 +1122,26 @@ def sep_istft_pre(P, phasor, out=None):
     return out
 
 
+def sep_bin_rows(spec, masks, out=None):
+    """The forward GEMM's [Re | Im] rows [N*2*32, 1024] and the first U-Net's masks BHWC [N,512,32,2] -> the inverse DFT GEMM's rows
+    for the binaural target, the shape and row order of spec: max(mask, 0) * (re | im) of the mask's own channel
+    (m2h_sep_bin_rows).  out=None works in place and returns spec; out must otherwise not overlap spec."""
+    _chk(spec, "sep_bin_rows(spec)")
+    _chk(masks, "sep_bin_rows(masks)")
+    N = masks.shape[0]
+    if tuple(masks.shape) != (N, SEP_BINS, SEP_FRAMES, 2) or tuple(spec.shape) != (N * 2 * SEP_FRAMES, SEP_LD):
+        raise RuntimeError("m2h.sep_bin_rows: expected masks [N,512,32,2] and spec [N*64, %d], got %s and %s" % (SEP_LD, tuple(masks.shape), tuple(spec.shape)))
+    if out is None:
+        out = spec
+    else:
+        _chk(out, "sep_bin_rows(out)")
+        if tuple(out.shape) != tuple(spec.shape):
+            raise RuntimeError("m2h.sep_bin_rows: out must be [%d, %d], got %s" % (N * 2 * SEP_FRAMES, SEP_LD, tuple(out.shape)))
+    with torch.cuda.device(spec.device):
+        _lib.check(_lib.load().m2h_sep_bin_rows(_ptr(spec), _ptr(masks), _ptr(out), N, _stream(spec)), "m2h_sep_bin_rows")
+    return out
+
+
 def sep_istft_ola(frames, window, y, s0, nseg):
     """The inverse GEMM's rows [nseg*R*32, 1024] -> windowed overlap-add of segments [s0, s0+nseg) written at their offsets of
     y [R, L], cut at L (m2h_sep_istft_ola).  window: periodic Hann(1022)."""

@@ -4,6 +4,7 @@
     mono = sep.separate(wave, target_class)          # wave [R, 2, L] (or [2, L]) fp32 at 16 kHz  ->  [R, L]
     mono = sep.separate(wave, target_class, sample_rate=44100)     # any supported rate in, the same rate and length out
     mono = sep.separate(wave, target_class, overlap=2)             # one-second segments every half second, cross-faded
+    binaural = sep.separate(wave, target_class, output="binaural") # the target in both ears, [R, 2, L]; "both": (mono, binaural)
 
 Semantics (the CPU statement of the same thing is tests/separate_ref.py):
   * the recording is cut into S = ceil(L / 16000) non-overlapping one-second segments -- the agent's steps; samples at or past L are zero;
@@ -38,6 +39,28 @@ outside the recording -- scipy.signal.resample_poly(x, up, down, padtype="consta
 recording has L16 = ceil(L * 16000 / f) samples; its back-conversion never has fewer than L.  Spectrograms are those of the
 16 kHz recording.  Rates with max(up, down) <= 1024 are supported (tests/resample_ref.py is the CPU statement).
 
+Binaural target (``output="binaural"`` -> [R, 2, L], ``output="both"`` -> (mono, binaural); tests/separate_binaural_ref.py is the CPU
+statement).  The first U-Net predicts the target in both ears: its two masks times the mixture magnitude are the separated binaural
+magnitude the reference trains and scores.  For every segment s and recording r, X_c [512, 32] (the segment's spectrum of channel c),
+M = log1p|X| and m = get_binSepMasks({M, target_class}) [512, 32, 2] are exactly what the mono path uses, and
+  * the predicted spectrum of channel c is the mixture's own complex spectrum scaled by the clamped mask, Y_c = max(m[..., c], 0) * X_c:
+    magnitude max(m_c |X_c|, 0) -- the clamp the second U-Net's input applies -- with the phase of X_c.  No phase is invented, and
+    there is no phasor, no log1p / expm1 round trip and no second U-Net on this path;
+  * v_{s,c} = np_istft(Y_c as complex64, hop 512, length 16000), the evaluation path's inverse transform as for the mono output;
+  * the segments are placed exactly as for the mono output, each channel on its own: overlap=1 concatenated and cut at L, overlap=k
+    cross-faded with the same window and normalisation, sample_rate=f both channels converted back with the same Resampler;
+  * the acoustic memory and convert_bin2mono take no part: use_memory=True with output="binaural" is a ValueError.  With "both" the
+    transform and the first U-Net run once, the binaural branch of a chunk finishes before the second U-Net starts, and the mono
+    output is the "mono" call's bit for bit.
+  The path is NOT transparent at m == 1: the reference's forward transform has n_fft 1023 and its inverse 1022 (the mono path inherits
+  the same convention), and on the CPU np_istft(np_stft(segment)) reproduces the end-to-end test signal (noise plus one tone per
+  channel) only to rel-L1 0.44 (0.27 .. 0.61 per channel, with the tone's frequency).  A mask of ones is not an identity, and
+  nothing here promises one.
+  The clamp is live: with the synthetic test weights about 54 % of the mask values are negative (mask range -11.5 .. 13.3).
+In HIP: m2h_sep_bin_rows scales the forward GEMM's rows in place (masks are bin-major, rows frame-major: a transpose through LDS) into
+the inverse GEMM's operand, and the inverse GEMM's rows are those of 2R mono recordings -- row ((sl*R + r)*2 + c)*32 + t is row
+((sl*2R + (2r + c))*32 + t -- so m2h_sep_istft_ola / m2h_sep_istft_xfade write the contiguous [R, 2, L] result viewed as [2R, L].
+
 The two DFTs are dense 1024 x 1024 GEMMs (ops.linear) and follow the calling thread's arithmetic like the U-Nets; framing, the
 magnitude / phasor store, the inverse transform's operand and the overlap-add are the HIP kernels of csrc/separate.hip, which
 read the recording and write the output in place: no padded, framed or angle copies.
@@ -56,6 +79,7 @@ MEMORY_ROOT = "acoustic_mem."
 # 1024 rows hold 0.5 GB of transform buffers and half the activations of the benchmark's batch (256 spectrograms of 512 x 256).
 DEFAULT_MAX_SEGMENTS = 1024
 OVERLAPS = (1, 2, 4)
+OUTPUTS = ("mono", "binaural", "both")
 
 
 def segment_plan(L, max_segments):
@@ -180,16 +204,26 @@ class Separator:
         return self._resamplers[key]
 
     @torch.no_grad()
-    def separate(self, wave, target_class, use_memory=None, return_spectrograms=False, sample_rate=SAMPLE_RATE, overlap=1):
+    def separate(self, wave, target_class, use_memory=None, return_spectrograms=False, sample_rate=SAMPLE_RATE, overlap=1, output="mono"):
         """wave [R, 2, L] or [2, L] fp32 on this separator's device, L >= 1; target_class: an int or one per recording.
         Returns the separated waveform [R, L] ([L] for a [2, L] input); with return_spectrograms also P [R, S, 512, 32] (the
         log1p magnitude the inverse transform was given) and the phasor [R, S, 512, 32, 2].  sample_rate: the recording's rate;
         other than 16000 the recording is converted to 16 kHz and the result back (module docstring), the output has the
         input's rate and length, and S counts the seconds of the 16 kHz recording.  overlap: 1, 2 or 4 one-second segments over
-        every sample, cross-faded (module docstring); S is then ceil(L / (16000 / overlap)), in segment order."""
+        every sample, cross-faded (module docstring); S is then ceil(L / (16000 / overlap)), in segment order.
+        output: "mono" (the above), "binaural" or "both" (module docstring, "Binaural target").  "binaural" returns the target in both
+        ears [R, 2, L] ([2, L] for a [2, L] input), with return_spectrograms also the first U-Net's masks [R, S, 512, 32, 2]; it runs
+        no memory, and use_memory=True given with it is a ValueError.  "both" returns (mono, binaural), with return_spectrograms
+        (mono, binaural, P, phasor, masks); its mono is the "mono" call's bit for bit."""
         if isinstance(overlap, bool) or overlap not in OVERLAPS:
             raise ValueError("m2h.Separator: overlap must be one of %s, got %r" % (OVERLAPS, overlap))
         overlap = int(overlap)
+        if not isinstance(output, str) or output not in OUTPUTS:
+            raise ValueError("m2h.Separator: output must be one of %s, got %r" % (OUTPUTS, output))
+        want_mono, want_bin = output != "binaural", output != "mono"
+        if not want_mono and use_memory:
+            raise ValueError("m2h.Separator: output=\"binaural\" runs no acoustic memory (it refines the mono prediction only); "
+                             "leave use_memory at None or False, or ask for output=\"both\"")
         if not torch.is_tensor(wave):
             raise RuntimeError("m2h.Separator: wave must be a torch tensor, got %s" % type(wave).__name__)
         single = wave.dim() == 2
@@ -202,7 +236,7 @@ class Separator:
         if wave.device != self.device:
             raise RuntimeError("m2h.Separator: wave lives on %s, the separator on %s" % (wave.device, self.device))
         if use_memory is None:
-            use_memory = self.memory is not None
+            use_memory = want_mono and self.memory is not None
         if use_memory and self.memory is None:
             raise RuntimeError("m2h.Separator: use_memory=True, but the checkpoint has no acoustic_mem.cnn.* weights")
         wave = wave.contiguous()
@@ -222,8 +256,9 @@ class Separator:
         if tc.numel() != R:
             raise RuntimeError("m2h.Separator: target_class must be one int or one per recording (%d), got %d values" % (R, tc.numel()))
         tc = tc.to(self.device).contiguous()
-        y = torch.empty((R, L), device=self.device, dtype=torch.float32)
-        keep_P, keep_ph = [], []
+        y = torch.empty((R, L), device=self.device, dtype=torch.float32) if want_mono else None
+        yb = torch.empty((R, 2, L), device=self.device, dtype=torch.float32) if want_bin else None
+        keep_P, keep_ph, keep_m = [], [], []
         prev = None
         hop = SEGMENT // overlap
         if overlap > 1 and self._win_xfade is None:
@@ -239,10 +274,31 @@ class Separator:
                     frames = ops.sep_frames_hop(wave, self._win_fwd, hop, s0, ns)
                 spec = ops.linear(frames, self._W_fwd, None, name="separate.dft")
                 mag, phasor = ops.sep_stft_post(spec, N)
-                del frames, spec
+                del frames
+                if not want_bin:
+                    del spec
                 self._mark("stft")
                 obs = {"mixed_bin_audio_mag": mag, "target_class": tc.repeat(ns)}
                 masks = self.policy.get_binSepMasks(obs)
+                if want_bin:
+                    # finished before the second U-Net: the spectrum buffer is not held alongside that U-Net's activations.
+                    # The inverse GEMM's rows are those of 2R mono recordings: ((sl*R + r)*2 + c)*32 + t = ((sl*2R + (2r + c))*32 + t.
+                    self._mark("unets")
+                    masks = masks.contiguous()
+                    rows = ops.sep_bin_rows(spec, masks)
+                    del spec
+                    out_frames = ops.linear(rows, self._W_inv, None, name="separate.idft")
+                    del rows
+                    if overlap == 1:
+                        ops.sep_istft_ola(out_frames, self._win_inv, yb.view(2 * R, L), s0, ns)
+                    else:
+                        ops.sep_istft_xfade(out_frames, self._win_inv, self._win_xfade, yb.view(2 * R, L), hop, s0, ns)
+                    del out_frames
+                    self._mark("istft_bin")
+                    if return_spectrograms:
+                        keep_m.append(masks.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES, 2))
+                    if not want_mono:
+                        continue
                 P = self.policy.convert_bin2mono(masks, mixed_audio=mag)
                 self._mark("unets")
                 if use_memory:
@@ -267,10 +323,17 @@ class Separator:
                     keep_P.append(P.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES))
                     keep_ph.append(phasor.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES, 2))
             if back is not None:
-                y = back(y)[:, :L_given].contiguous()      # ceil(ceil(L a / b) b / a) >= L: never short
+                if want_mono:
+                    y = back(y)[:, :L_given].contiguous()      # ceil(ceil(L a / b) b / a) >= L: never short
+                if want_bin:
+                    yb = back(yb)[:, :, :L_given].contiguous()
                 self._mark("resample_out")
-        if not return_spectrograms:
-            return y[0] if single else y
-        Pall = torch.cat(keep_P).transpose(0, 1).contiguous()
-        ph = torch.cat(keep_ph).transpose(0, 1).contiguous()
-        return (y[0], Pall[0], ph[0]) if single else (y, Pall, ph)
+        res = ((y,) if want_mono else ()) + ((yb,) if want_bin else ())
+        if return_spectrograms:
+            if want_mono:
+                res += (torch.cat(keep_P).transpose(0, 1).contiguous(), torch.cat(keep_ph).transpose(0, 1).contiguous())
+            if want_bin:
+                res += (torch.cat(keep_m).transpose(0, 1).contiguous(),)
+        if single:
+            res = tuple(a[0] for a in res)
+        return res[0] if len(res) == 1 else res

@@ -2,6 +2,7 @@
 """Separate one sound class out of a binaural recording of any length:
 
     python separate.py --ckpt F --in mix.wav --target-class K --out out.wav [--no-memory] [--math fp32|bf16x3] [--resample] [--overlap 1|2|4]
+                       [--output mono|binaural|both] [--out-binaural bin.wav]
 
 ``--ckpt``: a passive-separator checkpoint or a PPO checkpoint (``{"state_dict", "config"}`` file or a bare state dict, with or
 without the ``actor_critic.`` root).  ``--in``: a two-channel WAV at 16 kHz, int16 or float32.  The output is a mono WAV of the
@@ -10,6 +11,10 @@ same length and sample format.  The acoustic memory is used when the checkpoint 
 back, and the output has the input's rate, length and sample format.  Without the flag any other rate is an error.
 ``--overlap k``: k one-second segments over every sample (a segment every 1/k second), cross-faded with a sin^2 window, instead of
 non-overlapping seconds; the default 1 is the plain path.
+``--output binaural``: ``--out`` gets the target in both ears, a two-channel WAV (the mixture's own spectrum of each channel scaled by
+the first U-Net's clamped mask; no memory, and ``--no-memory`` changes nothing).  ``--output both``: the mono WAV goes to ``--out`` and
+the two-channel WAV to ``--out-binaural``, which is required then and an error otherwise.  Both have the input's rate, length and
+sample format.
 Semantics, the conversion's and the cross-fade's definition: m2h/separate.py.
 """
 import argparse
@@ -58,7 +63,12 @@ def main():
     parser.add_argument("--max-segments", type=int, default=None, help="largest U-Net batch in one-second segments")
     parser.add_argument("--resample", action="store_true", help="accept an input at another sample rate: convert to 16 kHz, separate, convert back")
     parser.add_argument("--overlap", type=int, choices=[1, 2, 4], default=1, help="one-second segments over every sample, cross-faded (1: non-overlapping)")
+    parser.add_argument("--output", choices=["mono", "binaural", "both"], default="mono",
+                        help="mono: the target's mono waveform; binaural: the target in both ears (two channels); both: mono to --out, binaural to --out-binaural")
+    parser.add_argument("--out-binaural", default=None, help="with --output both: the two-channel WAV")
     args = parser.parse_args()
+    if (args.output == "both") != (args.out_binaural is not None):
+        parser.error("--output both needs --out-binaural PATH, and --out-binaural is given with --output both only")
     wave, dtype, rate = read_wav(args.inp, args.resample)
     if rate != SAMPLE_RATE:
         from m2h.audio.resample import ratio
@@ -73,12 +83,15 @@ def main():
     dev = torch.device("cuda", 0)
     sep = Separator(args.ckpt, dev, math=ops.MATH_FP32 if args.math == "fp32" else ops.MATH_BF16X3,
                     max_segments=args.max_segments or DEFAULT_MAX_SEGMENTS)
-    y = sep.separate(torch.from_numpy(wave).to(dev), args.target_class, use_memory=False if args.no_memory else None, sample_rate=rate,
-                     overlap=args.overlap)
-    wavfile.write(args.out, rate, to_wav_samples(y.cpu().numpy(), dtype))
-    print("separate.py: wrote %s (%d samples at %d Hz, %.2f s, class %d, memory %s, %s, overlap %d)" % (
-        args.out, y.numel(), rate, y.numel() / rate, args.target_class, "on" if (sep.memory is not None and not args.no_memory) else "off", args.math,
-        args.overlap))
+    res = sep.separate(torch.from_numpy(wave).to(dev), args.target_class, use_memory=False if args.no_memory else None, sample_rate=rate,
+                       overlap=args.overlap, output=args.output)
+    outs = ((args.out, res[0]), (args.out_binaural, res[1])) if args.output == "both" else ((args.out, res),)
+    for path, y in outs:
+        y = y.cpu().numpy()
+        wavfile.write(path, rate, to_wav_samples(y.T if y.ndim == 2 else y, dtype))      # two channels: [L, 2] in the file
+        memory = "on" if (y.ndim == 1 and sep.memory is not None and not args.no_memory) else "off"
+        print("separate.py: wrote %s (%d samples at %d Hz, %.2f s, class %d, memory %s, %s, overlap %d)%s" % (
+            path, y.shape[-1], rate, y.shape[-1] / rate, args.target_class, memory, args.math, args.overlap, ", two channels" if y.ndim == 2 else ""))
 
 
 if __name__ == "__main__":

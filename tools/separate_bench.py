@@ -26,6 +26,12 @@ composed path is what a user could do before it: k calls of Separator.separate o
 16000 / k samples, then the weighting with the tiled window and the division by the weights' sum in torch (stage "xfade"; the
 weights are built once, outside the timed window).  Its shifted copies are counted with the "stft" stage of their call.
 
+--output mono|binaural|both (one case; driver mode: --outputs, default mono; 16 kHz, overlap 1, --path new only): what
+Separator.separate is asked for.  "binaural" runs the first U-Net only, no memory, and the inverse transform of both channels (stage
+"istft_bin": m2h_sep_bin_rows in place on the spectrum + inverse DFT + overlap-add of 2R rows); "both" runs everything once.  The rate
+is seconds of input audio per second whatever comes out.  The driver runs mono, binaural, both, mono per case: the two mono runs
+give the margin ("binaural_no_slower_than_mono": binaural's rate >= mono's slower run less the spread of mono's two runs).
+
 Weights are synthetic.policy_shapes() with the acoustic memory's weights scaled by 0.25: as generated they are not contractive,
 and a recurrence over 600 steps would overflow expm1.  Every GPU step runs under its own timeout and the driver stops at the
 first failure.
@@ -112,7 +118,7 @@ def composed_separate(sep, stft, istft, wave, tc, mark):
     return y[:, :L].contiguous()
 
 
-def run_case(case, math_name, path, max_segments=None, sample_rate=SEG, overlap=1):
+def run_case(case, math_name, path, max_segments=None, sample_rate=SEG, overlap=1, output="mono", quiet=False):
     import numpy as np
     import torch
     from m2h import ops, synthetic
@@ -146,7 +152,9 @@ def run_case(case, math_name, path, max_segments=None, sample_rate=SEG, overlap=
     resampled = sample_rate != SEG
     if overlap != 1 and resampled:
         raise SystemExit("separate_bench: --overlap is measured at 16 kHz only")
-    stages = STAGES + (RESAMPLE_STAGES if resampled else ()) + (("xfade",) if overlap != 1 else ())
+    if output != "mono" and (resampled or overlap != 1 or path != "new"):
+        raise SystemExit("separate_bench: --output %s is measured with --path new at 16 kHz, overlap 1" % output)
+    stages = STAGES + (RESAMPLE_STAGES if resampled else ()) + (("xfade",) if overlap != 1 else ()) + (("istft_bin",) if output != "mono" else ())
     if overlap != 1:
         from m2h.separate import crossfade_window
         H = SEG // overlap
@@ -167,6 +175,8 @@ def run_case(case, math_name, path, max_segments=None, sample_rate=SEG, overlap=
     def new_path():
         sep._timing = marks
         try:
+            if output != "mono":
+                return sep.separate(wave, tc, use_memory=None if output == "binaural" else True, output=output)
             return sep.separate(wave, tc, use_memory=True, **({"sample_rate": sample_rate} if resampled else {}), **({"overlap": overlap} if overlap != 1 else {}))
         finally:
             sep._timing = None
@@ -216,7 +226,7 @@ def run_case(case, math_name, path, max_segments=None, sample_rate=SEG, overlap=
         return {"audio_s_per_s": R * seconds * reps / (total * 1e-3), "ms_per_run": total / reps,
                 "stage_share": {k: v / total for k, v in stage_ms.items()}}
 
-    res = {"case": case, "R": R, "audio_seconds_per_recording": seconds, "sample_rate": sample_rate, "overlap": overlap, "math": math_name, "reps": reps, "max_segments": sep.max_segments, "chunk_rows": max(1, sep.max_segments // R) * R}
+    res = {"case": case, "R": R, "audio_seconds_per_recording": seconds, "sample_rate": sample_rate, "overlap": overlap, "output": output, "math": math_name, "reps": reps, "max_segments": sep.max_segments, "chunk_rows": max(1, sep.max_segments // R) * R}
     order = {"new": ("new",), "composed": ("composed",), "both": ("composed", "new", "composed")}[path]
     fns = {"new": new_path, "composed": composed_path}
     outs = {}
@@ -240,6 +250,21 @@ def run_case(case, math_name, path, max_segments=None, sample_rate=SEG, overlap=
         res["bounding_stage"] = max(share, key=share.get)
     if resampled:
         res["resample"] = resample_alone(wave, to16, back, c_to16, c_back, reps)
+    if not quiet:
+        print(json.dumps(res))
+    return res
+
+
+def run_outputs(case, math_name, max_segments=None):
+    """mono, binaural, both, mono in one process: the two mono runs give the margin of the comparison."""
+    runs = [run_case(case, math_name, "new", max_segments, output=o, quiet=True) for o in ("mono", "binaural", "both", "mono")]
+    rate = [r["new"][0]["audio_s_per_s"] for r in runs]
+    spread = abs(rate[0] - rate[3]) / max(rate[0], rate[3])
+    res = {k: runs[0][k] for k in ("case", "R", "audio_seconds_per_recording", "sample_rate", "overlap", "math", "reps", "max_segments", "chunk_rows")}
+    res.update({"order": ["mono", "binaural", "both", "mono"], "mono": [runs[0]["new"][0], runs[3]["new"][0]], "binaural": [runs[1]["new"][0]],
+                "both": [runs[2]["new"][0]], "mono_spread": spread, "binaural_over_mono": rate[1] / (0.5 * (rate[0] + rate[3])),
+                "both_over_mono": rate[2] / (0.5 * (rate[0] + rate[3])),
+                "binaural_no_slower_than_mono": bool(rate[1] >= min(rate[0], rate[3]) * (1.0 - spread))})
     print(json.dumps(res))
     return res
 
@@ -282,17 +307,25 @@ def main():
     ap.add_argument("--sample-rates", type=int, nargs="+", default=[SEG, 44100, 48000], help="driver mode: the rates every case is run at")
     ap.add_argument("--overlap", type=int, choices=[1, 2, 4], default=1, help="segments over every sample (one case; 16 kHz)")
     ap.add_argument("--overlaps", type=int, nargs="+", choices=[1, 2, 4], default=[1], help="driver mode: the overlaps every 16 kHz case is run at")
+    ap.add_argument("--output", choices=["mono", "binaural", "both"], default="mono", help="what Separator.separate returns (one case; --path new, 16 kHz, overlap 1)")
+    ap.add_argument("--outputs", action="store_true", help="mono, binaural, both, mono in one process per case (bf16x3, 16 kHz, overlap 1); with --case: that case here")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=240, help="driver mode: seconds per case")
     args = ap.parse_args()
     if args.case is not None:
-        run_case(args.case, args.math, args.path, args.max_segments, args.sample_rate, args.overlap)
+        if args.outputs:
+            run_outputs(args.case, args.math, args.max_segments)
+        else:
+            run_case(args.case, args.math, args.path, args.max_segments, args.sample_rate, args.overlap, args.output)
         return
     results = []
-    for case, math, rate, overlap in [(c, m, r, k) for r in args.sample_rates for k in (args.overlaps if r == SEG else [1]) for c in ("1x60", "16x600")
-                                      for m in ("fp32", "bf16x3")]:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case, "--math", math, "--path", args.path,
-               "--sample-rate", str(rate), "--overlap", str(overlap)]
+    jobs = [(c, m, r, k) for r in args.sample_rates for k in (args.overlaps if r == SEG else [1]) for c in ("1x60", "16x600")
+                                      for m in ("fp32", "bf16x3")]
+    if args.outputs:
+        jobs = [(c, "bf16x3", SEG, 1) for c in ("1x60", "16x600")]
+    for case, math, rate, overlap in jobs:
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case, "--math", math]
+        cmd += ["--outputs"] if args.outputs else ["--path", args.path, "--sample-rate", str(rate), "--overlap", str(overlap)]
         if args.max_segments:
             cmd += ["--max-segments", str(args.max_segments)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
