@@ -657,6 +657,39 @@ int m2h_sep_istft_xfade(const float* frames, const float* window, const float* x
  * T * up < 2 * half + 1. */
 int m2h_resample_poly(const float* x, const float* G, float* y, int rows, long long L_in, long long L_out, int up, int down, int T, m2h_stream stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Window forms of the four kernels above, for a recording that arrives block by block (m2h/separate.py: SeparatorStream;
+ * m2h/audio/resample.py: ResamplerStream).  A device buffer [rows][cap] holds the absolute samples [origin, origin + cap) of every
+ * row: sample g of row q lives at buf[q * cap + g - origin].  `end` is the number of samples received so far (the recording's length
+ * at the last call); samples at or past it read as zero and are never written.  The row stride, the origin and `end` are separate
+ * arguments; with cap = end = L and origin = 0 every entry point below is its offline twin, and for any window the arithmetic and its
+ * order are the twin's: results are bit-identical.  Every call is refused before any launch when the samples below `end` that it
+ * reads or writes do not lie inside [origin, origin + cap).
+ * ------------------------------------------------------------------------------------------------------------------ */
+
+/* m2h_sep_frames_hop's rows for segments [s0, s0 + nseg) (segment s covers [s * hop, s * hop + 16000); (s0 + nseg - 1) * hop < end)
+ * read from the window buf [R * 2][cap]. */
+int m2h_sep_frames_win(const float* buf, const float* window, float* frames, int R, long long cap, long long origin, long long end, int hop, int s0,
+                       int nseg, m2h_stream stream);
+
+/* m2h_sep_istft_ola into the window y [R][cap]: segment s written to y[r][s * 16000 - origin ..), cut at end. */
+int m2h_sep_istft_ola_win(const float* frames, const float* window, float* y, int R, long long cap, long long origin, long long end, int s0, int nseg,
+                          m2h_stream stream);
+
+/* m2h_sep_istft_xfade into the window y [R][cap], the same rule: a call adds its segments in ascending order onto zero where it holds
+ * the sample's first covering segment and onto the stored value elsewhere, so the partial sums of the samples that later segments
+ * still cover must stay in the window from call to call (at their absolute positions: the caller may move the window between calls).
+ * W[n] counts the segments s <= n / hop that cover n: for n < end it does not depend on what arrives later. */
+int m2h_sep_istft_xfade_win(const float* frames, const float* window, const float* xwin, float* y, int R, long long cap, long long origin, long long end,
+                            int hop, int s0, int nseg, m2h_stream stream);
+
+/* Outputs [n_first, n_first + count) of m2h_resample_poly's definition, y [rows][count], from the input window x [rows][cap]: samples
+ * below 0 and at or past end are zero, n_first + count <= ceil(end * up / down), count > 0.  The window must hold every sample of
+ * [0, end) that these outputs read, x[j0(n_first) - T + 1 .. j0(n_first + count - 1)] with j0(n) = (n * down + half) div up.  The same
+ * tile-or-direct choice per ratio, the same k = 0 .. T-1 fmaf chain and the same one-phase path as m2h_resample_poly. */
+int m2h_resample_poly_win(const float* x, const float* G, float* y, int rows, long long cap, long long origin, long long end, long long n_first,
+                          long long count, int up, int down, int T, m2h_stream stream);
+
 /* RIR-convolution feeder glue (pretrain/datasets/dataset.py:178-186,214-216; habitat_audio/simulator_train.py:416-424).
  * m2h_feeder_round_mix: takes the "same"-mode window [start, start+L) of S full linear convolutions (rows of ldfull floats),
  * applies np.round -> int16 -> float32 / 32768, optionally stores it (conv_out [S][L], NULL to skip) and accumulates it into

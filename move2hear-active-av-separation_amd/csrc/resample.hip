@@ -24,6 +24,13 @@
 //   4. The tile leaves through LDS: a scalar head up to the first 16-byte boundary of the destination, 16-byte stores, a scalar tail.
 // resample_direct_kernel: the same sum straight from memory, one output per thread, for the ratios whose table and span do not fit
 // into 64 KB of LDS (max(up, down) above a few hundred).
+//
+// Window form (m2h_resample_poly_win; m2h.audio.resample.ResamplerStream): both kernels take the input as a window -- row r holds the
+// absolute samples [origin, origin + stride_in) at x[r * stride_in + j - origin], samples below 0 and at or past `end` are zero -- and
+// produce the outputs [n_first, n_stop) of the definition into y[r * stride_out + n - n_first].  The whole recording is the window
+// stride_in = end = L_in, origin = 0, n_first = 0, n_stop = stride_out = L_out.  The tile size depends on the ratio alone and an
+// output's sum on its own n alone (the same p, j0 and k = 0 .. T-1 fmaf chain wherever its tile starts; fmaf(g, 0, acc) is exact), so
+// a recording converted window by window equals the one-call result bit for bit.
 #include "m2h_internal.h"
 
 #include <cstdint>
@@ -43,7 +50,8 @@ static inline long long rs_span_floats(int tile, int up, int down, int T) {
 
 template <int NPT, bool UP1>
 __global__ __launch_bounds__(RS_THREADS) void resample_tile_kernel(const float* __restrict__ x, const float* __restrict__ G, float* __restrict__ y,
-                                                                   long long L_in, long long L_out, int up, int down, int T, int half,
+                                                                   long long stride_in, long long origin, long long end, long long n_first,
+                                                                   long long n_stop, long long stride_out, int up, int down, int T, int half,
                                                                    long long total_in, unsigned tiles_per_row, int table_floats) {
   extern __shared__ __align__(16) float rs_lds[];
   constexpr int TILE = RS_THREADS * NPT;
@@ -51,8 +59,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_tile_kernel(const float* 
   float* xs = rs_lds + table_floats;            // the staged span; table_floats % 4 == 0
   const int tid = threadIdx.x;
   const long long row = blockIdx.x / tiles_per_row;
-  const long long n0 = (long long)(blockIdx.x % tiles_per_row) * TILE;
-  const int cnt = (int)(L_out - n0 < TILE ? L_out - n0 : TILE);
+  const long long n0 = n_first + (long long)(blockIdx.x % tiles_per_row) * TILE;
+  const int cnt = (int)(n_stop - n0 < TILE ? n_stop - n0 : TILE);
   const long long t0 = n0 * down + half;
   const long long jb = t0 / up;                 // j0 of the tile's first output
   const int pb = (int)(t0 - jb * up);
@@ -61,7 +69,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_tile_kernel(const float* 
 
   // ---- 1. the span, on the 16-byte grid of the address space
   const long long xa4 = (long long)(reinterpret_cast<uintptr_t>(x) >> 2);
-  const long long rowA = xa4 + row * L_in;      // absolute float index of x[row][0]
+  const long long rowA = xa4 + row * stride_in - origin;   // absolute float index of the row's sample 0 (outside the window when origin > 0)
   const long long A0 = rowA + jlo;
   const int shift = (int)(A0 & 3);
   const long long F0 = A0 >> 2;
@@ -74,17 +82,17 @@ __global__ __launch_bounds__(RS_THREADS) void resample_tile_kernel(const float* 
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (have_wide) v = *reinterpret_cast<const float4*>(static_cast<uintptr_t>(Fc) << 4);
     float e[4] = {v.x, v.y, v.z, v.w};
-    const long long j = (F << 2) - rowA;        // row-relative index of the slot's first sample
+    const long long j = (F << 2) - rowA;        // sample index, in its row, of the slot's first sample
     if (F != Fc || !have_wide) {                // the first or last slot of the whole buffer: sample by sample, clamped
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        long long jj = j + u;
-        jj = jj < 0 ? 0 : (jj >= L_in ? L_in - 1 : jj);
-        e[u] = x[row * L_in + jj];
+        long long jj = j + u - origin;
+        jj = jj < 0 ? 0 : (jj >= stride_in ? stride_in - 1 : jj);
+        e[u] = x[row * stride_in + jj];
       }
     }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) e[u] = (j + u >= 0 && j + u < L_in) ? e[u] : 0.f;
+    for (int u = 0; u < 4; ++u) e[u] = (j + u >= 0 && j + u >= origin && j + u < end && j + u < origin + stride_in) ? e[u] : 0.f;
     *reinterpret_cast<float4*>(xs + 4 * q) = make_float4(e[0], e[1], e[2], e[3]);
   }
   // ---- 2. the table, transposed
@@ -131,7 +139,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_tile_kernel(const float* 
 #pragma unroll
   for (int i = 0; i < NPT; ++i) ot[tid + RS_THREADS * i] = acc[i];
   __syncthreads();
-  float* yr = y + row * L_out + n0;
+  float* yr = y + row * stride_out + (n0 - n_first);
   int lead = (int)((4 - ((reinterpret_cast<uintptr_t>(yr) >> 2) & 3)) & 3);
   lead = lead < cnt ? lead : cnt;
   const int nfull = (cnt - lead) >> 2;
@@ -145,34 +153,72 @@ __global__ __launch_bounds__(RS_THREADS) void resample_tile_kernel(const float* 
 }
 
 __global__ __launch_bounds__(RS_THREADS) void resample_direct_kernel(const float* __restrict__ x, const float* __restrict__ G, float* __restrict__ y,
-                                                                     long long L_in, long long L_out, int up, int down, int T, int half,
+                                                                     long long stride_in, long long origin, long long end, long long n_first,
+                                                                     long long n_stop, long long stride_out, int up, int down, int T, int half,
                                                                      unsigned tiles_per_row) {
   const long long row = blockIdx.x / tiles_per_row;
-  const long long n = (long long)(blockIdx.x % tiles_per_row) * RS_THREADS + threadIdx.x;
-  if (n >= L_out) return;
+  const long long n = n_first + (long long)(blockIdx.x % tiles_per_row) * RS_THREADS + threadIdx.x;
+  if (n >= n_stop) return;
   const long long t = n * down + half;
   const long long j0 = t / up;
   const float* g = G + (size_t)(t - j0 * up) * T;
-  const float* xr = x + row * L_in;
+  const float* xr = x + row * stride_in;
   float acc = 0.f;
   for (int k = 0; k < T; ++k) {
     const long long j = j0 - k;
-    const long long jc = j < 0 ? 0 : (j >= L_in ? L_in - 1 : j);
+    const long long jr = j - origin;
+    const long long jc = jr < 0 ? 0 : (jr >= stride_in ? stride_in - 1 : jr);
     const float v = xr[jc];
-    acc = fmaf(g[k], (j >= 0 && j < L_in) ? v : 0.f, acc);
+    acc = fmaf(g[k], (j >= 0 && jr >= 0 && j < end && jr < stride_in) ? v : 0.f, acc);
   }
-  y[row * L_out + n] = acc;
+  y[row * stride_out + (n - n_first)] = acc;
 }
 
 template <int NPT>
-static void rs_launch_tile(bool up1, unsigned grid, size_t lds, hipStream_t s, const float* x, const float* G, float* y, long long L_in, long long L_out,
-                           int up, int down, int T, int half, long long total_in, unsigned tiles_per_row, int table_floats) {
+static void rs_launch_tile(bool up1, unsigned grid, size_t lds, hipStream_t s, const float* x, const float* G, float* y, long long stride_in,
+                           long long origin, long long end, long long n_first, long long n_stop, long long stride_out, int up, int down, int T, int half,
+                           long long total_in, unsigned tiles_per_row, int table_floats) {
   if (up1)
-    M2H_LAUNCH((resample_tile_kernel<NPT, true>), dim3(grid), dim3(RS_THREADS), lds, s, x, G, y, L_in, L_out, up, down, T, half, total_in, tiles_per_row,
-               table_floats);
+    M2H_LAUNCH((resample_tile_kernel<NPT, true>), dim3(grid), dim3(RS_THREADS), lds, s, x, G, y, stride_in, origin, end, n_first, n_stop, stride_out, up,
+               down, T, half, total_in, tiles_per_row, table_floats);
   else
-    M2H_LAUNCH((resample_tile_kernel<NPT, false>), dim3(grid), dim3(RS_THREADS), lds, s, x, G, y, L_in, L_out, up, down, T, half, total_in, tiles_per_row,
-               table_floats);
+    M2H_LAUNCH((resample_tile_kernel<NPT, false>), dim3(grid), dim3(RS_THREADS), lds, s, x, G, y, stride_in, origin, end, n_first, n_stop, stride_out, up,
+               down, T, half, total_in, tiles_per_row, table_floats);
+}
+
+// The tile-or-direct choice of a ratio and the launch of outputs [n_first, n_stop) from the window (x, stride_in, origin, end); every
+// argument has been checked.  Returns false when the grid would not fit.
+static bool rs_run(const float* x, const float* G, float* y, int rows, long long stride_in, long long origin, long long end, long long n_first,
+                   long long n_stop, long long stride_out, int up, int down, int T, int half, hipStream_t s, bool* direct) {
+  const long long table = rs_table_floats(up, T);
+  const int table_floats = (int)((table + 3) / 4 * 4);
+  int npt = 0;
+  size_t lds = 0;
+  for (int c = 8; c >= 1 && !npt; c >>= 1) {
+    const int tile = RS_THREADS * c;
+    long long f = table_floats + rs_span_floats(tile, up, down, T);
+    if (f < tile) f = tile;
+    if (f * 4 <= RS_LDS_BYTES) {
+      npt = c;
+      lds = (size_t)f * 4;
+    }
+  }
+  const long long tile = RS_THREADS * (npt ? npt : 1);
+  const long long tiles_per_row = (n_stop - n_first + tile - 1) / tile;
+  if (tiles_per_row * rows >= (1LL << 31)) return false;
+  const unsigned grid = (unsigned)(tiles_per_row * rows);
+  const long long total_in = (long long)rows * stride_in;
+  const unsigned tpr = (unsigned)tiles_per_row;
+  switch (npt) {
+    case 8: rs_launch_tile<8>(up == 1, grid, lds, s, x, G, y, stride_in, origin, end, n_first, n_stop, stride_out, up, down, T, half, total_in, tpr, table_floats); break;
+    case 4: rs_launch_tile<4>(up == 1, grid, lds, s, x, G, y, stride_in, origin, end, n_first, n_stop, stride_out, up, down, T, half, total_in, tpr, table_floats); break;
+    case 2: rs_launch_tile<2>(up == 1, grid, lds, s, x, G, y, stride_in, origin, end, n_first, n_stop, stride_out, up, down, T, half, total_in, tpr, table_floats); break;
+    case 1: rs_launch_tile<1>(up == 1, grid, lds, s, x, G, y, stride_in, origin, end, n_first, n_stop, stride_out, up, down, T, half, total_in, tpr, table_floats); break;
+    default:
+      M2H_LAUNCH(resample_direct_kernel, dim3(grid), dim3(RS_THREADS), 0, s, x, G, y, stride_in, origin, end, n_first, n_stop, stride_out, up, down, T, half, tpr);
+  }
+  *direct = npt == 0;
+  return true;
 }
 
 }  // namespace m2h
@@ -192,34 +238,37 @@ int m2h_resample_poly(const float* x, const float* G, float* y, int rows, long l
   M2H_REQUIRE((long long)T * up >= 2 * half + 1 && T <= 2 * half + 1, "resample_poly: a table of T %d x up %d does not hold the %d taps of this ratio", T, up, 2 * half + 1);
   M2H_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 3) == 0,
               "resample_poly: buffers must be 4-byte aligned");
-  const long long table = rs_table_floats(up, T);
-  const int table_floats = (int)((table + 3) / 4 * 4);
-  int npt = 0;
-  size_t lds = 0;
-  for (int c = 8; c >= 1 && !npt; c >>= 1) {
-    const int tile = RS_THREADS * c;
-    long long f = table_floats + rs_span_floats(tile, up, down, T);
-    if (f < tile) f = tile;
-    if (f * 4 <= RS_LDS_BYTES) {
-      npt = c;
-      lds = (size_t)f * 4;
-    }
-  }
-  const long long tile = RS_THREADS * (npt ? npt : 1);
-  const long long tiles_per_row = (L_out + tile - 1) / tile;
-  M2H_REQUIRE(tiles_per_row * rows < (1LL << 31), "resample_poly: bad sizes (%lld tiles)", tiles_per_row * rows);
-  const unsigned grid = (unsigned)(tiles_per_row * rows);
-  const long long total_in = (long long)rows * L_in;
-  hipStream_t s = as_stream(stream);
-  switch (npt) {
-    case 8: rs_launch_tile<8>(up == 1, grid, lds, s, x, G, y, L_in, L_out, up, down, T, half, total_in, (unsigned)tiles_per_row, table_floats); break;
-    case 4: rs_launch_tile<4>(up == 1, grid, lds, s, x, G, y, L_in, L_out, up, down, T, half, total_in, (unsigned)tiles_per_row, table_floats); break;
-    case 2: rs_launch_tile<2>(up == 1, grid, lds, s, x, G, y, L_in, L_out, up, down, T, half, total_in, (unsigned)tiles_per_row, table_floats); break;
-    case 1: rs_launch_tile<1>(up == 1, grid, lds, s, x, G, y, L_in, L_out, up, down, T, half, total_in, (unsigned)tiles_per_row, table_floats); break;
-    default:
-      M2H_LAUNCH(resample_direct_kernel, dim3(grid), dim3(RS_THREADS), 0, s, x, G, y, L_in, L_out, up, down, T, half, (unsigned)tiles_per_row);
-  }
-  return launch_status(npt ? "resample_poly" : "resample_poly_direct");
+  bool direct = false;
+  M2H_REQUIRE(rs_run(x, G, y, rows, L_in, 0, L_in, 0, L_out, L_out, up, down, T, half, as_stream(stream), &direct), "resample_poly: bad sizes (too many tiles)");
+  return launch_status(direct ? "resample_poly_direct" : "resample_poly");
+}
+
+int m2h_resample_poly_win(const float* x, const float* G, float* y, int rows, long long cap, long long origin, long long end, long long n_first,
+                          long long count, int up, int down, int T, m2h_stream stream) {
+  M2H_REQUIRE(x && G && y, "resample_poly_win: null pointer");
+  M2H_REQUIRE(rows > 0 && cap > 0 && origin >= 0 && end > 0 && n_first >= 0 && up > 0 && down > 0 && T > 0,
+              "resample_poly_win: bad sizes (rows %d, cap %lld, origin %lld, end %lld, n_first %lld, up %d, down %d, T %d)", rows, cap, origin, end, n_first, up, down, T);
+  M2H_REQUIRE(count > 0, "resample_poly_win: count must be positive, got %lld", count);
+  M2H_REQUIRE(up <= RS_MAX_RATIO && down <= RS_MAX_RATIO, "resample_poly_win: ratio %d/%d is over the limit (max(up, down) <= %d)", up, down, RS_MAX_RATIO);
+  M2H_REQUIRE(end <= (1LL << 40) && cap <= (1LL << 40) && count <= (1LL << 40) && (long long)rows * (cap > count ? cap : count) <= (1LL << 44),
+              "resample_poly_win: bad sizes (rows %d x cap %lld / count %lld is too long)", rows, cap, count);
+  M2H_REQUIRE(n_first + count <= (end * up + down - 1) / down, "resample_poly_win: outputs [%lld, %lld + %lld) pass ceil(end * up / down) = %lld", n_first, n_first,
+              count, (end * up + down - 1) / down);
+  const int half = 10 * (up > down ? up : down);
+  M2H_REQUIRE((long long)T * up >= 2 * half + 1 && T <= 2 * half + 1, "resample_poly_win: a table of T %d x up %d does not hold the %d taps of this ratio", T, up, 2 * half + 1);
+  M2H_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 3) == 0,
+              "resample_poly_win: buffers must be 4-byte aligned");
+  // the samples inside [0, end) that the outputs read: x[j0(n_first) - T + 1 .. j0(n_first + count - 1)]
+  long long jlo = (n_first * down + half) / up - (T - 1);
+  long long jhi = ((n_first + count - 1) * down + half) / up + 1;
+  if (jlo < 0) jlo = 0;
+  if (jhi > end) jhi = end;
+  M2H_REQUIRE(jlo >= jhi || (jlo >= origin && jhi <= origin + cap), "resample_poly_win: outputs [%lld, %lld + %lld) read samples [%lld, %lld), outside the window [%lld, %lld + %lld)",
+              n_first, n_first, count, jlo, jhi, origin, origin, cap);
+  bool direct = false;
+  M2H_REQUIRE(rs_run(x, G, y, rows, cap, origin, end, n_first, n_first + count, count, up, down, T, half, as_stream(stream), &direct),
+              "resample_poly_win: bad sizes (too many tiles)");
+  return launch_status(direct ? "resample_poly_win_direct" : "resample_poly_win");
 }
 
 }  // extern "C"

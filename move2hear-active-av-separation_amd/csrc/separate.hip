@@ -26,8 +26,12 @@ constexpr int SEP_KT = 32;        // bins per workgroup of the two transposing k
 // seg[j] = wave[r][c][(s0 + sl)*16000 + j] below L, 0 from L on.  One thread = four consecutive n = one 16-byte store; the source
 // offsets are odd by construction (n - 511), so the reads are scalar and coalesced across the wave.
 // Segment s starts at sample s * hop: 16000 for the plain path, 16000 / k for overlapped segments (sep_frames_hop_kernel).
+// Window form (sep_frames_win_kernel, a live feed: m2h/separate.py, SeparatorStream): the buffer holds the absolute samples
+// [origin, origin + stride) of every row, sample g at wave[(r*2 + c)*stride + g - origin], and samples at or past `end` are zero.
+// The whole recording is the window stride = end = L, origin = 0.
 __device__ __forceinline__ void sep_frames_body(const float* __restrict__ wave, const float* __restrict__ window /* [1024], [1023] = 0 */,
-                                                float* __restrict__ frames, int R, long long L, int hop, int s0, int nseg) {
+                                                float* __restrict__ frames, int R, long long stride, long long origin, long long end, int hop,
+                                                int s0, int nseg) {
   const size_t total = (size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int n0 = (int)(i % (SEP_LD / 4)) * 4;
@@ -39,7 +43,7 @@ __device__ __forceinline__ void sep_frames_body(const float* __restrict__ wave, 
     const int r = (int)(nrow % R);
     const int sl = (int)(nrow / R);
     const long long base = (long long)(s0 + sl) * hop;
-    const float* src = wave + ((size_t)r * 2 + c) * (size_t)L;
+    const float* src = wave + ((size_t)r * 2 + c) * (size_t)stride;
     const float4 w = *reinterpret_cast<const float4*>(window + n0);
     const float wv[4] = {w.x, w.y, w.z, w.w};
     float v[4];
@@ -52,7 +56,7 @@ __device__ __forceinline__ void sep_frames_body(const float* __restrict__ wave, 
         if (j < 0) j = -j;                                  // np.pad(mode="reflect"): edge sample not repeated
         if (j >= SEP_SEG) j = 2 * (SEP_SEG - 1) - j;
         const long long g = base + j;
-        if (g < L) x = wv[e] * src[g];
+        if (g < end) x = wv[e] * src[g - origin];
       }
       v[e] = x;
     }
@@ -62,12 +66,17 @@ __device__ __forceinline__ void sep_frames_body(const float* __restrict__ wave, 
 
 __global__ __launch_bounds__(256) void sep_frames_kernel(const float* __restrict__ wave, const float* __restrict__ window, float* __restrict__ frames, int R,
                                                          long long L, int s0, int nseg) {
-  sep_frames_body(wave, window, frames, R, L, SEP_SEG, s0, nseg);
+  sep_frames_body(wave, window, frames, R, L, 0, L, SEP_SEG, s0, nseg);
 }
 
 __global__ __launch_bounds__(256) void sep_frames_hop_kernel(const float* __restrict__ wave, const float* __restrict__ window, float* __restrict__ frames, int R,
                                                              long long L, int hop, int s0, int nseg) {
-  sep_frames_body(wave, window, frames, R, L, hop, s0, nseg);
+  sep_frames_body(wave, window, frames, R, L, 0, L, hop, s0, nseg);
+}
+
+__global__ __launch_bounds__(256) void sep_frames_win_kernel(const float* __restrict__ buf, const float* __restrict__ window, float* __restrict__ frames, int R,
+                                                             long long cap, long long origin, long long end, int hop, int s0, int nseg) {
+  sep_frames_body(buf, window, frames, R, cap, origin, end, hop, s0, nseg);
 }
 
 // spec rows [(n*2 + c)*32 + t][1024] = [Re(512) | Im(512)]  ->  mag [n][512][32][2] = log1p|X_c|, phasor [n][512][32][2] = D / |D|
@@ -225,8 +234,10 @@ __device__ __forceinline__ float sep_ola_sample(const float* __restrict__ fr, co
 // Windowed overlap-add as a gather (istft_ola_kernel's arithmetic), every segment written at its offset of y [R][L] and cut at L:
 // y[r][(s0 + sl)*16000 + j] = (sum_t frames[(sl*R + r)*32 + t][jj - 512 t] * window[jj - 512 t]) / wss(jj), jj = j + 511.
 // One thread = four consecutive j: one 16-byte store where the destination is aligned (always when L % 4 == 0) and inside L.
-__global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
-                                                            float* __restrict__ y, int R, long long L, int s0, int nseg) {
+// Window form (sep_istft_ola_win_kernel): y holds the absolute samples [origin, origin + stride) of every row, sample n at
+// y[r*stride + n - origin], cut at L = the samples received; the whole recording is stride = L, origin = 0.
+__device__ __forceinline__ void sep_istft_ola_body(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */, float* __restrict__ y,
+                                                   int R, long long stride, long long origin, long long L, int s0, int nseg) {
   const size_t total = (size_t)nseg * R * (SEP_SEG / 4);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int j0 = (int)(i % (SEP_SEG / 4)) * 4;
@@ -239,7 +250,7 @@ __global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restr
     float v[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = sep_ola_sample(fr, window, j0 + e);
-    float* dst = y + (size_t)r * (size_t)L + g0;
+    float* dst = y + (size_t)r * (size_t)stride + (g0 - origin);
     if (g0 + 4 <= L && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
       *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
@@ -250,15 +261,29 @@ __global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restr
   }
 }
 
+__global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                            float* __restrict__ y, int R, long long L, int s0, int nseg) {
+  sep_istft_ola_body(frames, window, y, R, L, 0, L, s0, nseg);
+}
+
+__global__ __launch_bounds__(256) void sep_istft_ola_win_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                                float* __restrict__ y, int R, long long cap, long long origin, long long end, int s0,
+                                                                int nseg) {
+  sep_istft_ola_body(frames, window, y, R, cap, origin, end, s0, nseg);
+}
+
 // Overlapped segments (segment s covers samples [s*hop, s*hop + 16000), hop = 16000 / k) cross-faded into y [R][L]:
 // y[r][n] = sum_s xwin[n - s*hop] * v_s[n - s*hop] / W[n], W[n] = sum_s xwin[n - s*hop] over all segments 0 <= s < S of the recording
 // that cover n, v_s = the segment's inverse transform (sep_ola_sample).  A gather: one thread = four consecutive n of the span
 // [s0*hop, min(L, (s0 + nseg - 1)*hop + 16000)) the chunk's segments cover; hop % 4 == 0, so the four share their covering segments.
 // The chunk's covering segments are added in ascending order onto 0 when the chunk holds the sample's first covering segment and
 // onto y[n] otherwise: chunks come in ascending order, y needs no clearing, and the order of the additions is the same for any chunking.
-__global__ __launch_bounds__(256) void sep_istft_xfade_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
-                                                              const float* __restrict__ xwin /* [16000] */, float* y, int R, long long L, int hop,
-                                                              int s0, int nseg, long long S) {
+// Window form (sep_istft_xfade_win_kernel): y holds the absolute samples [origin, origin + stride) of every row, sample n at
+// y[r*stride + n - origin]; the partial sums of the samples that later segments still cover stay there between calls.  L = the samples
+// received so far: a sample below it is covered by no segment past ceil(L / hop) - 1 whatever arrives later, so W[n] is final.
+__device__ __forceinline__ void sep_istft_xfade_body(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                     const float* __restrict__ xwin /* [16000] */, float* y, int R, long long stride, long long origin,
+                                                     long long L, int hop, int s0, int nseg, long long S) {
   const long long n_first = (long long)s0 * hop;
   long long n_end = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
   if (n_end > L) n_end = L;
@@ -279,7 +304,7 @@ __global__ __launch_bounds__(256) void sep_istft_xfade_kernel(const float* __res
       W[2] += w.z;
       W[3] += w.w;
     }
-    float* dst = y + (size_t)r * (size_t)L + n0;
+    float* dst = y + (size_t)r * (size_t)stride + (n0 - origin);
     const bool wide = n0 + 4 <= L && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     if (a < s0) {                                           // earlier chunks have added their segments already
@@ -312,6 +337,18 @@ __global__ __launch_bounds__(256) void sep_istft_xfade_kernel(const float* __res
   }
 }
 
+__global__ __launch_bounds__(256) void sep_istft_xfade_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                              const float* __restrict__ xwin /* [16000] */, float* y, int R, long long L, int hop,
+                                                              int s0, int nseg, long long S) {
+  sep_istft_xfade_body(frames, window, xwin, y, R, L, 0, L, hop, s0, nseg, S);
+}
+
+__global__ __launch_bounds__(256) void sep_istft_xfade_win_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                                  const float* __restrict__ xwin /* [16000] */, float* y, int R, long long cap,
+                                                                  long long origin, long long end, int hop, int s0, int nseg, long long S) {
+  sep_istft_xfade_body(frames, window, xwin, y, R, cap, origin, end, hop, s0, nseg, S);
+}
+
 static inline unsigned sep_grid(size_t total) {
   size_t g = (total + 255) / 256;
   if (g > 16384) g = 16384;
@@ -335,6 +372,22 @@ static inline bool sep_chunk_hop_ok(int R, long long L, int hop, int s0, int nse
   const long long S = (L + hop - 1) / hop;
   if ((long long)s0 + nseg > S) return false;
   return (long long)nseg * R <= (1 << 20);
+}
+
+// window forms: rows [R][cap] hold the absolute samples [origin, origin + cap); `end` samples have been received
+static inline bool sep_win_ok(int R, long long cap, long long origin, long long end, int hop, int s0, int nseg) {
+  if (R <= 0 || cap <= 0 || origin < 0 || end <= 0 || s0 < 0 || nseg <= 0) return false;
+  if (end > (1LL << 40) || cap > (1LL << 40) || (long long)R * cap > (1LL << 44)) return false;
+  if ((long long)s0 + nseg > (end + hop - 1) / hop) return false;
+  return (long long)nseg * R <= (1 << 20);
+}
+
+// the samples below `end` that segments [s0, s0 + nseg) cover lie inside the window
+static inline bool sep_win_holds(long long cap, long long origin, long long end, int hop, int s0, int nseg) {
+  const long long first = (long long)s0 * hop;
+  long long stop = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
+  if (stop > end) stop = end;
+  return first >= origin && stop <= origin + cap;
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -407,6 +460,52 @@ int m2h_sep_istft_xfade(const float* frames, const float* window, const float* x
   const size_t quads = (size_t)((n_end - (long long)s0 * hop + 3) / 4);
   M2H_LAUNCH(sep_istft_xfade_kernel, dim3(sep_grid(quads * R)), dim3(256), 0, as_stream(stream), frames, window, xwin, y, R, L, hop, s0, nseg, S);
   return launch_status("sep_istft_xfade");
+}
+
+// ---- window forms: a live feed, block by block (m2h/separate.py, SeparatorStream)
+
+int m2h_sep_frames_win(const float* buf, const float* window, float* frames, int R, long long cap, long long origin, long long end, int hop, int s0,
+                       int nseg, m2h_stream stream) {
+  M2H_REQUIRE(buf && window && frames, "sep_frames_win: null pointer");
+  M2H_REQUIRE(sep_hop_ok(hop), "sep_frames_win: hop must be 16000, 8000 or 4000, got %d", hop);
+  M2H_REQUIRE(sep_win_ok(R, cap, origin, end, hop, s0, nseg), "sep_frames_win: bad sizes (R %d, cap %lld, origin %lld, end %lld, hop %d, segments [%d, %d + %d))",
+              R, cap, origin, end, hop, s0, s0, nseg);
+  M2H_REQUIRE(sep_win_holds(cap, origin, end, hop, s0, nseg), "sep_frames_win: segments [%d, %d + %d) at hop %d leave the window [%lld, %lld + %lld) (end %lld)",
+              s0, s0, nseg, hop, origin, origin, cap, end);
+  M2H_REQUIRE(aligned16(window) && aligned16(frames), "sep_frames_win: window / frames must be 16-byte aligned");
+  M2H_LAUNCH(sep_frames_win_kernel, dim3(sep_grid((size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4))), dim3(256), 0, as_stream(stream), buf, window, frames, R,
+             cap, origin, end, hop, s0, nseg);
+  return launch_status("sep_frames_win");
+}
+
+int m2h_sep_istft_ola_win(const float* frames, const float* window, float* y, int R, long long cap, long long origin, long long end, int s0, int nseg,
+                          m2h_stream stream) {
+  M2H_REQUIRE(frames && window && y, "sep_istft_ola_win: null pointer");
+  M2H_REQUIRE(sep_win_ok(R, cap, origin, end, SEP_SEG, s0, nseg), "sep_istft_ola_win: bad sizes (R %d, cap %lld, origin %lld, end %lld, segments [%d, %d + %d))", R,
+              cap, origin, end, s0, s0, nseg);
+  M2H_REQUIRE(sep_win_holds(cap, origin, end, SEP_SEG, s0, nseg), "sep_istft_ola_win: segments [%d, %d + %d) leave the window [%lld, %lld + %lld) (end %lld)", s0, s0,
+              nseg, origin, origin, cap, end);
+  M2H_LAUNCH(sep_istft_ola_win_kernel, dim3(sep_grid((size_t)nseg * R * (SEP_SEG / 4))), dim3(256), 0, as_stream(stream), frames, window, y, R, cap, origin,
+             end, s0, nseg);
+  return launch_status("sep_istft_ola_win");
+}
+
+int m2h_sep_istft_xfade_win(const float* frames, const float* window, const float* xwin, float* y, int R, long long cap, long long origin, long long end,
+                            int hop, int s0, int nseg, m2h_stream stream) {
+  M2H_REQUIRE(frames && window && xwin && y, "sep_istft_xfade_win: null pointer");
+  M2H_REQUIRE(sep_hop_ok(hop), "sep_istft_xfade_win: hop must be 16000, 8000 or 4000, got %d", hop);
+  M2H_REQUIRE(sep_win_ok(R, cap, origin, end, hop, s0, nseg), "sep_istft_xfade_win: bad sizes (R %d, cap %lld, origin %lld, end %lld, hop %d, segments [%d, %d + %d))",
+              R, cap, origin, end, hop, s0, s0, nseg);
+  M2H_REQUIRE(sep_win_holds(cap, origin, end, hop, s0, nseg), "sep_istft_xfade_win: segments [%d, %d + %d) at hop %d leave the window [%lld, %lld + %lld) (end %lld)",
+              s0, s0, nseg, hop, origin, origin, cap, end);
+  M2H_REQUIRE(aligned16(xwin), "sep_istft_xfade_win: the cross-fade window must be 16-byte aligned");
+  const long long S = (end + hop - 1) / hop;
+  long long n_end = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
+  if (n_end > end) n_end = end;
+  const size_t quads = (size_t)((n_end - (long long)s0 * hop + 3) / 4);
+  M2H_LAUNCH(sep_istft_xfade_win_kernel, dim3(sep_grid(quads * R)), dim3(256), 0, as_stream(stream), frames, window, xwin, y, R, cap, origin, end, hop, s0,
+             nseg, S);
+  return launch_status("sep_istft_xfade_win");
 }
 
 }  // extern "C"

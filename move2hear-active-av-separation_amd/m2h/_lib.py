@@ -278,6 +278,10 @@ SIGNATURES = {
     "m2h_sep_frames_hop": [_P, _P, _P, _I, _L, _I, _I, _I, _P],
     "m2h_sep_istft_xfade": [_P, _P, _P, _P, _I, _L, _I, _I, _I, _P],
     "m2h_resample_poly": [_P, _P, _P, _I, _L, _L, _I, _I, _I, _P],
+    "m2h_sep_frames_win": [_P, _P, _P, _I, _L, _L, _L, _I, _I, _I, _P],
+    "m2h_sep_istft_ola_win": [_P, _P, _P, _I, _L, _L, _L, _I, _I, _P],
+    "m2h_sep_istft_xfade_win": [_P, _P, _P, _P, _I, _L, _L, _L, _I, _I, _I, _P],
+    "m2h_resample_poly_win": [_P, _P, _P, _I, _L, _L, _L, _L, _L, _I, _I, _I, _P],
     "m2h_split32": [_P, _P, ctypes.c_size_t, _P],
     "m2h_feeder_round_mix": [_P, _I, _I, _P, _P, _I, _I, _I, _F, _P],
     "m2h_rms_normalize": [_P, _I, _I, _F, _P],

@@ -81,6 +81,10 @@ class Resampler:
     def output_length(self, L):
         return output_length(L, self.up, self.down)
 
+    def stream(self, lead=()):
+        """A ResamplerStream over rows of the shape `lead` (a block is [*lead, n])."""
+        return ResamplerStream(self, lead)
+
     def __call__(self, x):
         import torch
         from .. import ops
@@ -95,3 +99,118 @@ class Resampler:
         lead = x.shape[:-1]
         y = ops.resample_poly(x.contiguous().reshape(-1, x.shape[-1]), self.table, self.up, self.down)
         return y.reshape(*lead, y.shape[-1])
+
+
+# ---- block by block ----
+def ready_outputs(P, up, down):
+    """How many outputs P received input samples determine: output n is emitted once input sample (n * down + half) div up has
+    arrived, so this is the number of n >= 0 with (n * down + half) div up < P.  Never more than ceil(P * up / down).  Pure Python; P may
+    be an int or an integer numpy array."""
+    half = 10 * max(up, down)
+    n = (P * up - half - 1) // down + 1
+    return np.maximum(n, 0) if isinstance(n, np.ndarray) else max(0, n)
+
+
+class SampleWindow:
+    """The last samples of rows that arrive block by block: buf [*lead, cap] holds the absolute samples [origin, origin + fill) at
+    buf[..., : fill].  Two buffers take turns: moving the window copies the kept tail and the new block from one into the other, never
+    between overlapping views of one buffer, and costs O(kept + block).  The pair grows (doubling) only when a window needs more than
+    cap samples: with blocks of a bounded size the window is allocated once."""
+
+    def __init__(self, lead, device):
+        self.lead, self.device = tuple(lead), device
+        self.bufs, self.cur, self.cap = [None, None], 0, 0
+        self.origin = self.fill = 0
+
+    @property
+    def buf(self):
+        return self.bufs[self.cur]
+
+    def clear(self):
+        self.origin = self.fill = 0
+
+    def advance(self, origin, block=None, extra=0):
+        """Move to [origin, old end + n): drops the samples below origin, appends block [*lead, n] or, with extra = n, n samples that the
+        caller writes.  origin lies inside [old origin, old end]."""
+        import torch
+        off = origin - self.origin
+        keep = self.fill - off
+        assert 0 <= off and keep >= 0, (origin, self.origin, self.fill)
+        n = block.shape[-1] if block is not None else int(extra)
+        need = keep + n
+        if off == 0 and need <= self.cap:                      # nothing to drop: append in place
+            dst = self.buf
+        else:
+            if need > self.cap:
+                self.cap = (max(need, 2 * self.cap) + 3) // 4 * 4
+                new = [torch.empty(self.lead + (self.cap,), device=self.device, dtype=torch.float32) for _ in range(2)]
+                dst, nxt = new[0], 0
+            else:
+                new, nxt = self.bufs, 1 - self.cur
+                dst = new[nxt]
+            if keep:
+                dst[..., :keep].copy_(self.buf[..., off:off + keep])
+            self.bufs, self.cur = new, nxt
+        if block is not None and n:
+            dst[..., keep:need].copy_(block)
+        self.origin, self.fill = origin, need
+
+
+class ResamplerStream:
+    """Resampler(...).stream(lead) -> push(block [*lead, n]) returns every output the samples so far determine (ready_outputs), flush()
+    the rest up to ceil(L * up / down); the pieces, concatenated, are Resampler(x) of the concatenated blocks bit for bit, for any
+    blocking (m2h_resample_poly_win).  The window keeps the T - 1 samples of history the next output needs."""
+
+    def __init__(self, resampler, lead):
+        self.rs, self.lead = resampler, tuple(int(d) for d in lead)
+        self.rows = int(np.prod(self.lead)) if self.lead else 1
+        self.win = SampleWindow(self.lead, resampler.device)
+        self.reset()
+
+    def reset(self):
+        self.received = self.emitted = 0
+        self.closed = False
+        self.win.clear()
+
+    def _j0(self, n):
+        return (n * self.rs.down + self.rs.half) // self.rs.up
+
+    def _run(self, count):
+        import torch
+        from .. import ops
+        if count <= 0:
+            return torch.empty(self.lead + (0,), device=self.rs.device, dtype=torch.float32)
+        w = self.win
+        y = ops.resample_poly_win(w.buf.view(self.rows, w.cap), self.rs.table, self.rs.up, self.rs.down, w.origin, self.received, self.emitted, count)
+        self.emitted += count
+        return y.view(self.lead + (count,))
+
+    def push(self, block):
+        import torch
+        if self.closed:
+            raise RuntimeError("m2h.ResamplerStream: push after flush")
+        if not torch.is_tensor(block) or tuple(block.shape[:-1]) != self.lead or block.dim() != len(self.lead) + 1:
+            raise RuntimeError("m2h.ResamplerStream: expected a block [%s, n], got %s" % (", ".join(map(str, self.lead)), tuple(block.shape) if torch.is_tensor(block) else type(block).__name__))
+        if block.dtype != torch.float32:
+            raise RuntimeError("m2h.ResamplerStream: block must be float32, got %s" % block.dtype)
+        if self.rs.identity:
+            self.received += block.shape[-1]
+            self.emitted = self.received
+            return block
+        if block.device != self.rs.device:
+            raise RuntimeError("m2h.ResamplerStream: block lives on %s, the resampler on %s" % (block.device, self.rs.device))
+        w = self.win
+        # the lowest sample the next output reads; it never moves back, and lies at or below what has arrived
+        lo = min(max(self._j0(self.emitted) - (self.rs.T - 1), w.origin), self.received)
+        w.advance(lo, block)
+        self.received += block.shape[-1]
+        return self._run(ready_outputs(self.received, self.rs.up, self.rs.down) - self.emitted)
+
+    def flush(self):
+        import torch
+        if self.closed:
+            raise RuntimeError("m2h.ResamplerStream: flush after flush")
+        self.closed = True
+        if self.rs.identity or self.received == 0:
+            return torch.empty(self.lead + (0,), device=self.rs.device, dtype=torch.float32)
+        return self._run(output_length(self.received, self.rs.up, self.rs.down) - self.emitted)

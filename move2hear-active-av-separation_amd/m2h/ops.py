@@ -1242,3 +1242,90 @@ def resample_poly(x, G, up, down, out=None):
     with torch.cuda.device(x.device):
         _lib.check(_lib.load().m2h_resample_poly(_ptr(x), _ptr(G), _ptr(out), rows, L_in, L_out, up, down, G.shape[1], _stream(x)), "m2h_resample_poly")
     return out
+
+
+# ---- window forms for a recording that arrives block by block (include/m2h.h, "Window forms"; m2h/separate.py: SeparatorStream) ----
+def sep_frames_win(buf, window, origin, end, hop, s0, nseg, out=None):
+    """sep_frames_hop's rows for segments [s0, s0+nseg) from a window: buf [R, 2, cap] holds the absolute samples [origin, origin + cap)
+    of a recording of which `end` samples have arrived; samples at or past end are zero (m2h_sep_frames_win).  The library refuses a
+    call whose reads would leave the window."""
+    _chk(buf, "sep_frames_win(buf)")
+    _chk(window, "sep_frames_win(window)")
+    if buf.dim() != 3 or buf.shape[1] != 2 or buf.shape[0] < 1 or buf.shape[2] < 1:
+        raise RuntimeError("m2h.sep_frames_win: expected a [R, 2, cap] window, got %s" % (tuple(buf.shape),))
+    if window.numel() != SEP_LD:
+        raise RuntimeError("m2h.sep_frames_win: window must hold %d floats, got %d" % (SEP_LD, window.numel()))
+    R, _, cap = buf.shape
+    rows = max(int(nseg), 0) * R * 2 * SEP_FRAMES
+    if out is None:
+        out = torch.empty((rows, SEP_LD), device=buf.device, dtype=torch.float32)
+    else:
+        _chk(out, "sep_frames_win(out)")
+        if tuple(out.shape) != (rows, SEP_LD):
+            raise RuntimeError("m2h.sep_frames_win: out must be [%d, %d], got %s" % (rows, SEP_LD, tuple(out.shape)))
+    with torch.cuda.device(buf.device):
+        _lib.check(_lib.load().m2h_sep_frames_win(_ptr(buf), _ptr(window), _ptr(out), R, cap, int(origin), int(end), int(hop), int(s0), int(nseg), _stream(buf)),
+                   "m2h_sep_frames_win")
+    return out
+
+
+def sep_istft_ola_win(frames, window, y, origin, end, s0, nseg):
+    """sep_istft_ola into a window: y [R, cap] holds the absolute samples [origin, origin + cap), cut at end (m2h_sep_istft_ola_win)."""
+    _chk(frames, "sep_istft_ola_win(frames)")
+    _chk(window, "sep_istft_ola_win(window)")
+    _chk(y, "sep_istft_ola_win(y)")
+    if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
+        raise RuntimeError("m2h.sep_istft_ola_win: y must be [R, cap], got %s" % (tuple(y.shape),))
+    R, cap = y.shape
+    if tuple(frames.shape) != (nseg * R * SEP_FRAMES, SEP_LD) or window.numel() < 1022:
+        raise RuntimeError("m2h.sep_istft_ola_win: expected frames [%d, %d] and a 1022-point window, got %s and %d points"
+                           % (nseg * R * SEP_FRAMES, SEP_LD, tuple(frames.shape), window.numel()))
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().m2h_sep_istft_ola_win(_ptr(frames), _ptr(window), _ptr(y), R, cap, int(origin), int(end), int(s0), int(nseg), _stream(y)),
+                   "m2h_sep_istft_ola_win")
+    return y
+
+
+def sep_istft_xfade_win(frames, window, xwin, y, origin, end, hop, s0, nseg):
+    """sep_istft_xfade into a window: y [R, cap] holds the absolute samples [origin, origin + cap) and keeps, between calls, the partial
+    sums of the samples that later segments still cover (m2h_sep_istft_xfade_win)."""
+    _chk(frames, "sep_istft_xfade_win(frames)")
+    _chk(window, "sep_istft_xfade_win(window)")
+    _chk(xwin, "sep_istft_xfade_win(xwin)")
+    _chk(y, "sep_istft_xfade_win(y)")
+    if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
+        raise RuntimeError("m2h.sep_istft_xfade_win: y must be [R, cap], got %s" % (tuple(y.shape),))
+    R, cap = y.shape
+    if tuple(frames.shape) != (nseg * R * SEP_FRAMES, SEP_LD) or window.numel() < 1022 or xwin.numel() != SEP_SEGMENT:
+        raise RuntimeError("m2h.sep_istft_xfade_win: expected frames [%d, %d], a 1022-point window and a %d-point cross-fade window, got %s, %d and %d points"
+                           % (nseg * R * SEP_FRAMES, SEP_LD, SEP_SEGMENT, tuple(frames.shape), window.numel(), xwin.numel()))
+    with torch.cuda.device(y.device):
+        _lib.check(_lib.load().m2h_sep_istft_xfade_win(_ptr(frames), _ptr(window), _ptr(xwin), _ptr(y), R, cap, int(origin), int(end), int(hop), int(s0),
+                                                       int(nseg), _stream(y)), "m2h_sep_istft_xfade_win")
+    return y
+
+
+def resample_poly_win(x, G, up, down, origin, end, n_first, count, out=None):
+    """Outputs [n_first, n_first + count) of resample_poly's definition, [rows, count], from the window x [rows, cap] that holds the
+    absolute samples [origin, origin + cap) of rows of which `end` samples have arrived (m2h_resample_poly_win).  Bit-identical to the
+    same outputs of one resample_poly call over the whole rows."""
+    _chk(x, "resample_poly_win(x)")
+    _chk(G, "resample_poly_win(G)")
+    up, down, count = int(up), int(down), int(count)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise RuntimeError("m2h.resample_poly_win: expected a window [rows, cap] with cap >= 1, got %s" % (tuple(x.shape),))
+    if up < 1 or down < 1 or G.dim() != 2 or G.shape[0] != up:
+        raise RuntimeError("m2h.resample_poly_win: expected a [up, T] table for the ratio %d/%d, got %s" % (up, down, tuple(G.shape)))
+    if G.device != x.device:
+        raise RuntimeError("m2h.resample_poly_win: the table lives on %s, x on %s" % (G.device, x.device))
+    rows, cap = x.shape
+    if out is None:
+        out = torch.empty((rows, max(count, 0)), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, "resample_poly_win(out)")
+        if tuple(out.shape) != (rows, count) or out.device != x.device:
+            raise RuntimeError("m2h.resample_poly_win: out must be [%d, %d] on %s, got %s on %s" % (rows, count, x.device, tuple(out.shape), out.device))
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().m2h_resample_poly_win(_ptr(x), _ptr(G), _ptr(out), rows, cap, int(origin), int(end), int(n_first), count, up, down, G.shape[1],
+                                                     _stream(x)), "m2h_resample_poly_win")
+    return out

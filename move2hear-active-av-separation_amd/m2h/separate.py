@@ -61,6 +61,25 @@ In HIP: m2h_sep_bin_rows scales the forward GEMM's rows in place (masks are bin-
 the inverse GEMM's operand, and the inverse GEMM's rows are those of 2R mono recordings -- row ((sl*R + r)*2 + c)*32 + t is row
 ((sl*2R + (2r + c))*32 + t -- so m2h_sep_istft_ola / m2h_sep_istft_xfade write the contiguous [R, 2, L] result viewed as [2R, L].
 
+A live feed (``st = sep.stream(target_class, recordings=R, use_memory=None, sample_rate=16000, overlap=1, output="mono")``): the same
+separation for a recording that arrives block by block.  st.push(block [R, 2, n]), n >= 0, returns the samples that became final
+([R, m], [R, 2, m] or the pair, m >= 0), st.flush() the rest, st.reset() goes back to sample 0 with the same buffers.
+  * Defining property: with x the blocks pushed so far, concatenated, the returned pieces, concatenated, equal
+    sep.separate(x, target_class, use_memory=..., sample_rate=..., overlap=..., output=...), whatever the blocking; after flush() they
+    hold exactly L samples.  Bit for bit where the pushes run the batches separate() runs, to the U-Nets' batch-size tolerance otherwise;
+  * segment s is processed as soon as sample s * H + 15999 has arrived; a sample is final once every segment that covers it is done, so
+    after P samples exactly stream_emitted(P, overlap) = H * ((P - 16000) div H + 1) have been returned (0 while P < 16000).  No segment
+    of the future covers a final sample: W[n] does not depend on the unknown L.  flush() processes every remaining segment with
+    s * H < L (samples at or past L zero, as offline) and cuts the output at L;
+  * at another rate every stage returns all that its input determines (the converter emits output n once input sample
+    (n * down + half) div up has arrived: m2h.audio.resample.ResamplerStream), stream_returned(P, sample_rate, overlap) samples after P,
+    and the backlog stays under 1.01 seconds;
+  * the memory keeps one state per chain c = s mod overlap, zeros at the start, carried across pushes; the segments that complete in one
+    push are one segment-major U-Net batch, split at max_segments rows; several streams of one Separator do not disturb each other;
+  * the input and the cross-fade's partial sums live in windows [rows][cap] of absolute samples [origin, origin + cap) read and written
+    by the window forms of the glue kernels (m2h_sep_frames_win, m2h_sep_istft_ola_win, m2h_sep_istft_xfade_win, m2h_resample_poly_win:
+    the offline kernels' arithmetic, bit for bit); a push costs O(block + one second).  return_spectrograms is not offered.
+
 The two DFTs are dense 1024 x 1024 GEMMs (ops.linear) and follow the calling thread's arithmetic like the U-Nets; framing, the
 magnitude / phasor store, the inverse transform's operand and the overlap-add are the HIP kernels of csrc/separate.hip, which
 read the recording and write the output in place: no padded, framed or angle copies.
@@ -337,3 +356,214 @@ class Separator:
         if single:
             res = tuple(a[0] for a in res)
         return res[0] if len(res) == 1 else res
+
+    def stream(self, target_class, recordings, use_memory=None, sample_rate=SAMPLE_RATE, overlap=1, output="mono"):
+        """A SeparatorStream: the same separation for `recordings` binaural feeds that arrive block by block (module docstring,
+        "A live feed").  The argument checks are separate()'s."""
+        return SeparatorStream(self, target_class, recordings, use_memory, sample_rate, overlap, output)
+
+
+def stream_emitted(P, overlap):
+    """Samples a 16 kHz SeparatorStream has returned once P samples have arrived (before flush): segment s is processed as soon as
+    sample s * H + 15999 is there, H = 16000 / overlap, and a sample is final once no later segment covers it.  Pure Python; P may be an
+    int or an integer numpy array."""
+    if isinstance(overlap, bool) or overlap not in OVERLAPS:
+        raise ValueError("stream_emitted: overlap must be one of %s, got %r" % (OVERLAPS, overlap))
+    hop = SEGMENT // int(overlap)
+    n = hop * ((P - SEGMENT) // hop + 1)
+    return np.maximum(n, 0) if isinstance(n, np.ndarray) else max(0, n)
+
+
+def stream_returned(P, sample_rate, overlap):
+    """Samples a SeparatorStream at any supported rate has returned once P samples have arrived (before flush): every stage returns all
+    that its input determines -- the converter to 16 kHz (m2h.audio.resample.ready_outputs), stream_emitted, the converter back.  The
+    backlog P - stream_returned(P) stays under 1.01 seconds.  Pure Python; P may be an int or an integer numpy array."""
+    from .audio.resample import ratio, ready_outputs
+    if sample_rate == SAMPLE_RATE:
+        return stream_emitted(P, overlap)
+    up, down = ratio(sample_rate, SAMPLE_RATE)
+    return ready_outputs(stream_emitted(ready_outputs(P, up, down), overlap), down, up)
+
+
+class SeparatorStream:
+    """Separator.stream(...): push(block [R, 2, n]) returns what is final, flush() the rest.  The pieces, concatenated, are
+    separate() of the concatenated blocks (module docstring, "A live feed").  Holds the windows of the input and of the cross-fade's
+    partial sums (m2h.audio.resample.SampleWindow), one memory state per chain and, for other sample rates, three ResamplerStreams."""
+
+    def __init__(self, sep, target_class, recordings, use_memory=None, sample_rate=SAMPLE_RATE, overlap=1, output="mono"):
+        from .audio.resample import SampleWindow
+        if isinstance(overlap, bool) or overlap not in OVERLAPS:
+            raise ValueError("m2h.Separator: overlap must be one of %s, got %r" % (OVERLAPS, overlap))
+        if not isinstance(output, str) or output not in OUTPUTS:
+            raise ValueError("m2h.Separator: output must be one of %s, got %r" % (OUTPUTS, output))
+        self.want_mono, self.want_bin = output != "binaural", output != "mono"
+        if not self.want_mono and use_memory:
+            raise ValueError("m2h.Separator: output=\"binaural\" runs no acoustic memory (it refines the mono prediction only); "
+                             "leave use_memory at None or False, or ask for output=\"both\"")
+        if isinstance(recordings, bool) or int(recordings) != recordings or recordings < 1:
+            raise ValueError("m2h.Separator: recordings must be a positive int, got %r" % (recordings,))
+        if use_memory is None:
+            use_memory = self.want_mono and sep.memory is not None
+        if use_memory and sep.memory is None:
+            raise RuntimeError("m2h.Separator: use_memory=True, but the checkpoint has no acoustic_mem.cnn.* weights")
+        self.sep, self.R, self.overlap, self.hop, self.use_memory = sep, int(recordings), int(overlap), SEGMENT // int(overlap), bool(use_memory)
+        R, dev = self.R, sep.device
+        tc = torch.as_tensor(target_class, dtype=torch.int64).reshape(-1)
+        if tc.numel() == 1:
+            tc = tc.expand(R)
+        if tc.numel() != R:
+            raise RuntimeError("m2h.Separator: target_class must be one int or one per recording (%d), got %d values" % (R, tc.numel()))
+        self.tc = tc.to(dev).contiguous()
+        self.to16 = self.back_mono = self.back_bin = None
+        if sample_rate != SAMPLE_RATE:
+            to16, back = sep.resamplers(sample_rate)
+            self.to16 = to16.stream((R, 2))
+            self.back_mono = back.stream((R,)) if self.want_mono else None
+            self.back_bin = back.stream((R, 2)) if self.want_bin else None
+        if self.overlap > 1 and sep._win_xfade is None:
+            sep._win_xfade = torch.from_numpy(crossfade_window()).to(dev)
+        self.win_in = SampleWindow((R, 2), dev)
+        self.win_mono = SampleWindow((R,), dev) if self.want_mono and self.overlap > 1 else None
+        self.win_bin = SampleWindow((R, 2), dev) if self.want_bin and self.overlap > 1 else None
+        self.reset()
+
+    def reset(self):
+        """Back to sample 0: the same settings and buffers, the memory's states cleared."""
+        self.received = self.emitted = 0          # samples of the caller's rate
+        self.P16 = self.next_seg = 0              # 16 kHz samples received, segments processed
+        self.closed = False
+        self.states = [None] * self.overlap
+        for w in (self.win_in, self.win_mono, self.win_bin):
+            if w is not None:
+                w.clear()
+        for rs in (self.to16, self.back_mono, self.back_bin):
+            if rs is not None:
+                rs.reset()
+
+    def _empty(self):
+        dev = self.sep.device
+        return ((torch.empty((self.R, 0), device=dev),) if self.want_mono else ()) + ((torch.empty((self.R, 2, 0), device=dev),) if self.want_bin else ())
+
+    def _memory(self, P, c0, cn):
+        """The memory over the rows of segments [c0, c0 + cn): up to `overlap` consecutive segments -- one per chain -- per call, each on its
+        own chain's state."""
+        R, k, mem = self.R, self.overlap, self.sep.memory
+        steps = []
+        with self.sep._memory_scope(k * R):
+            for sl in range(0, cn, k):
+                segs = range(c0 + sl, c0 + min(sl + k, cn))
+                pm = P[sl * R:(sl + len(segs)) * R]
+                prev = [self.states[s % k] if self.states[s % k] is not None else torch.zeros_like(pm[:R]) for s in segs]
+                out = mem(pm, prev[0] if len(prev) == 1 else torch.cat(prev))
+                for i, s in enumerate(segs):
+                    self.states[s % k] = out[i * R:(i + 1) * R]
+                steps.append(out)
+        return torch.cat(steps) if len(steps) > 1 else steps[0]
+
+    def _write(self, out_frames, win, y, rows, origin, end, c0, cn):
+        sep = self.sep
+        if self.overlap == 1:
+            ops.sep_istft_ola_win(out_frames, sep._win_inv, y.view(rows, -1), origin, end, c0, cn)
+        else:
+            ops.sep_istft_xfade_win(out_frames, sep._win_inv, sep._win_xfade, win.buf.view(rows, win.cap), origin, end, self.hop, c0, cn)
+
+    def _core(self, block, final):
+        """One block [R, 2, n] at 16 kHz -> the samples that became final, as a tuple (mono?, binaural?)."""
+        sep, R, k, H = self.sep, self.R, self.overlap, self.hop
+        s1 = self.next_seg
+        self.win_in.advance(min(s1 * H, self.P16), block)
+        self.P16 += block.shape[-1]
+        end = self.P16
+        ready = -(-end // H) if final else (0 if end < SEGMENT else (end - SEGMENT) // H + 1)
+        ns = ready - s1
+        if ns <= 0:
+            return self._empty()
+        origin = s1 * H
+        stop = min(end, (s1 + ns - 1) * H + SEGMENT)                 # the samples these segments cover: [origin, stop)
+        m = (stop if final else (s1 + ns) * H) - origin              # of which final
+        y = yb = None
+        if k == 1:
+            y = torch.empty((R, m), device=sep.device, dtype=torch.float32) if self.want_mono else None
+            yb = torch.empty((R, 2, m), device=sep.device, dtype=torch.float32) if self.want_bin else None
+        else:
+            for w in (self.win_mono, self.win_bin):
+                if w is not None:
+                    w.advance(origin, extra=stop - origin - w.fill)
+        per = max(1, sep.max_segments // R)
+        for c0 in range(s1, s1 + ns, per):
+            cn = min(per, s1 + ns - c0)
+            N = cn * R
+            frames = ops.sep_frames_win(self.win_in.buf, sep._win_fwd, self.win_in.origin, end, H, c0, cn)
+            spec = ops.linear(frames, sep._W_fwd, None, name="separate.dft")
+            mag, phasor = ops.sep_stft_post(spec, N)
+            del frames
+            if not self.want_bin:
+                del spec
+            masks = sep.policy.get_binSepMasks({"mixed_bin_audio_mag": mag, "target_class": self.tc.repeat(cn)})
+            if self.want_bin:
+                masks = masks.contiguous()
+                rows = ops.sep_bin_rows(spec, masks)
+                del spec
+                out_frames = ops.linear(rows, sep._W_inv, None, name="separate.idft")
+                del rows
+                self._write(out_frames, self.win_bin, yb, 2 * R, origin, end, c0, cn)
+                del out_frames
+                if not self.want_mono:
+                    continue
+            P = sep.policy.convert_bin2mono(masks, mixed_audio=mag)
+            if self.use_memory:
+                P = self._memory(P, c0, cn)
+            rows = ops.sep_istft_pre(P, phasor)
+            out_frames = ops.linear(rows, sep._W_inv, None, name="separate.idft")
+            self._write(out_frames, self.win_mono, y, R, origin, end, c0, cn)
+        self.next_seg = s1 + ns
+        if k > 1:
+            res = ()
+            for w in (self.win_mono, self.win_bin):
+                if w is not None:
+                    res += (w.buf[..., :m].clone(),)
+                    w.advance(origin + m)                            # the partial sums that later segments still cover stay
+            return res
+        return ((y,) if self.want_mono else ()) + ((yb,) if self.want_bin else ())
+
+    def _step(self, block, final):
+        with torch.cuda.device(self.sep.device), ops.math_scope(self.sep.math):
+            if self.to16 is None:
+                res = self._core(block, final)
+            else:
+                b16 = self.to16.push(block)
+                if final:
+                    b16 = torch.cat((b16, self.to16.flush()), dim=-1)
+                pieces = self._core(b16, final)
+                res = ()
+                for piece, back in zip(pieces, [b for b in (self.back_mono, self.back_bin) if b is not None]):
+                    out = back.push(piece)
+                    if final:
+                        out = torch.cat((out, back.flush()), dim=-1)[..., :self.received - self.emitted].contiguous()   # never short (separate())
+                    res += (out,)
+        self.emitted += res[0].shape[-1]
+        return res[0] if len(res) == 1 else res
+
+    @torch.no_grad()
+    def push(self, block):
+        """block [R, 2, n] fp32 on the separator's device, n >= 0 -> the samples that became final: [R, m], [R, 2, m] or the pair."""
+        if self.closed:
+            raise RuntimeError("m2h.SeparatorStream: push after flush")
+        if not torch.is_tensor(block):
+            raise RuntimeError("m2h.SeparatorStream: a block must be a torch tensor, got %s" % type(block).__name__)
+        if block.dim() != 3 or block.shape[0] != self.R or block.shape[1] != 2:
+            raise RuntimeError("m2h.SeparatorStream: expected a block [%d, 2, n], got %s" % (self.R, tuple(block.shape)))
+        if block.dtype != torch.float32:
+            raise RuntimeError("m2h.SeparatorStream: a block must be float32, got %s" % block.dtype)
+        if block.device != self.sep.device:
+            raise RuntimeError("m2h.SeparatorStream: the block lives on %s, the separator on %s" % (block.device, self.sep.device))
+        self.received += block.shape[2]
+        return self._step(block, False)
+
+    @torch.no_grad()
+    def flush(self):
+        """The rest: every remaining segment, samples past the end zero, the output cut at the number of samples pushed.  Closes the stream."""
+        if self.closed:
+            raise RuntimeError("m2h.SeparatorStream: flush after flush")
+        self.closed = True
+        return self._step(torch.empty((self.R, 2, 0), device=self.sep.device, dtype=torch.float32), True)

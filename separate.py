@@ -2,7 +2,7 @@
 """Separate one sound class out of a binaural recording of any length:
 
     python separate.py --ckpt F --in mix.wav --target-class K --out out.wav [--no-memory] [--math fp32|bf16x3] [--resample] [--overlap 1|2|4]
-                       [--output mono|binaural|both] [--out-binaural bin.wav]
+                       [--output mono|binaural|both] [--out-binaural bin.wav] [--stream-block N]
 
 ``--ckpt``: a passive-separator checkpoint or a PPO checkpoint (``{"state_dict", "config"}`` file or a bare state dict, with or
 without the ``actor_critic.`` root).  ``--in``: a two-channel WAV at 16 kHz, int16 or float32.  The output is a mono WAV of the
@@ -15,6 +15,9 @@ non-overlapping seconds; the default 1 is the plain path.
 the first U-Net's clamped mask; no memory, and ``--no-memory`` changes nothing).  ``--output both``: the mono WAV goes to ``--out`` and
 the two-channel WAV to ``--out-binaural``, which is required then and an error otherwise.  Both have the input's rate, length and
 sample format.
+``--stream-block N``: read the input N frames at a time, push every block through a stream (Separator.stream) and write what comes
+back as it comes: the recording is never whole in GPU memory, and the result is that of the one-call path (the same samples up to the
+batch size of the U-Nets, which follows the blocks).  Works with every option above.
 Semantics, the conversion's and the cross-fade's definition: m2h/separate.py.
 """
 import argparse
@@ -52,6 +55,74 @@ def to_wav_samples(y, dtype):
     return y.astype(np.float32)
 
 
+def open_wav(path, resample=False):
+    """read_wav without reading: -> (the file's samples [L, 2] memory-mapped, their numpy dtype, the file's sample rate)"""
+    import numpy as np
+    from scipy.io import wavfile
+    rate, data = wavfile.read(path, mmap=True)
+    if rate != SAMPLE_RATE and not resample:
+        raise SystemExit("separate.py: %s is sampled at %d Hz; 16000 Hz is required (pass --resample to convert it on the GPU and back)" % (path, rate))
+    if data.ndim != 2 or data.shape[1] != 2 or data.shape[0] < 1:
+        raise SystemExit("separate.py: %s must be a two-channel (binaural) recording, got an array of shape %s" % (path, data.shape))
+    if data.dtype not in (np.int16, np.float32):
+        raise SystemExit("separate.py: %s holds %s samples; int16 or float32 is required" % (path, data.dtype))
+    return data, data.dtype, int(rate)
+
+
+class WavWriter:
+    """A WAV file written piece by piece: int16 PCM or IEEE float32, the sizes of the header filled in on close."""
+
+    def __init__(self, path, rate, channels, dtype):
+        import struct
+        import numpy as np
+        self.f = open(path, "wb")
+        self.dtype, self.frames, self.channels = np.dtype(dtype), 0, channels
+        width = self.dtype.itemsize
+        self.f.write(b"RIFF" + struct.pack("<I", 0) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1 if self.dtype == np.int16 else 3, channels, rate,
+                                                                                         rate * channels * width, channels * width, 8 * width))
+        self.f.write(b"data" + struct.pack("<I", 0))
+
+    def write(self, y):
+        """y: float32 [n] or [channels, n]"""
+        import numpy as np
+        samples = to_wav_samples(y.T if y.ndim == 2 else y, self.dtype)
+        self.f.write(np.ascontiguousarray(samples).astype("<" + self.dtype.str[1:]).tobytes())
+        self.frames += samples.shape[0]
+
+    def close(self):
+        import struct
+        size = self.frames * self.channels * self.dtype.itemsize
+        self.f.seek(4)
+        self.f.write(struct.pack("<I", 36 + size))
+        self.f.seek(40)
+        self.f.write(struct.pack("<I", size))
+        self.f.close()
+
+
+def stream_file(sep, args, data, dtype, rate):
+    """--stream-block: the file's blocks through a SeparatorStream, every returned piece written at once."""
+    import numpy as np
+    import torch
+    st = sep.stream(args.target_class, recordings=1, use_memory=False if args.no_memory else None, sample_rate=rate, overlap=args.overlap, output=args.output)
+    paths = (args.out, args.out_binaural) if args.output == "both" else (args.out,)
+    writers = [WavWriter(p, rate, 2 if (args.output == "binaural" or i == 1) else 1, dtype) for i, p in enumerate(paths)]
+    scale = np.float32(1.0 / 32768.0)
+
+    def put(res):
+        for w, y in zip(writers, res if isinstance(res, tuple) else (res,)):
+            if y.shape[-1]:
+                w.write(y[0].cpu().numpy())
+
+    for a in range(0, data.shape[0], args.stream_block):
+        block = np.asarray(data[a:a + args.stream_block])
+        block = block.astype(np.float32) * scale if dtype == np.int16 else block
+        put(st.push(torch.from_numpy(np.ascontiguousarray(block.T)).to(sep.device).unsqueeze(0)))
+    put(st.flush())
+    for w in writers:
+        w.close()
+    return [(p, w.frames, w.channels) for p, w in zip(paths, writers)]
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument("--ckpt", required=True)
@@ -66,10 +137,16 @@ def main():
     parser.add_argument("--output", choices=["mono", "binaural", "both"], default="mono",
                         help="mono: the target's mono waveform; binaural: the target in both ears (two channels); both: mono to --out, binaural to --out-binaural")
     parser.add_argument("--out-binaural", default=None, help="with --output both: the two-channel WAV")
+    parser.add_argument("--stream-block", type=int, default=None, help="read the input N frames at a time and push them through a stream")
     args = parser.parse_args()
+    if args.stream_block is not None and args.stream_block < 1:
+        parser.error("--stream-block needs a positive number of frames")
     if (args.output == "both") != (args.out_binaural is not None):
         parser.error("--output both needs --out-binaural PATH, and --out-binaural is given with --output both only")
-    wave, dtype, rate = read_wav(args.inp, args.resample)
+    if args.stream_block is not None:
+        wave, dtype, rate = open_wav(args.inp, args.resample)
+    else:
+        wave, dtype, rate = read_wav(args.inp, args.resample)
     if rate != SAMPLE_RATE:
         from m2h.audio.resample import ratio
         try:
@@ -83,6 +160,12 @@ def main():
     dev = torch.device("cuda", 0)
     sep = Separator(args.ckpt, dev, math=ops.MATH_FP32 if args.math == "fp32" else ops.MATH_BF16X3,
                     max_segments=args.max_segments or DEFAULT_MAX_SEGMENTS)
+    if args.stream_block is not None:
+        for path, frames, channels in stream_file(sep, args, wave, dtype, rate):
+            memory = "on" if (channels == 1 and sep.memory is not None and not args.no_memory) else "off"
+            print("separate.py: wrote %s (%d samples at %d Hz, %.2f s, class %d, memory %s, %s, overlap %d, blocks of %d)%s" % (
+                path, frames, rate, frames / rate, args.target_class, memory, args.math, args.overlap, args.stream_block, ", two channels" if channels == 2 else ""))
+        return
     res = sep.separate(torch.from_numpy(wave).to(dev), args.target_class, use_memory=False if args.no_memory else None, sample_rate=rate,
                        overlap=args.overlap, output=args.output)
     outs = ((args.out, res[0]), (args.out_binaural, res[1])) if args.output == "both" else ((args.out, res),)

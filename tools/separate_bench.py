@@ -32,6 +32,12 @@ Separator.separate is asked for.  "binaural" runs the first U-Net only, no memor
 is seconds of input audio per second whatever comes out.  The driver runs mono, binaural, both, mono per case: the two mono runs
 give the margin ("binaural_no_slower_than_mono": binaural's rate >= mono's slower run less the spread of mono's two runs).
 
+--stream [--out profiles/separate_stream.json] (this process): a live feed.  For R = 1 and R = 16 in bf16x3, memory on, at 16 kHz overlap 1,
+16 kHz overlap 4 and 44.1 kHz overlap 1: a Separator.stream is pushed one hop of audio at a time (16000 / overlap samples at 16 kHz, one
+second at 44.1 kHz), so that every push after the first second completes exactly one segment.  Every push lies between two HIP events
+and is followed by a synchronise; reported are the median and the maximum over the timed pushes (events, and the host's wall clock
+around push + synchronise), and the same figures for the same second sent as a one-second Separator.separate call, in the same run.
+
 Weights are synthetic.policy_shapes() with the acoustic memory's weights scaled by 0.25: as generated they are not contractive,
 and a recurrence over 600 steps would overflow expm1.  Every GPU step runs under its own timeout and the driver stops at the
 first failure.
@@ -297,8 +303,76 @@ def resample_alone(wave, to16, back, c_to16, c_back, reps):
     return out
 
 
+STREAM_CASES = ((16000, 1), (16000, 4), (44100, 1))       # sample rate, overlap
+STREAM_WARMUP, STREAM_PUSHES = 6, 40
+
+
+def run_stream(out_path=None):
+    import statistics
+    import time
+    import numpy as np
+    import torch
+    from m2h import ops, synthetic
+    from m2h.separate import Separator
+    if not torch.cuda.is_available():
+        raise SystemExit("separate_bench: no GPU; this measurement has no CPU path")
+    dev = torch.device("cuda", 0)
+    sd = synthetic.make_state_dict(synthetic.policy_shapes(), 2)
+    for k in sd:
+        if k.startswith("acoustic_mem."):
+            sd[k] = sd[k] * np.float32(0.25)
+    sep = Separator(sd, dev, math=ops.MATH_BF16X3)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return out, e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3
+
+    def figures(ms):
+        return {"median_ms": statistics.median(ms), "max_ms": max(ms), "min_ms": min(ms), "n": len(ms)}
+
+    results = []
+    for R in (1, 16):
+        tc = torch.full((R,), 4, dtype=torch.int64, device=dev)
+        for rate, overlap in STREAM_CASES:
+            block = rate // overlap
+            per_second = rate // block
+            n = per_second + STREAM_WARMUP + STREAM_PUSHES
+            g = torch.Generator(device=dev).manual_seed(7)
+            wave = torch.randn((R, 2, n * block), device=dev, generator=g) * 0.05
+            wave += 0.3 * torch.sin(2 * np.pi * 440.0 * torch.arange(n * block, device=dev) / float(rate))
+            st = sep.stream(tc, recordings=R, use_memory=True, sample_rate=rate, overlap=overlap)
+            ev, wall = [], []
+            for i in range(n):
+                seg0 = st.next_seg
+                y, ms, w = timed(lambda: st.push(wave[:, :, i * block:(i + 1) * block].contiguous()))
+                if i >= per_second + STREAM_WARMUP - 1 and st.next_seg == seg0 + 1:          # a push that completes one segment
+                    ev.append(ms)
+                    wall.append(w)
+            st.flush()
+            second = wave[:, :, :rate].contiguous()
+            for _ in range(STREAM_WARMUP):
+                sep.separate(second, tc, use_memory=True, sample_rate=rate, overlap=overlap)
+            one = [timed(lambda: sep.separate(second, tc, use_memory=True, sample_rate=rate, overlap=overlap))[1:] for _ in range(STREAM_PUSHES)]
+            res = {"R": R, "sample_rate": rate, "overlap": overlap, "math": "bf16x3", "memory": True, "block_samples": block,
+                   "push_events": figures(ev), "push_wall": figures(wall), "one_second_separate_events": figures([a for a, _ in one]),
+                   "one_second_separate_wall": figures([b for _, b in one]), "segments_per_separate_call": overlap}
+            print(json.dumps(res), flush=True)
+            results.append(res)
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump({"tool": "tools/separate_bench.py --stream", "device": "MI355X (gfx950)", "results": results}, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stream", action="store_true", help="per-push times of a live feed against one-second separate() calls (this process)")
     ap.add_argument("--case", choices=sorted(CASES), default=None)
     ap.add_argument("--math", choices=["fp32", "bf16x3"], default="bf16x3")
     ap.add_argument("--path", choices=["new", "composed", "both"], default="both")
@@ -312,6 +386,9 @@ def main():
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=240, help="driver mode: seconds per case")
     args = ap.parse_args()
+    if args.stream:
+        run_stream(args.out)
+        return
     if args.case is not None:
         if args.outputs:
             run_outputs(args.case, args.math, args.max_segments)
