@@ -14,7 +14,10 @@ Row geometry (kind):
   c3    Conv2d(3, 1, 1); H x W is the image
   lin   nn.Linear over B rows of C0 floats (H = W = 1)
   full  a conv whose window is the whole H x W image: one output pixel per sample
-M = B * H * W GEMM rows (per phase for `up`); `split` = sources and weights in the split32 layout (bf16x3 only)."""
+M = B * H * W GEMM rows (per phase for `up`); `split` = sources and weights in the split32 layout (bf16x3 only).
+
+run() is the launch the facts were recorded from; run_on() is the same launch on the caller's data in the torch layouts, for
+tests/test_gpu_forward_fp64.py, which checks every row's values against float64."""
 import ctypes
 
 import torch
@@ -237,4 +240,82 @@ def run(row, dev):
         _lib.check(lib.m2h_conv_igemm_f32(ctypes.byref(a), ops._stream(out)), "m2h_conv_igemm_f32")
         launches = int(lib.m2h_launch_count() - n0)
         label = ops.last_kernel()
+    return out, label, launches, wsb
+
+
+def args_of(row):
+    """conv_args(row), and one more kind for the forms only tests/test_gpu_forward_fp64.py holds (no row of the table has it):
+      c1    Conv2d(1, 1, 0) over an H x W image"""
+    if row["kind"] != "c1":
+        return conv_args(row)
+    a, Hi, Wi, Ho, Wo, _ = conv_args(dict(row, kind="c3"))
+    a.nth, a.ntw, a.offh, a.offw = 1, 1, 0, 0
+    return a, Hi, Wi, Ho, Wo, row["C0"] + row["C1"]
+
+
+def run_on(row, dev, x, x2, w, scale, shift, cls_val=None, head=None, deslice=False, dst_split=False, dst=None, ldc=None):
+    """The row's layer on the caller's data: the same geometry (conv_args; args_of), default knobs and the workspace the library asks for, as run()
+    -- but from fp32 CPU tensors in the torch layouts, packed by the library's own packers, so that the packers and the sub-pixel phase /
+    tap map of include/m2h.h sit between the caller's reference and the output too (run() fills the packed buffer directly).
+      x, x2   NCHW [B][C0][Hi][Wi] / [B][C1][Hi][Wi] (x2 None when C1 == 0)
+      w       Conv2d [N][C0 + C1][kh][kw]; `up`: ConvTranspose2d [C0 + C1][N][4][4]; `lin` / `full`: [N][C0][H][W]
+      scale, shift   [N] or None (the folded BatchNorm of a `down` / `up` row)
+    `split` rows get ops.split32 of the sources and of the packed weights.  Forms the table's rows do not hold:
+      cls_val    [B]: w carries one more input channel (C0 + 1), packed with ci_used = C0; that channel enters as the class plane
+                 (ops.unet_class_table of it, times cls_val[b])
+      head       (head_w [N][N], head_b [N]): the fused 1x1 head, de-sliced output, no workspace
+      deslice    OUT_DESLICE: the output is [B][16 Ho][Wo][N / 16]
+      dst_split  FMT_DST_SPLIT: the output rows are written in the split32 layout
+      dst, ldc   a caller-owned destination on the device whose rows are ldc >= N floats apart (a column block of a wider matrix)
+    Returns (output tensor on the device -- NHWC unless a form above says otherwise, label, launches, workspace bytes)."""
+    from m2h import _lib, ops
+    kind, B, C0, C1, N = (row[k] for k in ("kind", "B", "C0", "C1", "N"))
+    a, Hi, Wi, Ho, Wo, K = args_of(row)
+    assert tuple(x.shape) == (B, C0, Hi, Wi) and (x2 is None) == (C1 == 0) and (x2 is None or tuple(x2.shape) == (B, C1, Hi, Wi))
+
+    def nhwc(t):
+        return t.permute(0, 2, 3, 1).contiguous().to(dev)
+
+    xd, x2d, wd = nhwc(x), (nhwc(x2) if C1 else None), w.contiguous().to(dev)
+    keep = []
+    if kind == "up":
+        assert tuple(w.shape) == (C0 + C1, N, 4, 4) and cls_val is None
+        wp = ops.pack_convT_weight(wd)
+    elif cls_val is not None:
+        assert tuple(w.shape) == (N, C0 + 1, a.nth, a.ntw) and C1 == 0
+        wp = ops.pack_conv_weight(wd, ci_used=C0)
+        keep += [ops.unet_class_table(wd, C0), cls_val.contiguous().to(dev)]
+        a.cls_table, a.cls_val = keep[0].data_ptr(), keep[1].data_ptr()
+    else:
+        assert tuple(w.shape) == (N, C0 + C1, a.nth, a.ntw)
+        wp = ops.pack_conv_weight(wd)
+    assert wp.numel() == N * K
+    if row["split"]:
+        xd, x2d, wp = ops.split32(xd), (ops.split32(x2d) if C1 else None), ops.split32(wp)
+    if scale is not None:
+        keep += [scale.contiguous().to(dev), shift.contiguous().to(dev)]
+        a.scale, a.shift = keep[-2].data_ptr(), keep[-1].data_ptr()
+    if head is not None:
+        keep += [head[0].contiguous().to(dev), head[1].contiguous().to(dev)]
+        a.head_w, a.head_b = keep[-2].data_ptr(), keep[-1].data_ptr()
+        deslice = True
+    if deslice:
+        a.out_mode = ops.OUT_DESLICE
+    if dst_split:
+        a.operand_format |= ops.FMT_DST_SPLIT
+    if dst is not None:
+        out, a.ldc = dst, ldc
+    else:
+        out = torch.zeros((B, 16 * Ho, Wo, N // 16) if deslice else (B, Ho, Wo, N), device=dev, dtype=torch.float32)
+    a.src0, a.src1, a.wp, a.dst = xd.data_ptr(), (x2d.data_ptr() if C1 else None), wp.data_ptr(), out.data_ptr()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        wsb = 0 if head is not None else int(lib.m2h_conv_igemm_workspace_bytes(ctypes.byref(a)))
+        ws, _ = ops._workspace(wsb, dev)
+        a.workspace, a.workspace_bytes = (ws.data_ptr() if ws is not None else None), wsb
+        n0 = lib.m2h_launch_count()
+        _lib.check(lib.m2h_conv_igemm_f32(ctypes.byref(a), ops._stream(out)), "m2h_conv_igemm_f32")
+        launches = int(lib.m2h_launch_count() - n0)   # (the packers and split32 above launched before n0)
+        label = ops.last_kernel()
+        torch.cuda.synchronize(dev)   # the operands above live until the launch is done
     return out, label, launches, wsb

@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 import grad_routes as G
 import m2h_oracle as O
+from elem_bound import TAU_BF16X3, TAU_FP32, bound   # (the bound and its constants: shared with the forward route test)
 from m2h import functional as MF, ops
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +23,6 @@ pytestmark = pytest.mark.gpu
 # Calibrated on an MI355X (worst |g - r| / s over the whole table, printed per row with -s; test_zz_report_worst_ratios sums it up):
 # fp32 weight gradients 2.2e-6, fp32 input gradients 3.5e-6, bias gradients 6.1e-7, bf16x3 input gradients 3.0e-5 (products carry ~16
 # mantissa bits).  The bounds sit 6-10x above; one split's rows, a (1 - 1/S) scale or a tap column move the ratio by 1e-3 or more.
-TAU_FP32 = 2e-5
-TAU_BF16X3 = 2e-4
 MODES = {"fp32": ops.MATH_FP32, "bf16x3": ops.MATH_BF16X3}
 WORST = {}
 
@@ -39,20 +38,6 @@ def _nhwc(t, dev):
 
 def _nchw(t):
     return t.detach().permute(0, 3, 1, 2).cpu()
-
-
-def bound(g, r, s, tau):
-    """(worst |g - r| / s, least-squares scale <g, r> / <r, r>, holds): the element bound and the scale check together."""
-    g, r, s = g.double().reshape(-1), r.double().reshape(-1), s.double().reshape(-1)
-    d = (g - r).abs()
-    if bool(((s == 0) & (d > 0)).any()):
-        worst = float("inf")
-    else:
-        nz = s > 0
-        worst = float((d[nz] / s[nz]).max()) if bool(nz.any()) else 0.0
-    rr = float((r * r).sum())
-    scale = float((g * r).sum()) / rr if rr > 0 else 1.0
-    return worst, scale, worst <= tau and abs(scale - 1.0) <= tau
 
 
 def _check(name, row, mode, g, r, s, tau):
