@@ -344,6 +344,42 @@ int m2h_episode_stats_update(const m2h_episode_stats* st, const float* rewards, 
 int m2h_fftconv_full(const float* mono, const float* rirs, const float* twiddles, float* xspec, float* full, int CS, int L, int Lr,
                      int log2n, m2h_stream stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Auralizer (m2h/audio/render.py holds the definition; csrc/render.hip): uniformly partitioned overlap-add convolution of sources of
+ * any length with RIRs of up to 16 partitions.  Block = partition = M2H_RENDER_BLOCK samples, transform length 32768 (a packed
+ * 16384-point complex transform in 128 KB of LDS).  twiddles: [2][16384] complex fp32: first t[k] = exp(-2 pi i k / 32768), as
+ * m2h_fftconv_full's at log2n = 15, then the same values in the order the transform's stages read them: entry
+ * 16384 - (16384 >> s) + pos = t[(pos << s) * 2] for stage s < 14, pos < 8192 >> s (the last entry is unused).  A spectrum is 16384 complex fp32 values (128 KB): the real signal's spectrum S in natural order, slot k <= 8192
+ * holding S[k], slot 16384 - k holding conj(S[16384 - k]) and slot 0 the two real bins {S[0], S[16384]}.  A frame is the first
+ * 2 * M2H_RENDER_BLOCK samples of one inverse transform.  Every entry point checks its arguments, the windows included, and returns a
+ * negative status before any launch; fixed order, no atomics: results do not depend on how the work is cut into calls.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define M2H_RENDER_BLOCK 16000
+#define M2H_RENDER_MAX_PARTITIONS 16
+
+/* Forward spectra of rows of at most M2H_RENDER_BLOCK samples.  Row (o, c, i), o < n_outer, c < n_mid, i < n_inner, starts at
+ * x + o * outer_stride + c * mid_stride + i * inner_stride and has row_len samples at element stride elem_stride; its block b < nblk
+ * holds samples [(first_block + b) * 16000, + 16000), zero past row_len; every block must start inside the row.
+ * spec: [n_outer][n_mid][n_inner][nblk] spectra.  Sources [RS][L]: n_outer = RS, outer_stride = L, n_mid = n_inner = 1, elem_stride 1.
+ * Interleaved RIRs [RS][K][Lr][2], RIRs k0 .. k0 + nh - 1, both ears in one call: x + k0 * Lr * 2, n_outer = RS, outer_stride = K * Lr * 2,
+ * n_mid = nh, mid_stride = Lr * 2, n_inner = 2, inner_stride = 1, elem_stride 2, nblk = Pn: the layout m2h_render_frames reads. */
+int m2h_render_spectra(const float* x, const float* twiddles, float* spec, int n_outer, int n_mid, int n_inner, long long outer_stride,
+                       long long mid_stride, long long inner_stride, long long row_len, int elem_stride, int first_block, int nblk, m2h_stream stream);
+
+/* Frames m0 .. m0 + nm - 1 of RS (recording, source) pairs, both ears: frame m = IFFT(sum over p = 0 .. Pn-1 ascending with
+ * 0 <= m - p < J of X[m - p] * H[kappa(m - p)][p]), kappa(j) = 0 for K = 1 and j for K = J.  xspec: [RS][nx] spectra of the source
+ * blocks jx0 .. jx0 + nx - 1; hspec: [RS][nh][2 ears][Pn] spectra of the RIRs kh0 .. kh0 + nh - 1 (K = 1: kh0 = 0, nh = 1); both
+ * windows must hold what the frames read.  frames: [RS][nm][2][32000] fp32, 16-byte aligned.  Pn <= M2H_RENDER_MAX_PARTITIONS. */
+int m2h_render_frames(const float* xspec, const float* hspec, const float* twiddles, float* frames, int RS, int J, int Pn, int K, int m0, int nm,
+                      int jx0, int nx, int kh0, int nh, m2h_stream stream);
+
+/* Output blocks o0 .. o1 - 1 (samples [o0 * 16000, min(o1 * 16000, L_out))) of mix [R][2][L_out] and, unless NULL, images
+ * [R][S][2][L_out]: image[n] = frame_o[i] + frame_{o-1}[16000 + i] for n = o * 16000 + i (a frame outside [0, F) contributes
+ * nothing), mix = the fmaf chain over s = 0 .. S-1 of gains[r][s] * image.  frames as written by m2h_render_frames for the window
+ * m0 .. m0 + nm - 1, which must hold the frames these blocks read; F = J + Pn - 1 is the recording's frame count. */
+int m2h_render_mix(const float* frames, const float* gains, float* mix, float* images, int R, int S, int m0, int nm, int F, int o0, int o1,
+                   long long L_out, m2h_stream stream);
+
 /* Batched weight packing: up to M2H_PACK_BATCH_MAX tensors (re)packed by ONE launch; same index maps and results as the
  * single-tensor entry points.  kind / p[]:
  *   M2H_PACK_CONV      m2h_pack_conv_weight_ex:  p = {Co, Ci, KH, KW, ci_used, ci_out}     [Co][Ci][KH][KW] -> [Co][KH][KW][ci_out]

@@ -12,52 +12,9 @@
 // Twiddles exp(-2 pi i k / N) come from a table built on the host in float64 (setup data, like the DFT matrices of the STFT).
 // Arithmetic fp32 throughout, like the library transform it replaces (rocFFT through torch.fft in round 1).
 #include "m2h_internal.h"
+#include "fft_lds.h"   // cf, fft_dif / ifft_dit, the pair-wise unpack and re-pack
 
 namespace m2h {
-
-namespace {
-struct cf {
-  float x, y;
-};
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ cf cmulc(cf a, cf b) { return {a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y}; }   // a * conj(b)
-__device__ __forceinline__ cf cadd(cf a, cf b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ cf csub(cf a, cf b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ cf conj(cf a) { return {a.x, -a.y}; }
-}  // namespace
-
-// z: M complex values in LDS.  tw[k] = exp(-2 pi i k / (2M)), k < M.
-template <int LOGM>
-__device__ __forceinline__ void fft_dif(cf* z, const cf* __restrict__ tw) {
-  constexpr int M = 1 << LOGM;
-  for (int s = 0; s < LOGM; ++s) {
-    const int half = M >> (s + 1);
-    for (int j = threadIdx.x; j < M / 2; j += blockDim.x) {
-      const int g = j / half, pos = j - g * half;
-      const int i0 = g * 2 * half + pos, i1 = i0 + half;
-      const cf a = z[i0], b = z[i1];
-      z[i0] = cadd(a, b);
-      z[i1] = cmul(csub(a, b), tw[(pos << s) * 2]);
-    }
-    __syncthreads();
-  }
-}
-
-template <int LOGM>
-__device__ __forceinline__ void ifft_dit(cf* z, const cf* __restrict__ tw) {
-  constexpr int M = 1 << LOGM;
-  for (int s = LOGM - 1; s >= 0; --s) {
-    const int half = M >> (s + 1);
-    for (int j = threadIdx.x; j < M / 2; j += blockDim.x) {
-      const int g = j / half, pos = j - g * half;
-      const int i0 = g * 2 * half + pos, i1 = i0 + half;
-      const cf a = z[i0], b = cmulc(z[i1], tw[(pos << s) * 2]);
-      z[i0] = cadd(a, b);
-      z[i1] = csub(a, b);
-    }
-    __syncthreads();
-  }
-}
 
 template <int LOGM>
 __global__ __launch_bounds__(1024) void fftconv_kernel(const float* __restrict__ mono, const float* __restrict__ rirs, const cf* __restrict__ tw,
@@ -90,28 +47,20 @@ __global__ __launch_bounds__(1024) void fftconv_kernel(const float* __restrict__
       if (k == 0) {
         const cf zh = z[0], zxx = zx[0];
         const float y0 = (zxx.x + zxx.y) * (zh.x + zh.y), ym = (zxx.x - zxx.y) * (zh.x - zh.y);   // X[0] H[0], X[M] H[M] (all real)
-        z[0] = {0.5f * (y0 + ym), 0.5f * (y0 - ym)};
+        z[0] = rfft_repack_dc(y0, ym);
         continue;
       }
       const int ik = br(k), im = br(M - k);
       const cf t = tw[k];
       const cf zhk = z[ik], zhm = z[im], zxk = zx[ik], zxm = zx[im];
-      // E = (Zk + conj Zm)/2, T O = T * (-i/2)(Zk - conj Zm);  S[k] = E + T O, S[M-k] = conj(E - T O)
-      auto unpack = [&](cf zk, cf zm, cf& e, cf& to) {
-        e = {0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)};
-        const cf d = {0.5f * (zk.x - zm.x), 0.5f * (zk.y + zm.y)};   // (Zk - conj Zm)/2
-        to = cmul(t, cf{d.y, -d.x});                                   // * (-i)
-      };
-      cf ex, ox, eh, oh;
-      unpack(zxk, zxm, ex, ox);
-      unpack(zhk, zhm, eh, oh);
+      cf ex, ox, eh, oh, zk, zm;
+      rfft_unpack(t, zxk, zxm, ex, ox);
+      rfft_unpack(t, zhk, zhm, eh, oh);
       const cf yk = cmul(cadd(ex, ox), cadd(eh, oh));                  // Y[k]
       const cf ymc = cmul(csub(ex, ox), csub(eh, oh));                 // conj(Y[M-k])
-      const cf e2 = {0.5f * (yk.x + ymc.x), 0.5f * (yk.y + ymc.y)};    // E' = (Y[k] + conj Y[M-k]) / 2
-      const cf w2 = {0.5f * (yk.x - ymc.x), 0.5f * (yk.y - ymc.y)};
-      const cf o2 = cmulc(w2, t);                                      // O' = conj(T) (Y[k] - conj Y[M-k]) / 2
-      z[ik] = {e2.x - o2.y, e2.y + o2.x};                              // Z'[k] = E' + i O'
-      if (im != ik) z[im] = {e2.x + o2.y, -e2.y + o2.x};               // Z'[M-k] = conj(E') + i conj(O')
+      rfft_repack(t, yk, ymc, zk, zm);
+      z[ik] = zk;
+      if (im != ik) z[im] = zm;
     }
     __syncthreads();
     ifft_dit<LOGM>(z, tw);

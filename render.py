@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""Render a binaural mixture of any length from mono sources and binaural room impulse responses:
+
+    python render.py --source a.wav --rir a_rir.wav [--source b.wav --rir b_rir.wav ...] [--gain g ...] --out mix.wav
+                     [--out-target target.wav] [--tail]
+
+Every ``--source`` is a mono WAV and has its own ``--rir``, a two-channel WAV (left and right ear); all files are 16 kHz, int16 or
+float32; any other sample rate is an error.  Shorter sources are zero-padded to the longest (and shorter RIRs to the longest RIR, which
+changes nothing).  ``--gain``: one per source, in order; without any, every source has gain 1 / (number of sources), the mean of the
+binaural images.  ``--out`` gets the mixture, a two-channel WAV of the sources' length, or of that length plus the longest RIR less
+one sample with ``--tail``.  ``--out-target`` gets the first source's binaural image at the gain it has in the mixture: the ground
+truth for separate.py.  Both are written in the first source's sample format (int16: round half to even, saturate).
+The scene is static, one RIR per source; one RIR per second (a moving listener) is m2h.audio.render.Auralizer's `rirs [R, S, K, Lr, 2]`.
+Definition: m2h/audio/render.py.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "move2hear-active-av-separation_amd"))
+
+from separate import SAMPLE_RATE, to_wav_samples  # noqa: E402  (the WAV conventions of separate.py)
+
+
+def read_wav(path, channels):
+    """-> (float32 [L] for a mono file, [L, 2] for a binaural one, in [-1, 1); the file's numpy dtype)"""
+    import numpy as np
+    from scipy.io import wavfile
+    rate, data = wavfile.read(path)
+    if rate != SAMPLE_RATE:
+        raise SystemExit("render.py: %s is sampled at %d Hz; %d Hz is required" % (path, rate, SAMPLE_RATE))
+    shape_ok = (data.ndim == 1 or (data.ndim == 2 and data.shape[1] == 1)) if channels == 1 else (data.ndim == 2 and data.shape[1] == 2)
+    if not shape_ok or data.shape[0] < 1:
+        raise SystemExit("render.py: %s must be a %s, got an array of shape %s" % (path, "mono recording" if channels == 1 else "two-channel (binaural) RIR", data.shape))
+    if data.dtype == np.int16:
+        wave = data.astype(np.float32) * np.float32(1.0 / 32768.0)
+    elif data.dtype == np.float32:
+        wave = data
+    else:
+        raise SystemExit("render.py: %s holds %s samples; int16 or float32 is required" % (path, data.dtype))
+    return (wave.reshape(-1) if channels == 1 else wave), data.dtype
+
+
+def main():
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument("--source", action="append", required=True, help="mono WAV, 16 kHz, int16 or float32 (repeat per source)")
+    parser.add_argument("--rir", action="append", required=True, help="two-channel WAV, 16 kHz: the source's binaural RIR (repeat per source)")
+    parser.add_argument("--gain", action="append", type=float, default=None, help="the source's gain in the mixture (repeat per source; default 1 / sources)")
+    parser.add_argument("--out", required=True, help="the binaural mixture")
+    parser.add_argument("--out-target", default=None, help="the first source's binaural image at its gain in the mixture")
+    parser.add_argument("--tail", action="store_true", help="keep the reverberation after the last source sample")
+    args = parser.parse_args()
+    S = len(args.source)
+    if len(args.rir) != S:
+        parser.error("%d --source and %d --rir: every source needs its own RIR" % (S, len(args.rir)))
+    if args.gain is not None and len(args.gain) != S:
+        parser.error("%d --gain for %d sources: give one per source or none" % (len(args.gain), S))
+    import numpy as np
+    sources = [read_wav(p, 1) for p in args.source]
+    rirs = [read_wav(p, 2)[0] for p in args.rir]
+    dtype = sources[0][1]
+    L, Lr = max(x.shape[0] for x, _ in sources), max(h.shape[0] for h in rirs)
+    x = np.zeros((1, S, L), np.float32)
+    h = np.zeros((1, S, Lr, 2), np.float32)
+    for s in range(S):
+        x[0, s, :sources[s][0].shape[0]] = sources[s][0]
+        h[0, s, :rirs[s].shape[0]] = rirs[s]
+    gains = np.asarray(args.gain if args.gain is not None else [1.0 / S] * S, np.float32).reshape(1, S)
+
+    import torch
+    from scipy.io import wavfile
+    from m2h.audio.render import Auralizer
+    dev = torch.device("cuda", 0)
+    try:
+        mix, images = Auralizer(dev).render(torch.from_numpy(x).to(dev), torch.from_numpy(h).to(dev), gains=torch.from_numpy(gains).to(dev),
+                                            tail=args.tail, return_images=True)
+    except ValueError as e:
+        raise SystemExit("render.py: %s" % e)
+    outs = [(args.out, mix[0])]
+    if args.out_target is not None:
+        outs.append((args.out_target, images[0, 0] * float(gains[0, 0])))
+    for path, y in outs:
+        y = y.cpu().numpy()                                                  # [2, L_out]
+        wavfile.write(path, SAMPLE_RATE, to_wav_samples(y.T, dtype))         # two channels: [L_out, 2] in the file
+        print("render.py: wrote %s (%d samples at %d Hz, %.2f s, %d source%s, RIR of %d taps%s, two channels)" % (
+            path, y.shape[-1], SAMPLE_RATE, y.shape[-1] / SAMPLE_RATE, S, "" if S == 1 else "s", Lr, ", with tail" if args.tail else ""))
+
+
+if __name__ == "__main__":
+    main()
