@@ -742,6 +742,22 @@ int m2h_rms_normalize(float* mag, int S, int n, float norm, m2h_stream stream);
  * improvement over using the mixture as the estimate). */
 int m2h_bss_metrics(const float* ref, const float* est, const float* mix_l, const float* mix_r, float* out, int S, int L, m2h_stream stream);
 
+/* Scorer (m2h/audio/score.py holds the definition; csrc/score.hip): the fp64 sums and Gram matrix of the N = S + 3 signals of every
+ * (recording r, channel c, tile j) in one pass -- s_0 .. s_{S-1} = refs[r][s][c], est[r][c], mix[r][0], mix[r][1], each a row of L fp32
+ * samples with unit stride; refs_sr / _ss / _sc, est_sr / _sc, mix_sr / _sc are the other strides IN ELEMENTS (any value; refs_sc and
+ * est_sc are not read when C = 1).  Tile j is samples [j * tile, min((j + 1) * tile, L)), J = ceil(L / tile).
+ *   out [R][C][J][N + N(N+1)/2] fp64:  [0 .. N) = sum_t a_i[t];  [N ..) = sum_t a_i[t] * a_k[t], i <= k, row-major.
+ * Products are exact (float -> double before the multiply); the summation order is fixed and does not depend on the batch, on the
+ * strides or on the alignment of a row.  Returns a negative status and launches nothing for a null pointer, S outside 1 .. 6,
+ * C outside {1, 2}, L < 1, tile < 1, R < 1, or more than 2^31 - 1 (r, c, j) triples. */
+int m2h_score_gram(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                   const float* mix, long long mix_sr, long long mix_sc, double* out, int R, int S, int C, long long L, int tile, m2h_stream stream);
+
+/* out [RC][M][K] = the sum of tiles [RC][J][K] over the tiles j = m * hop .. min(m * hop + window, J) - 1 of window m, added in tile
+ * order (0 for a window that holds no tile).  window = J, M = 1 is the whole recording. */
+int m2h_score_windows(const double* tiles, double* out, long long RC, long long J, int K, long long M, long long window, long long hop,
+                      m2h_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-network runner: one C call enqueues every kernel of one separator U-Net forward (K1/K2 slice, 5 down stages, 5 up
  * stages, head) = PassiveSepEncCNN.forward + PassiveSepDecCNN.forward (separator_cnn.py:70-108,153-170) in eval mode.  Same

@@ -1,0 +1,338 @@
+"""Scorer: the quality of a separated recording of any length against its ground truth, on the GPU (csrc/score.hip).
+
+Definition.  Inputs, fp32 on the GPU; the last stride is 1 and every other stride is arbitrary (views are read in place; a non-unit
+last stride is an error, not a hidden copy):
+
+  references [R, S, L] or [R, S, C, L], 1 <= S <= 6, C in {1, 2}: the target and the interferers as they are in the mixture, e.g. the
+             `images` of Auralizer.render(..., return_images=True) times their gains;
+  estimate   [R, L] or [R, C, L]: the separated target (C as in `references`; [R, L] means C = 1);
+  mixture    [R, 2, L]: what the separator was given;
+  target     an int, or R ints, in [0, S): which reference the estimate is an estimate of;
+  L >= 1.
+
+Tiles and windows.  A tile is `tile` samples (default 16000: one second, the Separator's segment); J = ceil(L / tile), the last tile may
+be short.  Windows are counted in tiles: `window` = w >= 1 tiles long, a window every `hop` = h >= 1 tiles.  There are M = 1 windows if
+J <= w, else M = ceil((J - w) / h) + 1; window m covers the tiles [m h, min(m h + w, J)).  (With h > w the windows leave tiles out, and
+the last one may then start at or past J: it is empty, n = 0.)  score_plan() returns all this in pure Python.
+
+Every window, and the whole recording, is scored as the reference scores one clip (common/eval_metrics.py: preprocess :172-199, then
+scale_bss_eval :60-122 with all S references).  n is the window's sample count; every signal has ITS OWN MEAN OVER THAT WINDOW removed.
+For channel c the signals are the S references' channel c, the estimate's channel c, and the baseline: for C = 1 the mean of the two
+mean-removed mixture channels (preprocess(is_mono=True)), for C = 2 the mixture's channel c (scale_bss_eval's docstring: each channel
+independently).  The eleven numbers, in eval_metrics.METRIC_ORDER, are scale_bss_eval_helper's (:12-57) with its two EPS terms: with s the
+target, x the estimate, P the references' Gram matrix,
+
+  alpha = <s, x> / <s, s>         snr = 10 log10(<s, s> / |x - s|^2)          si_sdr = 10 log10(|alpha s|^2 / |x - alpha s|^2)
+  srr = -10 log10((1 - 1 / alpha)^2)                                          sd_sdr = snr + 10 log10(alpha^2)
+  b = solve(P, refs^T (x - alpha s)) + EPS       e_interf = refs b            e_artif = x - alpha s - e_interf + EPS
+  si_sir = 10 log10(|alpha s|^2 / |e_interf|^2)                               si_sar = 10 log10(|alpha s|^2 / |e_artif|^2)
+
+then si_sdri, sd_sdri, snri, si_siri, si_sari: the estimate's number minus the baseline's.  No time alignment is made.
+
+Degenerate cases.  A source whose centred energy in the window is 0 (digital silence, or not positive after rounding) is left out of the
+projection: its coefficient is 0.  If the target's energy is 0 or n < 2, all eleven numbers are NaN.  If the reduced normal equations
+cannot be solved (info != 0 of torch.linalg.solve_ex, a pivot that is exactly 0: duplicate references; solve_pivoted), the SIR / SAR numbers and their improvements are NaN.
+Quadratic forms that are non-negative in exact arithmetic are clamped at 0, so a perfect estimate scores +inf, not NaN.  Otherwise
+IEEE rules apply, as in numpy with warnings off.
+
+Method.  All of the above follows from the sums and the Gram matrix of the N = S + 3 signals s_0 .. s_{S-1}, est_c, mix_l, mix_r of a
+window: <a - mean a, b - mean b> = sum a b - (sum a)(sum b) / n, the baseline is a linear combination of mix_l and mix_r, and norms of
+residuals are quadratic forms.  m2h_score_gram reads every signal once and writes those sums per (recording, channel, tile) in fp64 with
+exact products (an fp32 Gram loses the noise norm, a difference of Gram entries, exactly where a good separator scores: DESIGN.md §8.6);
+m2h_score_windows adds a window's tiles in tile order -- never a difference of prefix sums, so a window's score does not depend on what
+precedes it -- and metrics_from_gram does the algebra in torch float64, batched over recordings, channels and windows.
+"""
+import operator
+
+import torch
+
+from .. import ops
+from ..common.eval_metrics import EPS, METRIC_ORDER
+
+DEFAULT_TILE = 16000
+MAX_SOURCES = 6
+_NAN = float("nan")
+
+
+def score_plan(L, tile=DEFAULT_TILE, window=1, hop=1):
+    """Pure Python: the tiles and windows of one score.
+
+    -> {"L", "tile", "window", "hop", "J", "M", "tiles": [(j0, j1)] per window, "samples": [(t0, t1)] per window}; window m holds the tiles
+    j0 <= j < j1 and the samples t0 <= t < t1 (n = t1 - t0; an empty window has j0 == j1 and t0 == t1)."""
+    vals = []
+    for name, v in (("L", L), ("tile", tile), ("window", window), ("hop", hop)):
+        try:
+            vals.append(operator.index(v))
+        except TypeError:
+            raise TypeError("m2h.Scorer: %s must be an int, got %r" % (name, v))
+        if isinstance(v, bool) or vals[-1] < 1:
+            raise ValueError("m2h.Scorer: %s must be at least 1, got %r" % (name, v))
+    L, tile, window, hop = vals
+    J = -(-L // tile)
+    M = 1 if J <= window else -(-(J - window) // hop) + 1
+    tiles = [(min(m * hop, J), min(m * hop + window, J)) for m in range(M)]
+    return {"L": L, "tile": tile, "window": window, "hop": hop, "J": J, "M": M, "tiles": tiles,
+            "samples": [(min(j0 * tile, L), min(j1 * tile, L)) for j0, j1 in tiles]}
+
+
+def gram_signals(K):
+    """N of a Gram row of K = N + N(N+1)/2 numbers (4 <= N <= 9)."""
+    for N in range(4, MAX_SOURCES + 4):
+        if N + N * (N + 1) // 2 == K:
+            return N
+    raise ValueError("m2h.Scorer: a Gram row holds N + N(N+1)/2 numbers for N = S + 3 in 4 .. 9, not %d" % K)
+
+
+def _count(n, device):
+    """n as a float64 tensor on `device` (a number becomes a fill: no copy from the host)"""
+    if isinstance(n, torch.Tensor):
+        return n.to(device=device, dtype=torch.float64)
+    return torch.full((), float(n), dtype=torch.float64, device=device)
+
+
+def _dot(a, b):
+    """sum_k a[..., k] b[..., k], k in order: element-wise operations only, so a row's result does not depend on the batch around it"""
+    acc = a[..., 0] * b[..., 0]
+    for k in range(1, a.shape[-1]):
+        acc = acc + a[..., k] * b[..., k]
+    return acc
+
+
+def solve_pivoted(A, Y):
+    """A [..., S, S], Y [..., S, Q] -> (X [..., S, Q] with A X = Y, singular [...] bool).
+
+    Gaussian elimination with partial pivoting, the LU arithmetic of torch.linalg.solve_ex, written in element-wise torch operations:
+    every matrix is reduced by the same operations in the same order whatever the batch holds, which a library's batched solver does
+    not promise (it may pick another algorithm at another batch size), and the Scorer's numbers are bit for bit those of the
+    recording or the window scored alone.  `singular` is solve_ex's info != 0: a pivot that is exactly 0; X is then meaningless."""
+    S = A.shape[-1]
+    M = torch.cat([A, Y], dim=-1)
+    rows = [M[..., i, :] for i in range(S)]
+    singular = torch.zeros(A.shape[:-2], dtype=torch.bool, device=A.device)
+    for k in range(S):
+        for i in range(k + 1, S):                                                      # the first row of largest |entry| becomes the pivot row
+            swap = (rows[i][..., k].abs() > rows[k][..., k].abs())[..., None]
+            rows[k], rows[i] = torch.where(swap, rows[i], rows[k]), torch.where(swap, rows[k], rows[i])
+        zero = rows[k][..., k] == 0
+        singular = singular | zero
+        pivot = torch.where(zero, torch.ones_like(rows[k][..., k]), rows[k][..., k])
+        for i in range(k + 1, S):
+            rows[i] = rows[i] - (rows[i][..., k] / pivot)[..., None] * rows[k]
+        rows[k] = rows[k] / pivot[..., None]
+    for k in reversed(range(S)):
+        for i in range(k):
+            rows[i] = rows[i] - rows[i][..., k:k + 1] * rows[k]
+    return torch.stack([row[..., S:] for row in rows], dim=-2), singular
+
+
+def metrics_from_gram(gram, n, target, C):
+    """The eleven metrics from sums and Gram matrices (module docstring), in torch float64 on gram's device.
+
+    gram   [R, C, ..., K] float64 in m2h_score_gram's layout (K = N + N(N+1)/2; signals s_0 .. s_{S-1}, est_c, mix_l, mix_r);
+    n      the sample count: a number, or a tensor that broadcasts against gram.shape[:-1];
+    target an int, or an integer tensor [R] on gram's device;
+    C      1 (the baseline is the mean of the mixture's mean-removed channels) or 2 (axis 1 is the ear; the baseline is that ear's mixture).
+    -> [R, C, ..., 11] float64 in eval_metrics.METRIC_ORDER."""
+    if not isinstance(gram, torch.Tensor) or gram.dtype != torch.float64:
+        raise TypeError("m2h.Scorer: gram must be a float64 torch tensor, got %s" % (gram.dtype if isinstance(gram, torch.Tensor) else type(gram).__name__))
+    if C not in (1, 2) or gram.dim() < 3 or gram.shape[1] != C:
+        raise ValueError("m2h.Scorer: gram must be [R, C, ..., K] with C = %r in {1, 2}, got a tensor of shape %s" % (C, tuple(gram.shape)))
+    N = gram_signals(gram.shape[-1])
+    S = N - 3
+    dev, batch = gram.device, gram.shape[:-1]
+    R = batch[0]
+    sums = gram[..., :N]
+    iu = torch.triu_indices(N, N, device=dev)
+    G = gram.new_zeros(batch + (N, N))
+    G[..., iu[0], iu[1]] = gram[..., N:]
+    G[..., iu[1], iu[0]] = gram[..., N:]
+    n = _count(n, dev).expand(batch)
+    Gc = G - sums[..., :, None] * sums[..., None, :] / n[..., None, None]              # <a_i - mean, a_k - mean>
+
+    if isinstance(target, torch.Tensor):
+        if target.dtype not in (torch.int32, torch.int64) or tuple(target.shape) != (R,) or target.device != dev:
+            raise TypeError("m2h.Scorer: a tensor `target` must be [R] = [%d] int32 or int64 on %s" % (R, dev))
+        t = target.to(torch.int64).view((R,) + (1,) * (len(batch) - 1))
+        row_t = torch.take_along_dim(Gc, t[..., None, None].expand(batch + (1, N)), dim=-2).squeeze(-2)
+        pick = lambda v: torch.take_along_dim(v, t[..., None].expand(batch + (1,)), dim=-1).squeeze(-1)   # noqa: E731
+    else:
+        t = int(target)
+        if not 0 <= t < S:
+            raise ValueError("m2h.Scorer: target = %d is not one of the %d references" % (t, S))
+        row_t = Gc[..., t, :]
+        pick = lambda v: v[..., t]                                                                      # noqa: E731
+    ss = pick(row_t)                                                                   # <s, s>
+    P = Gc[..., :S, :S]
+    keep = torch.diagonal(P, dim1=-2, dim2=-1) > 0                                      # sources with energy in this window
+    keep2 = keep[..., :, None] & keep[..., None, :]
+    Pk = torch.where(keep2, P, torch.zeros_like(P))
+    A = Pk + torch.diag_embed((~keep).to(torch.float64))                                # the reduced normal equations, padded by ones
+    valid = (ss > 0) & (n >= 2)
+    A = torch.where(valid[..., None, None], A, torch.eye(S, dtype=torch.float64, device=dev).expand_as(A))
+
+    def first(gx, xx):
+        """scale_bss_eval_helper (:16-40) for a signal x given <x, a_i> (gx [..., N]) and <x, x>, all centred; and refs^T (x - alpha s)"""
+        sx = pick(gx)
+        alpha = sx / ss
+        noise = torch.clamp(xx - 2.0 * sx + ss, min=0.0)                                # |x - s|^2
+        snr = 10.0 * torch.log10(ss / noise)
+        signal = alpha * alpha * ss                                                     # |alpha s|^2
+        res = torch.clamp(xx - alpha * sx, min=0.0)                                     # |x - alpha s|^2
+        si_sdr = 10.0 * torch.log10(signal / res)
+        srr = -10.0 * torch.log10((1.0 - 1.0 / alpha) ** 2)
+        sd_sdr = snr + 10.0 * torch.log10(alpha ** 2)
+        rhs = torch.where(keep & valid[..., None], gx[..., :S] - alpha[..., None] * row_t[..., :S], torch.zeros_like(Pk[..., 0]))
+        return (si_sdr, sd_sdr, snr, srr), signal, res, rhs
+
+    def second(signal, res, rhs, b0):
+        """:45-55: the projection's two norms as quadratic forms"""
+        b = torch.where(keep, b0 + EPS, torch.zeros_like(rhs))
+        Pb = Pk[..., :, 0] * b[..., 0:1]
+        for k in range(1, S):
+            Pb = Pb + Pk[..., :, k] * b[..., k:k + 1]
+        bPb = _dot(b, Pb)
+        interf = torch.clamp(bPb, min=0.0)                                              # |refs b|^2
+        artif = torch.clamp(res - 2.0 * _dot(b, rhs) + bPb, min=0.0) + n * (EPS * EPS)  # |x - alpha s - refs b + EPS|^2
+        nan = torch.full_like(ss, _NAN)
+        return torch.where(singular, nan, 10.0 * torch.log10(signal / interf)), torch.where(singular, nan, 10.0 * torch.log10(signal / artif))
+
+    e, l, r = S, S + 1, S + 2
+    parts = [first(Gc[..., e, :], Gc[..., e, e])]
+    if C == 1:
+        parts.append(first(0.5 * (Gc[..., l, :] + Gc[..., r, :]), 0.25 * (Gc[..., l, l] + 2.0 * Gc[..., l, r] + Gc[..., r, r])))
+    else:
+        parts.append(first(torch.stack([Gc[:, 0, ..., l, :], Gc[:, 1, ..., r, :]], dim=1), torch.stack([Gc[:, 0, ..., l, l], Gc[:, 1, ..., r, r]], dim=1)))
+    x, singular = solve_pivoted(A, torch.stack([parts[0][3], parts[1][3]], dim=-1))     # one elimination, both right-hand sides
+    both = []
+    for q, ((si_sdr, sd_sdr, snr, srr), signal, res, rhs) in enumerate(parts):
+        si_sir, si_sar = second(signal, res, rhs, x[..., q])
+        both.append((si_sdr, si_sir, si_sar, sd_sdr, snr, srr))
+    est, base = both
+    out = torch.stack(list(est) + [est[0] - base[0], est[3] - base[3], est[4] - base[4], est[1] - base[1], est[2] - base[2]], dim=-1)
+    return torch.where(valid[..., None], out, torch.full_like(out, _NAN))
+
+
+def target_energy(gram, n, target):
+    """The target's centred energy per Gram row (> 0: the window is `active`)."""
+    N = gram_signals(gram.shape[-1])
+    batch = gram.shape[:-1]
+    n = _count(n, gram.device).expand(batch)
+    energy = []
+    for s in range(N - 3):                                                              # the diagonal entry of source s: N + idx(s, s)
+        energy.append(gram[..., N + s * N - s * (s - 1) // 2] - gram[..., s] * gram[..., s] / n)
+    energy = torch.stack(energy, dim=-1)
+    if isinstance(target, torch.Tensor):
+        t = target.to(torch.int64).view((batch[0],) + (1,) * len(batch[1:]))
+        return torch.take_along_dim(energy, t[..., None].expand(batch + (1,)), dim=-1).squeeze(-1)
+    return energy[..., int(target)]
+
+
+class Scorer:
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._timing = None          # tools/score_bench.py: a list that receives (stage, event) marks
+
+    def _mark(self, stage):
+        if self._timing is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record(torch.cuda.current_stream(self.device))
+            self._timing.append((stage, ev))
+
+    def _check(self, estimate, references, mixture, target, tile, window, hop):
+        for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("m2h.Scorer: %s must be a torch tensor, got %s" % (name, type(t).__name__))
+            if t.dtype != torch.float32:
+                raise TypeError("m2h.Scorer: %s must be float32, got %s" % (name, t.dtype))
+        if references.dim() not in (3, 4):
+            raise ValueError("m2h.Scorer: references must be [R, S, L] or [R, S, C, L], got a tensor of shape %s" % (tuple(references.shape),))
+        if estimate.dim() not in (2, 3):
+            raise ValueError("m2h.Scorer: estimate must be [R, L] or [R, C, L], got a tensor of shape %s" % (tuple(estimate.shape),))
+        if mixture.dim() != 3 or mixture.shape[1] != 2:
+            raise ValueError("m2h.Scorer: mixture must be [R, 2, L], got a tensor of shape %s" % (tuple(mixture.shape),))
+        refs = references if references.dim() == 4 else references.unsqueeze(2)
+        est = estimate if estimate.dim() == 3 else estimate.unsqueeze(1)
+        R, S, C, L = refs.shape
+        if C not in (1, 2):
+            raise ValueError("m2h.Scorer: references have C = %d channels; 1 or 2 are supported" % C)
+        if est.shape[1] != C:
+            raise ValueError("m2h.Scorer: references have C = %d channels and the estimate has %d" % (C, est.shape[1]))
+        if not 1 <= S <= MAX_SOURCES:
+            raise ValueError("m2h.Scorer: S = %d reference sources; 1 .. %d are supported" % (S, MAX_SOURCES))
+        if R < 1 or est.shape[0] != R or mixture.shape[0] != R:
+            raise ValueError("m2h.Scorer: references, estimate and mixture hold R = %d, %d and %d recordings; one R >= 1 is required"
+                             % (R, est.shape[0], mixture.shape[0]))
+        if L < 1 or est.shape[2] != L or mixture.shape[2] != L:
+            raise ValueError("m2h.Scorer: references, estimate and mixture are L = %d, %d and %d samples long; one L >= 1 is required"
+                             % (L, est.shape[2], mixture.shape[2]))
+        for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
+            if L > 1 and t.stride(-1) != 1:
+                raise ValueError("m2h.Scorer: the last stride of %s is %d; 1 is required (the scorer makes no hidden copy)" % (name, t.stride(-1)))
+        if isinstance(target, torch.Tensor):
+            if target.is_cuda:
+                raise TypeError("m2h.Scorer: target must be host integers (its range is checked before any launch), got a tensor on %s" % (target.device,))
+            target = target.tolist()
+        given = target
+        try:
+            target = operator.index(given) if not isinstance(given, bool) else None
+        except TypeError:
+            try:
+                target = [operator.index(t) for t in given]
+            except TypeError:
+                target = None
+        if target is None:
+            raise TypeError("m2h.Scorer: target must be an int or R ints, got %r" % (given,))
+        if not isinstance(target, int) and len(target) != R:
+            raise ValueError("m2h.Scorer: target must be an int or R = %d ints, got %d of them" % (R, len(target)))
+        for t in ([target] if isinstance(target, int) else target):
+            if not 0 <= t < S:
+                raise ValueError("m2h.Scorer: target %d is not one of the S = %d references (0 .. %d)" % (t, S, S - 1))
+        if not isinstance(target, int) and len(set(target)) == 1:
+            target = target[0]
+        plan = score_plan(L, tile, window, hop)                                         # raises on tile, window, hop
+        for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
+            if not t.is_cuda or t.device != self.device:
+                raise ValueError("m2h.Scorer: %s must live on %s, got %s; the scorer has no CPU path" % (name, self.device, t.device))
+        return refs, est, target, plan
+
+    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1):
+        """-> {"whole": [R, C, 11], "track": [R, C, M, 11], "active": [R, C, M] bool, "plan": score_plan(...)}; float64 on the device, in
+        eval_metrics.METRIC_ORDER; no host synchronisation.  The module docstring holds the definition."""
+        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop)
+        R, S, C, L = refs.shape
+        J, M, tile, window, hop = (plan[k] for k in ("J", "M", "tile", "window", "hop"))
+        dev = self.device
+        with torch.cuda.device(dev):
+            if not isinstance(target, int):                                            # R small fills: no copy from the host
+                tt = torch.empty((R,), dtype=torch.int64, device=dev)
+                for r, t in enumerate(target):
+                    tt[r].fill_(t)
+                target = tt
+            self._mark("start")
+            tiles = ops.score_gram(refs, est, mixture, tile)                            # [R, C, J, K]
+            self._mark("score_gram")
+            gram = torch.cat([ops.score_windows(tiles, 1, J, 1), ops.score_windows(tiles, M, window, hop)], dim=2)      # whole, then the track
+            m = torch.arange(M, device=dev, dtype=torch.int64) * hop
+            n = (torch.clamp((m + window) * tile, max=L) - torch.clamp(m * tile, max=L)).to(torch.float64)
+            n = torch.cat([torch.full((1,), float(L), dtype=torch.float64, device=dev), n])
+            scores = metrics_from_gram(gram, n, target, C)
+            active = target_energy(gram[:, :, 1:], n[1:], target) > 0
+            self._mark("metrics")
+        return {"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan}
+
+
+def summarize(result):
+    """Host-side summary of Scorer.score's result for one call: {"metrics", "whole": [R][C][11], "track_mean", "track_median": over the
+    active windows ([R][C][11], NaN without any), "active_windows": [R][C]} as Python lists (one synchronisation)."""
+    import numpy as np
+    whole, track, active = (result[k].cpu().numpy() for k in ("whole", "track", "active"))
+    R, C = whole.shape[:2]
+    mean, median = np.full((R, C, 11), np.nan), np.full((R, C, 11), np.nan)
+    with np.errstate(all="ignore"):
+        for r in range(R):
+            for c in range(C):
+                rows = track[r, c][active[r, c]]
+                if rows.shape[0]:
+                    mean[r, c], median[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
+    return {"metrics": list(METRIC_ORDER), "whole": whole.tolist(), "track_mean": mean.tolist(), "track_median": median.tolist(),
+            "active_windows": active.sum(axis=-1).tolist()}

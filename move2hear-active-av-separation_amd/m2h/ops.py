@@ -731,6 +731,42 @@ def bss_metrics(ref, est, mix_l, mix_r=None):
     return out
 
 
+def score_gram(refs, est, mix, tile):
+    """Tile Grams of the Scorer (m2h/audio/score.py): refs [R, S, C, L], est [R, C, L], mix [R, 2, L] fp32 with unit last stride and
+    any other strides (views are read in place) -> [R, C, J, N + N(N+1)/2] fp64, J = ceil(L / tile), N = S + 3 (include/m2h.h)."""
+    for t in (refs, est, mix):
+        if not t.is_cuda or t.dtype != torch.float32 or t.device != refs.device:
+            raise RuntimeError("m2h.score_gram: float32 tensors on one GPU are required (got %s on %s); the m2h ops have no CPU path" % (t.dtype, t.device))
+    if refs.dim() != 4 or est.dim() != 3 or mix.dim() != 3:
+        raise RuntimeError("m2h.score_gram: refs [R, S, C, L], est [R, C, L] and mix [R, 2, L] are required")
+    R, S, C, L = refs.shape
+    if tuple(est.shape) != (R, C, L) or tuple(mix.shape) != (R, 2, L) or L < 1 or R < 1:
+        raise RuntimeError("m2h.score_gram: refs %s, est %s and mix %s do not agree" % (tuple(refs.shape), tuple(est.shape), tuple(mix.shape)))
+    if L > 1 and any(t.stride(-1) != 1 for t in (refs, est, mix)):
+        raise RuntimeError("m2h.score_gram: the last stride must be 1")
+    tile = int(tile)
+    if tile < 1 or not 1 <= S <= 6 or C not in (1, 2):
+        raise RuntimeError("m2h.score_gram: tile = %d >= 1, S = %d in 1 .. 6 and C = %d in {1, 2} are required" % (tile, S, C))
+    N = S + 3
+    out = torch.empty((R, C, -(-L // tile), N + N * (N + 1) // 2), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_score_gram(_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1),
+                                      _ptr(mix), mix.stride(0), mix.stride(1), _ptr(out), R, S, C, L, tile, _stream(refs)), "m2h_score_gram")
+    return out
+
+
+def score_windows(tiles, M, window, hop):
+    """tiles [R, C, J, K] fp64 -> [R, C, M, K]: every window's tiles added in tile order (window m: tiles m * hop .. m * hop + window - 1)."""
+    _chk(tiles, "score_windows", torch.float64)
+    R, C, J, K = tiles.shape
+    out = torch.empty((R, C, int(M), K), device=tiles.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(tiles.device):
+        _lib.check(lib.m2h_score_windows(_ptr(tiles), _ptr(out), R * C, J, K, int(M), int(window), int(hop), _stream(tiles)), "m2h_score_windows")
+    return out
+
+
 def gather_envs(src, perm):
     """src [T,N,...] , perm [Nsel] int64 (device) -> [T*Nsel, ...]  (recurrent_generator stack + flatten)."""
     if not src.is_cuda or not src.is_contiguous():

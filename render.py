@@ -2,14 +2,16 @@
 """Render a binaural mixture of any length from mono sources and binaural room impulse responses:
 
     python render.py --source a.wav --rir a_rir.wav [--source b.wav --rir b_rir.wav ...] [--gain g ...] --out mix.wav
-                     [--out-target target.wav] [--tail]
+                     [--out-target target.wav] [--out-image image.wav ...] [--tail]
 
 Every ``--source`` is a mono WAV and has its own ``--rir``, a two-channel WAV (left and right ear); all files are 16 kHz, int16 or
 float32; any other sample rate is an error.  Shorter sources are zero-padded to the longest (and shorter RIRs to the longest RIR, which
 changes nothing).  ``--gain``: one per source, in order; without any, every source has gain 1 / (number of sources), the mean of the
 binaural images.  ``--out`` gets the mixture, a two-channel WAV of the sources' length, or of that length plus the longest RIR less
 one sample with ``--tail``.  ``--out-target`` gets the first source's binaural image at the gain it has in the mixture: the ground
-truth for separate.py.  Both are written in the first source's sample format (int16: round half to even, saturate).
+truth for separate.py.  ``--out-image``: repeatable, one per source in order (at most as many as sources); each gets that source's
+binaural image at the gain it has in the mixture, as ``--out-target`` does for the first: the target and the interferers for score.py.
+All are written in the first source's sample format (int16: round half to even, saturate).
 The scene is static, one RIR per source; one RIR per second (a moving listener) is m2h.audio.render.Auralizer's `rirs [R, S, K, Lr, 2]`.
 Definition: m2h/audio/render.py.
 """
@@ -48,6 +50,7 @@ def main():
     parser.add_argument("--gain", action="append", type=float, default=None, help="the source's gain in the mixture (repeat per source; default 1 / sources)")
     parser.add_argument("--out", required=True, help="the binaural mixture")
     parser.add_argument("--out-target", default=None, help="the first source's binaural image at its gain in the mixture")
+    parser.add_argument("--out-image", action="append", default=None, help="the k-th source's binaural image at its gain in the mixture (repeat, in source order)")
     parser.add_argument("--tail", action="store_true", help="keep the reverberation after the last source sample")
     args = parser.parse_args()
     S = len(args.source)
@@ -55,6 +58,8 @@ def main():
         parser.error("%d --source and %d --rir: every source needs its own RIR" % (S, len(args.rir)))
     if args.gain is not None and len(args.gain) != S:
         parser.error("%d --gain for %d sources: give one per source or none" % (len(args.gain), S))
+    if args.out_image is not None and len(args.out_image) > S:
+        parser.error("%d --out-image for %d sources: give at most one per source, in order" % (len(args.out_image), S))
     import numpy as np
     sources = [read_wav(p, 1) for p in args.source]
     rirs = [read_wav(p, 2)[0] for p in args.rir]
@@ -79,6 +84,8 @@ def main():
     outs = [(args.out, mix[0])]
     if args.out_target is not None:
         outs.append((args.out_target, images[0, 0] * float(gains[0, 0])))
+    for s, path in enumerate(args.out_image or ()):
+        outs.append((path, images[0, s] * float(gains[0, s])))
     for path, y in outs:
         y = y.cpu().numpy()                                                  # [2, L_out]
         wavfile.write(path, SAMPLE_RATE, to_wav_samples(y.T, dtype))         # two channels: [L_out, 2] in the file

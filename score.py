@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Score a separated recording of any length against its ground truth:
+
+    python score.py --estimate out.wav --mixture mix.wav --reference target.wav [--reference other.wav ...] [--window W --hop H]
+                    [--json scores.json]
+
+``--reference``: the sources as they are in the mixture, at most six; the FIRST one is the target the estimate is scored against, the
+others are the interferers (they enter SI-SIR and SI-SAR).  ``render.py --out-target / --out-image`` writes such files.  ``--mixture``:
+the two-channel recording the separator was given; the improvements (SI-SDRi, ...) are measured against it.  The estimate and every
+reference have the same channel count: mono files are scored against the mean of the mixture's channels (separate.py's default
+output), two-channel files ear by ear (``separate.py --output binaural``).  All files are 16 kHz, int16 or float32, and have the
+same length; anything else is an error.  NO TIME ALIGNMENT is made: a dry source scored against a reverberant estimate is the
+caller's business.
+
+The recording is scored as a whole and in windows of ``--window`` seconds, one every ``--hop`` seconds (defaults 1 and 1).  Printed:
+the whole-recording metrics, then the mean and the median of every metric over the active windows (those in which the target is not
+silent).  ``--json`` writes everything, the per-window track included.  Definition: m2h/audio/score.py.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "move2hear-active-av-separation_amd"))
+
+import render  # noqa: E402  (read_wav for mono files)
+import separate  # noqa: E402  (the WAV conventions: SAMPLE_RATE, read_wav for two-channel files)
+
+
+def read_wav(path):
+    """-> float32 [C, L] in [-1, 1), C = 1 or 2, by the readers of separate.py (two channels) and render.py (mono)"""
+    from scipy.io import wavfile
+    rate, data = wavfile.read(path, mmap=True)
+    if rate != separate.SAMPLE_RATE:
+        raise SystemExit("score.py: %s is sampled at %d Hz; %d Hz is required" % (path, rate, separate.SAMPLE_RATE))
+    if data.ndim == 2 and data.shape[1] == 2:
+        return separate.read_wav(path)[0]
+    if data.ndim == 2 and data.shape[1] != 1:
+        raise SystemExit("score.py: %s has %d channels; 1 or 2 are supported" % (path, data.shape[1]))
+    return render.read_wav(path, 1)[0][None]
+
+
+def main():
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument("--estimate", required=True, help="the separated target: WAV, 16 kHz, int16 or float32, one or two channels")
+    parser.add_argument("--mixture", required=True, help="the two-channel recording that was separated")
+    parser.add_argument("--reference", action="append", required=True, help="a source as it is in the mixture (repeat; the first is the target)")
+    parser.add_argument("--window", type=int, default=1, help="window length in seconds")
+    parser.add_argument("--hop", type=int, default=1, help="a window every HOP seconds")
+    parser.add_argument("--json", default=None, help="write every number here")
+    args = parser.parse_args()
+    import numpy as np
+    est = read_wav(args.estimate)
+    mix = read_wav(args.mixture)
+    refs = [read_wav(p) for p in args.reference]
+    if mix.shape[0] != 2:
+        raise SystemExit("score.py: %s must be a two-channel (binaural) recording, got %d channel" % (args.mixture, mix.shape[0]))
+    for path, x in zip(args.reference, refs):
+        if x.shape[0] != est.shape[0]:
+            raise SystemExit("score.py: %s has %d channel%s and %s has %d; the estimate and every reference need the same count"
+                             % (args.estimate, est.shape[0], "" if est.shape[0] == 1 else "s", path, x.shape[0]))
+    for path, x in [(args.mixture, mix)] + list(zip(args.reference, refs)):
+        if x.shape[1] != est.shape[1]:
+            raise SystemExit("score.py: %s is %d samples long and %s is %d; equal lengths are required (no alignment is made)"
+                             % (args.estimate, est.shape[1], path, x.shape[1]))
+
+    import torch
+    from m2h.audio.score import Scorer, summarize
+    dev = torch.device("cuda", 0)
+    try:
+        res = Scorer(dev).score(torch.from_numpy(np.ascontiguousarray(est)).to(dev)[None], torch.from_numpy(np.stack(refs)).to(dev)[None],
+                                torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop)
+    except (ValueError, TypeError) as e:
+        raise SystemExit("score.py: %s" % e)
+    s = summarize(res)
+    C, L, plan = est.shape[0], est.shape[1], res["plan"]
+    names = ("mono",) if C == 1 else ("left", "right")
+    print("score.py: %s against %s (%d samples at %d Hz, %.2f s, %d reference%s, %d window%s of %d s every %d s)" % (
+        args.estimate, args.reference[0], L, separate.SAMPLE_RATE, L / separate.SAMPLE_RATE, len(refs), "" if len(refs) == 1 else "s",
+        plan["M"], "" if plan["M"] == 1 else "s", args.window, args.hop))
+    print("%-8s %-14s" % ("channel", "") + " ".join("%13s" % m for m in s["metrics"]))
+    for c in range(C):
+        for label, key in (("whole", "whole"), ("window mean", "track_mean"), ("window median", "track_median")):
+            print("%-8s %-14s" % (names[c], label) + " ".join("%13.7f" % v for v in s[key][0][c]))
+        print("%-8s %d of %d windows active" % (names[c], s["active_windows"][0][c], plan["M"]))
+    if args.json is not None:
+        out = {"estimate": args.estimate, "mixture": args.mixture, "references": args.reference, "sample_rate": separate.SAMPLE_RATE,
+               "samples": L, "channels": list(names), "window_s": args.window, "hop_s": args.hop, "metrics": s["metrics"],
+               "whole": s["whole"][0], "track_mean": s["track_mean"][0], "track_median": s["track_median"][0],
+               "active_windows": s["active_windows"][0], "windows": [list(w) for w in plan["samples"]],
+               "track": res["track"][0].cpu().numpy().tolist(), "active": res["active"][0].cpu().numpy().tolist()}
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)       # (NaN and Infinity as Python's json writes them)
+            f.write("\n")
+        print("score.py: wrote %s" % args.json)
+
+
+if __name__ == "__main__":
+    main()

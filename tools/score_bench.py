@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""Cost of m2h.audio.score (the Scorer): the Gram launch's rate against the chip's copy rate, and the float64 post-processing's share.
+
+    python tools/score_bench.py --out profiles/score_bench.json      # every case, each in a child process under a timeout
+    python tools/score_bench.py --case 16x3x600c2                    # one case in this process
+
+Cases (R recordings x S sources x seconds, C channels): 16x3x600 and 1x2x60, each with C = 1 and C = 2; per-second windows.  Timing: HIP
+events on the stream around the Gram launch and around everything after it (Scorer._timing), summed over the repetitions.
+
+  ms_per_call             first to last event of one Scorer.score
+  gram_ms, gram_bytes_per_s   the m2h_score_gram launch: R C N L fp32 samples read (N = S + 3 rows per (recording, channel); with C = 2 both
+                          channels' workgroups read the mixture) plus the fp64 rows written, over its time
+  gram_share_of_copy_rate that rate over 6.29 TB/s, the chip's measured float4 copy rate
+  post_share              m2h_score_windows and the float64 algebra (metrics_from_gram), as a share of ms_per_call
+  torch_gram_ms           the same tile Grams from torch: the signals stacked, .double(), one batched matmul over the tiles and a sum; timed
+                          before and after the new path (two recordings at a time above 4 GiB of float64 operands); its largest
+                          relative difference from the kernel's Grams is recorded
+No threshold is set anywhere: the file reports what came out.  Every GPU step runs under its own timeout and the driver stops at the
+first failure.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "move2hear-active-av-separation_amd"))
+
+CASES = {"16x3x600c1": (16, 3, 600, 1, 10), "16x3x600c2": (16, 3, 600, 2, 10), "1x2x60c1": (1, 2, 60, 1, 200), "1x2x60c2": (1, 2, 60, 2, 200)}  # R, S, s, C, reps
+ORDER = ("16x3x600c1", "16x3x600c2", "1x2x60c1", "1x2x60c2")
+SEG = 16000
+COPY_RATE = 6.29e12
+
+
+def torch_gram(refs, est, mix, step):
+    """[R, C, J, N] sums and [R, C, J, N, N] products from torch, `step` recordings at a time (L a multiple of the tile)"""
+    import torch
+    R, S, C, L = refs.shape
+    sums, prods = [], []
+    for r0 in range(0, R, step):
+        r1 = min(r0 + step, R)
+        a = torch.cat([refs[r0:r1].transpose(1, 2), est[r0:r1].unsqueeze(2), mix[r0:r1].unsqueeze(1).expand(r1 - r0, C, 2, L)], dim=2)   # [r, C, N, L]
+        a = a.reshape(r1 - r0, C, S + 3, L // SEG, SEG).transpose(2, 3).double()                                                         # [r, C, J, N, tile]
+        sums.append(a.sum(-1))
+        prods.append(a @ a.transpose(-1, -2))
+    return torch.cat(sums), torch.cat(prods)
+
+
+def run_case(case):
+    import torch
+    from m2h import ops
+    from m2h.audio.score import Scorer
+    if not torch.cuda.is_available():
+        raise SystemExit("score_bench: no GPU; this measurement has no CPU path")
+    R, S, seconds, C, reps = CASES[case]
+    dev = torch.device("cuda", 0)
+    L, N = seconds * SEG, S + 3
+    g = torch.Generator(device=dev).manual_seed(7)
+    refs = torch.randn((R, S, C, L), device=dev, generator=g) * 0.1 + 0.01
+    mix = torch.stack([refs[:, :, 0].mean(1), refs[:, :, C - 1].mean(1)], dim=1) + 0.02 * torch.randn((R, 2, L), device=dev, generator=g)
+    est = 0.8 * refs[:, 0] + 0.03 * torch.randn((R, C, L), device=dev, generator=g)
+    sc = Scorer(dev)
+    step = R if R * C * N * L * 8 <= (4 << 30) else 2
+
+    def timed_scorer():
+        marks = []
+        sc._timing = marks
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            sc.score(est, refs, mix)
+        torch.cuda.synchronize()
+        sc._timing = None
+        ms = dict.fromkeys(("score_gram", "metrics"), 0.0)
+        for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
+            if name != "start":
+                ms[name] += e0.elapsed_time(e1)
+        return {k: v / reps for k, v in ms.items()}
+
+    def timed_torch():
+        n = max(1, reps // 5)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            torch_gram(refs, est, mix, step)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    # warm-up of every shape, and the two Grams against each other
+    res0 = sc.score(est, refs, mix)
+    tiles = ops.score_gram(refs, est, mix, SEG)
+    ts, tp = torch_gram(refs, est, mix, step)
+    iu = torch.triu_indices(N, N, device=dev)
+    want = torch.cat([ts, tp[..., iu[0], iu[1]]], dim=-1)
+    diff = float(((tiles - want).abs() / want.abs().clamp_min(1e-300)).max())
+    finite = bool(torch.isfinite(res0["whole"]).all())
+    del ts, tp, want, tiles
+    torch.cuda.synchronize()
+
+    before = timed_torch()
+    t = timed_scorer()
+    after = timed_torch()
+    gram_bytes = R * C * N * L * 4 + R * C * (L // SEG) * (N + N * (N + 1) // 2) * 8
+    total = t["score_gram"] + t["metrics"]
+    rate = gram_bytes / (t["score_gram"] * 1e-3)
+    res = {"case": case, "R": R, "S": S, "C": C, "audio_seconds_per_recording": seconds, "reps": reps, "ms_per_call": total, "gram_ms": t["score_gram"],
+           "gram_bytes": gram_bytes, "gram_bytes_per_s": rate, "gram_share_of_copy_rate": rate / COPY_RATE, "post_ms": t["metrics"],
+           "post_share": t["metrics"] / total, "audio_s_per_s": R * seconds / (total * 1e-3), "torch_gram_ms": [before, after],
+           "torch_gram_recordings_per_step": step, "torch_gram_over_kernel": 0.5 * (before + after) / t["score_gram"],
+           "kernel_vs_torch_gram_max_rel": diff, "whole_scores_finite": finite, "whole_si_sdr_db": float(res0["whole"][0, 0, 0])}
+    print(json.dumps(res))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", choices=sorted(CASES), default=None)
+    ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
+    ap.add_argument("--timeout", type=int, default=120, help="driver mode: seconds per case")
+    args = ap.parse_args()
+    if args.case is not None:
+        run_case(args.case)
+        return
+    results = []
+    for case in ORDER:
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0:
+            print(r.stdout[-4000:])
+            raise SystemExit("score_bench: case %s failed with status %d; stopping" % (case, r.returncode))
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+        results.append(json.loads(line))
+        print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/score_bench.py", "device": "MI355X (gfx950)", "copy_rate_bytes_per_s": COPY_RATE, "results": results}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
