@@ -698,9 +698,11 @@ int m2h_resample_poly(const float* x, const float* G, float* y, int rows, long l
  * m2h/audio/resample.py: ResamplerStream).  A device buffer [rows][cap] holds the absolute samples [origin, origin + cap) of every
  * row: sample g of row q lives at buf[q * cap + g - origin].  `end` is the number of samples received so far (the recording's length
  * at the last call); samples at or past it read as zero and are never written.  The row stride, the origin and `end` are separate
- * arguments; with cap = end = L and origin = 0 every entry point below is its offline twin, and for any window the arithmetic and its
- * order are the twin's: results are bit-identical.  Every call is refused before any launch when the samples below `end` that it
- * reads or writes do not lie inside [origin, origin + cap).
+ * arguments.  The whole-recording entry points above ARE the window cap = end = L, origin = 0 (and n_first = 0, count = L_out for the
+ * rate conversion): each pair runs one kernel behind one set of checks, so results are bit-identical for any window.  Every call
+ * is refused before any launch when the samples below `end` that it reads or writes do not lie inside [origin, origin + cap).
+ * Limits, for the whole-recording entry points too: end, cap (and L) <= 2^40, rows * cap <= 2^44 (m2h_sep_*: rows = R, also for the
+ * [R * 2][cap] input), nseg * R <= 2^20; m2h_resample_poly*: count (and L_out) <= 2^40, rows * max(cap, count) <= 2^44.
  * ------------------------------------------------------------------------------------------------------------------ */
 
 /* m2h_sep_frames_hop's rows for segments [s0, s0 + nseg) (segment s covers [s * hop, s * hop + 16000); (s0 + nseg - 1) * hop < end)

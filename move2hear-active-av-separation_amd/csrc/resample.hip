@@ -221,6 +221,38 @@ static bool rs_run(const float* x, const float* G, float* y, int rows, long long
   return true;
 }
 
+// The checks and the launch of both entry points: outputs [n_first, n_first + count) from the window (x [rows][cap], origin, end) for
+// the entry point `name` (`name` and `name_direct` are string literals: the labels m2h_last_kernel reports).  The whole recording is
+// cap = end = L_in, origin = 0, n_first = 0, count = L_out (`whole`: the count must then be every output, not just few enough).
+static int rs_window_run(const char* name, const char* name_direct, bool whole, const float* x, const float* G, float* y, int rows, long long cap, long long origin,
+                         long long end, long long n_first, long long count, int up, int down, int T, m2h_stream stream) {
+  M2H_REQUIRE(x && G && y, "%s: null pointer", name);
+  M2H_REQUIRE(rows > 0 && cap > 0 && origin >= 0 && end > 0 && n_first >= 0 && up > 0 && down > 0 && T > 0,
+              "%s: bad sizes (rows %d, cap %lld, origin %lld, end %lld, n_first %lld, up %d, down %d, T %d)", name, rows, cap, origin, end, n_first, up, down, T);
+  M2H_REQUIRE(count > 0, "%s: count must be positive, got %lld", name, count);
+  M2H_REQUIRE(up <= RS_MAX_RATIO && down <= RS_MAX_RATIO, "%s: ratio %d/%d is over the limit (max(up, down) <= %d)", name, up, down, RS_MAX_RATIO);
+  M2H_REQUIRE(end <= (1LL << 40) && cap <= (1LL << 40) && count <= (1LL << 40) && (long long)rows * (cap > count ? cap : count) <= (1LL << 44),
+              "%s: bad sizes (rows %d x cap %lld / count %lld is too long)", name, rows, cap, count);
+  M2H_REQUIRE(!whole || count == (end * up + down - 1) / down, "%s: L_out %lld is not ceil(L_in * up / down) = %lld", name, count, (end * up + down - 1) / down);
+  M2H_REQUIRE(n_first + count <= (end * up + down - 1) / down, "%s: outputs [%lld, %lld + %lld) pass ceil(end * up / down) = %lld", name, n_first, n_first, count,
+              (end * up + down - 1) / down);
+  const int half = 10 * (up > down ? up : down);
+  M2H_REQUIRE((long long)T * up >= 2 * half + 1 && T <= 2 * half + 1, "%s: a table of T %d x up %d does not hold the %d taps of this ratio", name, T, up, 2 * half + 1);
+  M2H_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 3) == 0,
+              "%s: buffers must be 4-byte aligned", name);
+  // the samples inside [0, end) that the outputs read: x[j0(n_first) - T + 1 .. j0(n_first + count - 1)]
+  long long jlo = (n_first * down + half) / up - (T - 1);
+  long long jhi = ((n_first + count - 1) * down + half) / up + 1;
+  if (jlo < 0) jlo = 0;
+  if (jhi > end) jhi = end;
+  M2H_REQUIRE(jlo >= jhi || (jlo >= origin && jhi <= origin + cap), "%s: outputs [%lld, %lld + %lld) read samples [%lld, %lld), outside the window [%lld, %lld + %lld)", name,
+              n_first, n_first, count, jlo, jhi, origin, origin, cap);
+  bool direct = false;
+  M2H_REQUIRE(rs_run(x, G, y, rows, cap, origin, end, n_first, n_first + count, count, up, down, T, half, as_stream(stream), &direct), "%s: bad sizes (too many tiles)",
+              name);
+  return launch_status(direct ? name_direct : name);
+}
+
 }  // namespace m2h
 
 using namespace m2h;
@@ -228,47 +260,13 @@ using namespace m2h;
 extern "C" {
 
 int m2h_resample_poly(const float* x, const float* G, float* y, int rows, long long L_in, long long L_out, int up, int down, int T, m2h_stream stream) {
-  M2H_REQUIRE(x && G && y, "resample_poly: null pointer");
-  M2H_REQUIRE(rows > 0 && L_in > 0 && L_out > 0 && up > 0 && down > 0 && T > 0, "resample_poly: bad sizes (rows %d, L_in %lld, L_out %lld, up %d, down %d, T %d)",
-              rows, L_in, L_out, up, down, T);
-  M2H_REQUIRE(up <= RS_MAX_RATIO && down <= RS_MAX_RATIO, "resample_poly: ratio %d/%d is over the limit (max(up, down) <= %d)", up, down, RS_MAX_RATIO);
-  M2H_REQUIRE(L_in <= (1LL << 40) && (long long)rows * (L_in > L_out ? L_in : L_out) <= (1LL << 44), "resample_poly: bad sizes (rows %d x L_in %lld is too long)", rows, L_in);
-  M2H_REQUIRE(L_out == (L_in * up + down - 1) / down, "resample_poly: L_out %lld is not ceil(L_in * up / down) = %lld", L_out, (L_in * up + down - 1) / down);
-  const int half = 10 * (up > down ? up : down);
-  M2H_REQUIRE((long long)T * up >= 2 * half + 1 && T <= 2 * half + 1, "resample_poly: a table of T %d x up %d does not hold the %d taps of this ratio", T, up, 2 * half + 1);
-  M2H_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 3) == 0,
-              "resample_poly: buffers must be 4-byte aligned");
-  bool direct = false;
-  M2H_REQUIRE(rs_run(x, G, y, rows, L_in, 0, L_in, 0, L_out, L_out, up, down, T, half, as_stream(stream), &direct), "resample_poly: bad sizes (too many tiles)");
-  return launch_status(direct ? "resample_poly_direct" : "resample_poly");
+  return rs_window_run("resample_poly", "resample_poly_direct", true, x, G, y, rows, L_in, 0, L_in, 0, L_out, up, down, T, stream);
 }
 
 int m2h_resample_poly_win(const float* x, const float* G, float* y, int rows, long long cap, long long origin, long long end, long long n_first,
                           long long count, int up, int down, int T, m2h_stream stream) {
-  M2H_REQUIRE(x && G && y, "resample_poly_win: null pointer");
-  M2H_REQUIRE(rows > 0 && cap > 0 && origin >= 0 && end > 0 && n_first >= 0 && up > 0 && down > 0 && T > 0,
-              "resample_poly_win: bad sizes (rows %d, cap %lld, origin %lld, end %lld, n_first %lld, up %d, down %d, T %d)", rows, cap, origin, end, n_first, up, down, T);
-  M2H_REQUIRE(count > 0, "resample_poly_win: count must be positive, got %lld", count);
-  M2H_REQUIRE(up <= RS_MAX_RATIO && down <= RS_MAX_RATIO, "resample_poly_win: ratio %d/%d is over the limit (max(up, down) <= %d)", up, down, RS_MAX_RATIO);
-  M2H_REQUIRE(end <= (1LL << 40) && cap <= (1LL << 40) && count <= (1LL << 40) && (long long)rows * (cap > count ? cap : count) <= (1LL << 44),
-              "resample_poly_win: bad sizes (rows %d x cap %lld / count %lld is too long)", rows, cap, count);
-  M2H_REQUIRE(n_first + count <= (end * up + down - 1) / down, "resample_poly_win: outputs [%lld, %lld + %lld) pass ceil(end * up / down) = %lld", n_first, n_first,
-              count, (end * up + down - 1) / down);
-  const int half = 10 * (up > down ? up : down);
-  M2H_REQUIRE((long long)T * up >= 2 * half + 1 && T <= 2 * half + 1, "resample_poly_win: a table of T %d x up %d does not hold the %d taps of this ratio", T, up, 2 * half + 1);
-  M2H_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(G) & 3) == 0,
-              "resample_poly_win: buffers must be 4-byte aligned");
-  // the samples inside [0, end) that the outputs read: x[j0(n_first) - T + 1 .. j0(n_first + count - 1)]
-  long long jlo = (n_first * down + half) / up - (T - 1);
-  long long jhi = ((n_first + count - 1) * down + half) / up + 1;
-  if (jlo < 0) jlo = 0;
-  if (jhi > end) jhi = end;
-  M2H_REQUIRE(jlo >= jhi || (jlo >= origin && jhi <= origin + cap), "resample_poly_win: outputs [%lld, %lld + %lld) read samples [%lld, %lld), outside the window [%lld, %lld + %lld)",
-              n_first, n_first, count, jlo, jhi, origin, origin, cap);
-  bool direct = false;
-  M2H_REQUIRE(rs_run(x, G, y, rows, cap, origin, end, n_first, n_first + count, count, up, down, T, half, as_stream(stream), &direct),
-              "resample_poly_win: bad sizes (too many tiles)");
-  return launch_status(direct ? "resample_poly_win_direct" : "resample_poly_win");
+  return rs_window_run("resample_poly_win", "resample_poly_win_direct", false, x, G, y, rows, cap, origin, end, n_first, count, up, down, T, stream);
 }
 
 }  // extern "C"
+

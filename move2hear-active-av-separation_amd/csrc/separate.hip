@@ -23,15 +23,15 @@ constexpr int SEP_HOP = 512;
 constexpr int SEP_KT = 32;        // bins per workgroup of the two transposing kernels
 
 // frames[((sl*R + r)*2 + c)*32 + t][n] = window[n] * seg[t*512 + n - 511] (reflected inside the segment), n < 1023; 0 at n = 1023.
-// seg[j] = wave[r][c][(s0 + sl)*16000 + j] below L, 0 from L on.  One thread = four consecutive n = one 16-byte store; the source
-// offsets are odd by construction (n - 511), so the reads are scalar and coalesced across the wave.
-// Segment s starts at sample s * hop: 16000 for the plain path, 16000 / k for overlapped segments (sep_frames_hop_kernel).
-// Window form (sep_frames_win_kernel, a live feed: m2h/separate.py, SeparatorStream): the buffer holds the absolute samples
-// [origin, origin + stride) of every row, sample g at wave[(r*2 + c)*stride + g - origin], and samples at or past `end` are zero.
-// The whole recording is the window stride = end = L, origin = 0.
-__device__ __forceinline__ void sep_frames_body(const float* __restrict__ wave, const float* __restrict__ window /* [1024], [1023] = 0 */,
-                                                float* __restrict__ frames, int R, long long stride, long long origin, long long end, int hop,
-                                                int s0, int nseg) {
+// seg[j] = sample s*hop + j of recording r, channel c, for segment s = s0 + sl: below `end` from the buffer, 0 from `end` on.  Segment s
+// starts at sample s * hop: 16000 for the plain path, 16000 / k for overlapped segments.  One thread = four consecutive n = one
+// 16-byte store; the source offsets are odd by construction (n - 511), so the reads are scalar and coalesced across the wave.
+// The buffer is a window: it holds the absolute samples [origin, origin + stride) of every row, sample g at
+// wave[(r*2 + c)*stride + g - origin] (a live feed: m2h/separate.py, SeparatorStream).  The whole recording is the window
+// stride = end = L, origin = 0.
+__global__ __launch_bounds__(256) void sep_frames_kernel(const float* __restrict__ wave, const float* __restrict__ window /* [1024], [1023] = 0 */,
+                                                         float* __restrict__ frames, int R, long long stride, long long origin, long long end, int hop,
+                                                         int s0, int nseg) {
   const size_t total = (size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int n0 = (int)(i % (SEP_LD / 4)) * 4;
@@ -62,21 +62,6 @@ __device__ __forceinline__ void sep_frames_body(const float* __restrict__ wave, 
     }
     *reinterpret_cast<float4*>(frames + row * SEP_LD + n0) = make_float4(v[0], v[1], v[2], v[3]);
   }
-}
-
-__global__ __launch_bounds__(256) void sep_frames_kernel(const float* __restrict__ wave, const float* __restrict__ window, float* __restrict__ frames, int R,
-                                                         long long L, int s0, int nseg) {
-  sep_frames_body(wave, window, frames, R, L, 0, L, SEP_SEG, s0, nseg);
-}
-
-__global__ __launch_bounds__(256) void sep_frames_hop_kernel(const float* __restrict__ wave, const float* __restrict__ window, float* __restrict__ frames, int R,
-                                                             long long L, int hop, int s0, int nseg) {
-  sep_frames_body(wave, window, frames, R, L, 0, L, hop, s0, nseg);
-}
-
-__global__ __launch_bounds__(256) void sep_frames_win_kernel(const float* __restrict__ buf, const float* __restrict__ window, float* __restrict__ frames, int R,
-                                                             long long cap, long long origin, long long end, int hop, int s0, int nseg) {
-  sep_frames_body(buf, window, frames, R, cap, origin, end, hop, s0, nseg);
 }
 
 // spec rows [(n*2 + c)*32 + t][1024] = [Re(512) | Im(512)]  ->  mag [n][512][32][2] = log1p|X_c|, phasor [n][512][32][2] = D / |D|
@@ -234,10 +219,11 @@ __device__ __forceinline__ float sep_ola_sample(const float* __restrict__ fr, co
 // Windowed overlap-add as a gather (istft_ola_kernel's arithmetic), every segment written at its offset of y [R][L] and cut at L:
 // y[r][(s0 + sl)*16000 + j] = (sum_t frames[(sl*R + r)*32 + t][jj - 512 t] * window[jj - 512 t]) / wss(jj), jj = j + 511.
 // One thread = four consecutive j: one 16-byte store where the destination is aligned (always when L % 4 == 0) and inside L.
-// Window form (sep_istft_ola_win_kernel): y holds the absolute samples [origin, origin + stride) of every row, sample n at
-// y[r*stride + n - origin], cut at L = the samples received; the whole recording is stride = L, origin = 0.
-__device__ __forceinline__ void sep_istft_ola_body(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */, float* __restrict__ y,
-                                                   int R, long long stride, long long origin, long long L, int s0, int nseg) {
+// y is a window: it holds the absolute samples [origin, origin + stride) of every row, sample n at y[r*stride + n - origin], cut at
+// L = the samples received; the whole recording is stride = L, origin = 0.
+__global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                            float* __restrict__ y, int R, long long stride, long long origin, long long L, int s0,
+                                                            int nseg) {
   const size_t total = (size_t)nseg * R * (SEP_SEG / 4);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int j0 = (int)(i % (SEP_SEG / 4)) * 4;
@@ -261,29 +247,19 @@ __device__ __forceinline__ void sep_istft_ola_body(const float* __restrict__ fra
   }
 }
 
-__global__ __launch_bounds__(256) void sep_istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
-                                                            float* __restrict__ y, int R, long long L, int s0, int nseg) {
-  sep_istft_ola_body(frames, window, y, R, L, 0, L, s0, nseg);
-}
-
-__global__ __launch_bounds__(256) void sep_istft_ola_win_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
-                                                                float* __restrict__ y, int R, long long cap, long long origin, long long end, int s0,
-                                                                int nseg) {
-  sep_istft_ola_body(frames, window, y, R, cap, origin, end, s0, nseg);
-}
-
 // Overlapped segments (segment s covers samples [s*hop, s*hop + 16000), hop = 16000 / k) cross-faded into y [R][L]:
 // y[r][n] = sum_s xwin[n - s*hop] * v_s[n - s*hop] / W[n], W[n] = sum_s xwin[n - s*hop] over all segments 0 <= s < S of the recording
 // that cover n, v_s = the segment's inverse transform (sep_ola_sample).  A gather: one thread = four consecutive n of the span
 // [s0*hop, min(L, (s0 + nseg - 1)*hop + 16000)) the chunk's segments cover; hop % 4 == 0, so the four share their covering segments.
 // The chunk's covering segments are added in ascending order onto 0 when the chunk holds the sample's first covering segment and
 // onto y[n] otherwise: chunks come in ascending order, y needs no clearing, and the order of the additions is the same for any chunking.
-// Window form (sep_istft_xfade_win_kernel): y holds the absolute samples [origin, origin + stride) of every row, sample n at
-// y[r*stride + n - origin]; the partial sums of the samples that later segments still cover stay there between calls.  L = the samples
-// received so far: a sample below it is covered by no segment past ceil(L / hop) - 1 whatever arrives later, so W[n] is final.
-__device__ __forceinline__ void sep_istft_xfade_body(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
-                                                     const float* __restrict__ xwin /* [16000] */, float* y, int R, long long stride, long long origin,
-                                                     long long L, int hop, int s0, int nseg, long long S) {
+// y is a window: it holds the absolute samples [origin, origin + stride) of every row, sample n at y[r*stride + n - origin]; on a live
+// feed the partial sums of the samples that later segments still cover stay there between calls, and L = the samples received so far:
+// a sample below it is covered by no segment past S - 1 = ceil(L / hop) - 1 whatever arrives later, so W[n] is final.  The whole
+// recording is stride = L, origin = 0.
+__global__ __launch_bounds__(256) void sep_istft_xfade_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
+                                                              const float* __restrict__ xwin /* [16000] */, float* y, int R, long long stride,
+                                                              long long origin, long long L, int hop, int s0, int nseg, long long S) {
   const long long n_first = (long long)s0 * hop;
   long long n_end = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
   if (n_end > L) n_end = L;
@@ -337,18 +313,6 @@ __device__ __forceinline__ void sep_istft_xfade_body(const float* __restrict__ f
   }
 }
 
-__global__ __launch_bounds__(256) void sep_istft_xfade_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
-                                                              const float* __restrict__ xwin /* [16000] */, float* y, int R, long long L, int hop,
-                                                              int s0, int nseg, long long S) {
-  sep_istft_xfade_body(frames, window, xwin, y, R, L, 0, L, hop, s0, nseg, S);
-}
-
-__global__ __launch_bounds__(256) void sep_istft_xfade_win_kernel(const float* __restrict__ frames, const float* __restrict__ window /* [1022] */,
-                                                                  const float* __restrict__ xwin /* [16000] */, float* y, int R, long long cap,
-                                                                  long long origin, long long end, int hop, int s0, int nseg, long long S) {
-  sep_istft_xfade_body(frames, window, xwin, y, R, cap, origin, end, hop, s0, nseg, S);
-}
-
 static inline unsigned sep_grid(size_t total) {
   size_t g = (total + 255) / 256;
   if (g > 16384) g = 16384;
@@ -356,25 +320,11 @@ static inline unsigned sep_grid(size_t total) {
   return (unsigned)g;
 }
 
-// chunk [s0, s0 + nseg) of a recording of L samples: inside its ceil(L / 16000) segments, batch rows within int range
-static inline bool sep_chunk_ok(int R, long long L, int s0, int nseg) {
-  if (R <= 0 || L <= 0 || s0 < 0 || nseg <= 0) return false;
-  const long long S = (L + SEP_SEG - 1) / SEP_SEG;
-  if ((long long)s0 + nseg > S) return false;
-  return (long long)nseg * R <= (1 << 20);
-}
-
-// the same for overlapped segments: hop = 16000 / k for k in {1, 2, 4}, ceil(L / hop) segments
+// hop = 16000 / k for k in {1, 2, 4}
 static inline bool sep_hop_ok(int hop) { return hop == SEP_SEG || hop == SEP_SEG / 2 || hop == SEP_SEG / 4; }
 
-static inline bool sep_chunk_hop_ok(int R, long long L, int hop, int s0, int nseg) {
-  if (R <= 0 || L <= 0 || s0 < 0 || nseg <= 0) return false;
-  const long long S = (L + hop - 1) / hop;
-  if ((long long)s0 + nseg > S) return false;
-  return (long long)nseg * R <= (1 << 20);
-}
-
-// window forms: rows [R][cap] hold the absolute samples [origin, origin + cap); `end` samples have been received
+// rows [R][cap] hold the absolute samples [origin, origin + cap); `end` samples have been received; segments [s0, s0 + nseg) lie
+// inside the ceil(end / hop) segments, batch rows within int range
 static inline bool sep_win_ok(int R, long long cap, long long origin, long long end, int hop, int s0, int nseg) {
   if (R <= 0 || cap <= 0 || origin < 0 || end <= 0 || s0 < 0 || nseg <= 0) return false;
   if (end > (1LL << 40) || cap > (1LL << 40) || (long long)R * cap > (1LL << 44)) return false;
@@ -392,6 +342,49 @@ static inline bool sep_win_holds(long long cap, long long origin, long long end,
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The runners: the checks, the grid and the launch of one kernel, for the entry point `name` (a string literal: it is the label
+// m2h_last_kernel reports).  A whole-recording entry passes cap = end = L, origin = 0.
+static int sep_window_check(const char* name, int R, long long cap, long long origin, long long end, int hop, int s0, int nseg) {
+  M2H_REQUIRE(sep_hop_ok(hop), "%s: hop must be 16000, 8000 or 4000, got %d", name, hop);
+  M2H_REQUIRE(sep_win_ok(R, cap, origin, end, hop, s0, nseg), "%s: bad sizes (R %d, cap %lld, origin %lld, end %lld, hop %d, segments [%d, %d + %d))", name, R, cap,
+              origin, end, hop, s0, s0, nseg);
+  M2H_REQUIRE(sep_win_holds(cap, origin, end, hop, s0, nseg), "%s: segments [%d, %d + %d) at hop %d leave the window [%lld, %lld + %lld) (end %lld)", name, s0, s0, nseg,
+              hop, origin, origin, cap, end);
+  return 0;
+}
+
+static int sep_frames_run(const char* name, const float* buf, const float* window, float* frames, int R, long long cap, long long origin, long long end, int hop,
+                          int s0, int nseg, m2h_stream stream) {
+  M2H_REQUIRE(buf && window && frames, "%s: null pointer", name);
+  if (const int rc = sep_window_check(name, R, cap, origin, end, hop, s0, nseg)) return rc;
+  M2H_REQUIRE(aligned16(window) && aligned16(frames), "%s: window / frames must be 16-byte aligned", name);
+  M2H_LAUNCH(sep_frames_kernel, dim3(sep_grid((size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4))), dim3(256), 0, as_stream(stream), buf, window, frames, R, cap, origin,
+             end, hop, s0, nseg);
+  return launch_status(name);
+}
+
+static int sep_istft_ola_run(const char* name, const float* frames, const float* window, float* y, int R, long long cap, long long origin, long long end, int s0,
+                             int nseg, m2h_stream stream) {
+  M2H_REQUIRE(frames && window && y, "%s: null pointer", name);
+  if (const int rc = sep_window_check(name, R, cap, origin, end, SEP_SEG, s0, nseg)) return rc;
+  M2H_LAUNCH(sep_istft_ola_kernel, dim3(sep_grid((size_t)nseg * R * (SEP_SEG / 4))), dim3(256), 0, as_stream(stream), frames, window, y, R, cap, origin, end, s0,
+             nseg);
+  return launch_status(name);
+}
+
+static int sep_istft_xfade_run(const char* name, const float* frames, const float* window, const float* xwin, float* y, int R, long long cap, long long origin,
+                               long long end, int hop, int s0, int nseg, m2h_stream stream) {
+  M2H_REQUIRE(frames && window && xwin && y, "%s: null pointer", name);
+  if (const int rc = sep_window_check(name, R, cap, origin, end, hop, s0, nseg)) return rc;
+  M2H_REQUIRE(aligned16(xwin), "%s: the cross-fade window must be 16-byte aligned", name);
+  const long long S = (end + hop - 1) / hop;
+  long long n_end = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
+  if (n_end > end) n_end = end;
+  const size_t quads = (size_t)((n_end - (long long)s0 * hop + 3) / 4);
+  M2H_LAUNCH(sep_istft_xfade_kernel, dim3(sep_grid(quads * R)), dim3(256), 0, as_stream(stream), frames, window, xwin, y, R, cap, origin, end, hop, s0, nseg, S);
+  return launch_status(name);
+}
+
 }  // namespace m2h
 
 using namespace m2h;
@@ -399,12 +392,7 @@ using namespace m2h;
 extern "C" {
 
 int m2h_sep_frames(const float* wave, const float* window, float* frames, int R, long long L, int s0, int nseg, m2h_stream stream) {
-  M2H_REQUIRE(wave && window && frames, "sep_frames: null pointer");
-  M2H_REQUIRE(sep_chunk_ok(R, L, s0, nseg), "sep_frames: bad sizes (R %d, L %lld, segments [%d, %d + %d))", R, L, s0, s0, nseg);
-  M2H_REQUIRE(aligned16(window) && aligned16(frames), "sep_frames: window / frames must be 16-byte aligned");
-  M2H_LAUNCH(sep_frames_kernel, dim3(sep_grid((size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4))), dim3(256), 0, as_stream(stream), wave, window, frames, R, L,
-             s0, nseg);
-  return launch_status("sep_frames");
+  return sep_frames_run("sep_frames", wave, window, frames, R, L, 0, L, SEP_SEG, s0, nseg, stream);
 }
 
 int m2h_sep_stft_post(const float* spec, float* mag, float* phasor, int N, m2h_stream stream) {
@@ -432,80 +420,34 @@ int m2h_sep_bin_rows(const float* spec, const float* masks, float* rows, int N, 
 }
 
 int m2h_sep_istft_ola(const float* frames, const float* window, float* y, int R, long long L, int s0, int nseg, m2h_stream stream) {
-  M2H_REQUIRE(frames && window && y, "sep_istft_ola: null pointer");
-  M2H_REQUIRE(sep_chunk_ok(R, L, s0, nseg), "sep_istft_ola: bad sizes (R %d, L %lld, segments [%d, %d + %d))", R, L, s0, s0, nseg);
-  M2H_LAUNCH(sep_istft_ola_kernel, dim3(sep_grid((size_t)nseg * R * (SEP_SEG / 4))), dim3(256), 0, as_stream(stream), frames, window, y, R, L, s0, nseg);
-  return launch_status("sep_istft_ola");
+  return sep_istft_ola_run("sep_istft_ola", frames, window, y, R, L, 0, L, s0, nseg, stream);
 }
 
 int m2h_sep_frames_hop(const float* wave, const float* window, float* frames, int R, long long L, int hop, int s0, int nseg, m2h_stream stream) {
-  M2H_REQUIRE(wave && window && frames, "sep_frames_hop: null pointer");
-  M2H_REQUIRE(sep_hop_ok(hop), "sep_frames_hop: hop must be 16000, 8000 or 4000, got %d", hop);
-  M2H_REQUIRE(sep_chunk_hop_ok(R, L, hop, s0, nseg), "sep_frames_hop: bad sizes (R %d, L %lld, hop %d, segments [%d, %d + %d))", R, L, hop, s0, s0, nseg);
-  M2H_REQUIRE(aligned16(window) && aligned16(frames), "sep_frames_hop: window / frames must be 16-byte aligned");
-  M2H_LAUNCH(sep_frames_hop_kernel, dim3(sep_grid((size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4))), dim3(256), 0, as_stream(stream), wave, window, frames, R,
-             L, hop, s0, nseg);
-  return launch_status("sep_frames_hop");
+  return sep_frames_run("sep_frames_hop", wave, window, frames, R, L, 0, L, hop, s0, nseg, stream);
 }
 
 int m2h_sep_istft_xfade(const float* frames, const float* window, const float* xwin, float* y, int R, long long L, int hop, int s0, int nseg,
                         m2h_stream stream) {
-  M2H_REQUIRE(frames && window && xwin && y, "sep_istft_xfade: null pointer");
-  M2H_REQUIRE(sep_hop_ok(hop), "sep_istft_xfade: hop must be 16000, 8000 or 4000, got %d", hop);
-  M2H_REQUIRE(sep_chunk_hop_ok(R, L, hop, s0, nseg), "sep_istft_xfade: bad sizes (R %d, L %lld, hop %d, segments [%d, %d + %d))", R, L, hop, s0, s0, nseg);
-  M2H_REQUIRE(aligned16(xwin), "sep_istft_xfade: the cross-fade window must be 16-byte aligned");
-  const long long S = (L + hop - 1) / hop;
-  long long n_end = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
-  if (n_end > L) n_end = L;
-  const size_t quads = (size_t)((n_end - (long long)s0 * hop + 3) / 4);
-  M2H_LAUNCH(sep_istft_xfade_kernel, dim3(sep_grid(quads * R)), dim3(256), 0, as_stream(stream), frames, window, xwin, y, R, L, hop, s0, nseg, S);
-  return launch_status("sep_istft_xfade");
+  return sep_istft_xfade_run("sep_istft_xfade", frames, window, xwin, y, R, L, 0, L, hop, s0, nseg, stream);
 }
 
 // ---- window forms: a live feed, block by block (m2h/separate.py, SeparatorStream)
 
 int m2h_sep_frames_win(const float* buf, const float* window, float* frames, int R, long long cap, long long origin, long long end, int hop, int s0,
                        int nseg, m2h_stream stream) {
-  M2H_REQUIRE(buf && window && frames, "sep_frames_win: null pointer");
-  M2H_REQUIRE(sep_hop_ok(hop), "sep_frames_win: hop must be 16000, 8000 or 4000, got %d", hop);
-  M2H_REQUIRE(sep_win_ok(R, cap, origin, end, hop, s0, nseg), "sep_frames_win: bad sizes (R %d, cap %lld, origin %lld, end %lld, hop %d, segments [%d, %d + %d))",
-              R, cap, origin, end, hop, s0, s0, nseg);
-  M2H_REQUIRE(sep_win_holds(cap, origin, end, hop, s0, nseg), "sep_frames_win: segments [%d, %d + %d) at hop %d leave the window [%lld, %lld + %lld) (end %lld)",
-              s0, s0, nseg, hop, origin, origin, cap, end);
-  M2H_REQUIRE(aligned16(window) && aligned16(frames), "sep_frames_win: window / frames must be 16-byte aligned");
-  M2H_LAUNCH(sep_frames_win_kernel, dim3(sep_grid((size_t)nseg * R * 2 * SEP_T * (SEP_LD / 4))), dim3(256), 0, as_stream(stream), buf, window, frames, R,
-             cap, origin, end, hop, s0, nseg);
-  return launch_status("sep_frames_win");
+  return sep_frames_run("sep_frames_win", buf, window, frames, R, cap, origin, end, hop, s0, nseg, stream);
 }
 
 int m2h_sep_istft_ola_win(const float* frames, const float* window, float* y, int R, long long cap, long long origin, long long end, int s0, int nseg,
                           m2h_stream stream) {
-  M2H_REQUIRE(frames && window && y, "sep_istft_ola_win: null pointer");
-  M2H_REQUIRE(sep_win_ok(R, cap, origin, end, SEP_SEG, s0, nseg), "sep_istft_ola_win: bad sizes (R %d, cap %lld, origin %lld, end %lld, segments [%d, %d + %d))", R,
-              cap, origin, end, s0, s0, nseg);
-  M2H_REQUIRE(sep_win_holds(cap, origin, end, SEP_SEG, s0, nseg), "sep_istft_ola_win: segments [%d, %d + %d) leave the window [%lld, %lld + %lld) (end %lld)", s0, s0,
-              nseg, origin, origin, cap, end);
-  M2H_LAUNCH(sep_istft_ola_win_kernel, dim3(sep_grid((size_t)nseg * R * (SEP_SEG / 4))), dim3(256), 0, as_stream(stream), frames, window, y, R, cap, origin,
-             end, s0, nseg);
-  return launch_status("sep_istft_ola_win");
+  return sep_istft_ola_run("sep_istft_ola_win", frames, window, y, R, cap, origin, end, s0, nseg, stream);
 }
 
 int m2h_sep_istft_xfade_win(const float* frames, const float* window, const float* xwin, float* y, int R, long long cap, long long origin, long long end,
                             int hop, int s0, int nseg, m2h_stream stream) {
-  M2H_REQUIRE(frames && window && xwin && y, "sep_istft_xfade_win: null pointer");
-  M2H_REQUIRE(sep_hop_ok(hop), "sep_istft_xfade_win: hop must be 16000, 8000 or 4000, got %d", hop);
-  M2H_REQUIRE(sep_win_ok(R, cap, origin, end, hop, s0, nseg), "sep_istft_xfade_win: bad sizes (R %d, cap %lld, origin %lld, end %lld, hop %d, segments [%d, %d + %d))",
-              R, cap, origin, end, hop, s0, s0, nseg);
-  M2H_REQUIRE(sep_win_holds(cap, origin, end, hop, s0, nseg), "sep_istft_xfade_win: segments [%d, %d + %d) at hop %d leave the window [%lld, %lld + %lld) (end %lld)",
-              s0, s0, nseg, hop, origin, origin, cap, end);
-  M2H_REQUIRE(aligned16(xwin), "sep_istft_xfade_win: the cross-fade window must be 16-byte aligned");
-  const long long S = (end + hop - 1) / hop;
-  long long n_end = (long long)(s0 + nseg - 1) * hop + SEP_SEG;
-  if (n_end > end) n_end = end;
-  const size_t quads = (size_t)((n_end - (long long)s0 * hop + 3) / 4);
-  M2H_LAUNCH(sep_istft_xfade_win_kernel, dim3(sep_grid(quads * R)), dim3(256), 0, as_stream(stream), frames, window, xwin, y, R, cap, origin, end, hop, s0,
-             nseg, S);
-  return launch_status("sep_istft_xfade_win");
+  return sep_istft_xfade_run("sep_istft_xfade_win", frames, window, xwin, y, R, cap, origin, end, hop, s0, nseg, stream);
 }
 
 }  // extern "C"
+

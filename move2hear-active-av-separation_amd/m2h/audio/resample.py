@@ -181,7 +181,8 @@ class ResamplerStream:
         if count <= 0:
             return torch.empty(self.lead + (0,), device=self.rs.device, dtype=torch.float32)
         w = self.win
-        y = ops.resample_poly_win(w.buf.view(self.rows, w.cap), self.rs.table, self.rs.up, self.rs.down, w.origin, self.received, self.emitted, count)
+        y = ops.resample_poly(w.buf.view(self.rows, w.cap), self.rs.table, self.rs.up, self.rs.down, origin=w.origin, end=self.received, n_first=self.emitted,
+                              count=count)
         self.emitted += count
         return y.view(self.lead + (count,))
 

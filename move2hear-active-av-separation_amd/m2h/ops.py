@@ -1095,34 +1095,52 @@ def acoustic_mem_small(pred_mono, prev_mem, not_done, w0p, w1p):
 
 # ---- separation of long recordings (csrc/separate.hip; driven by m2h/separate.py) ----
 SEP_SEGMENT, SEP_FRAMES, SEP_BINS, SEP_LD = 16000, 32, 512, 1024
+SEP_HOPS = (16000, 8000, 4000)
 
 
-def _sep_chunk(name, R, L, s0, nseg):
-    S = -(-L // SEP_SEGMENT)
-    if R < 1 or L < 1 or s0 < 0 or nseg < 1 or s0 + nseg > S:
-        raise RuntimeError("m2h.%s: segments [%d, %d) do not lie inside a [%d, 2, %d] recording of %d segments" % (name, s0, s0 + nseg, R, L, S))
+def _sep_window(name, cap, hop, s0, nseg, origin, end):
+    """The sample window of the framing and overlap-add ops (include/m2h.h, "Window forms"): rows of `cap` samples hold the absolute
+    samples [origin, origin + cap) of a recording of which `end` have arrived.  end=None: the rows are the whole recording, and the
+    segments must lie inside it; otherwise the library checks the ranges and refuses before any launch.  Returns (origin, end, whole)."""
+    if end is not None:
+        return int(origin), int(end), False
+    if origin:
+        raise RuntimeError("m2h.%s: origin = %s needs the window's end" % (name, origin))
+    if hop not in SEP_HOPS:
+        raise RuntimeError("m2h.%s: hop must be one of %s, got %s" % (name, SEP_HOPS, hop))
+    S = -(-cap // hop)
+    if cap < 1 or s0 < 0 or nseg < 1 or s0 + nseg > S:
+        raise RuntimeError("m2h.%s: segments [%d, %d) do not lie inside a recording of %d samples, %d segments at hop %d" % (name, s0, s0 + nseg, cap, S, hop))
+    return 0, cap, True
 
 
-def sep_frames(wave, window, s0, nseg, out=None):
-    """wave [R,2,L] -> the forward DFT GEMM's rows [nseg*R*2*32, 1024] for segments [s0, s0+nseg), framed and windowed straight from
-    the recording (segment-local reflect index, zeros past L; m2h_sep_frames).  window: [1024] = periodic Hann(1023) + one zero."""
-    _chk(wave, "sep_frames(wave)")
+def sep_frames(buf, window, s0, nseg, hop=SEP_SEGMENT, origin=0, end=None, out=None):
+    """buf [R,2,cap] -> the forward DFT GEMM's rows [nseg*R*2*32, 1024] for segments [s0, s0+nseg), framed and windowed straight from
+    the samples: segment s covers [s*hop, s*hop + 16000), hop in SEP_HOPS, segment-local reflect index, zeros from `end` on.
+    window: [1024] = periodic Hann(1023) + one zero.  buf is the whole recording (m2h_sep_frames_hop) or, with `end`, the window
+    [origin, origin + cap) of a recording of which `end` samples have arrived (m2h_sep_frames_win)."""
+    _chk(buf, "sep_frames(buf)")
     _chk(window, "sep_frames(window)")
-    if wave.dim() != 3 or wave.shape[1] != 2:
-        raise RuntimeError("m2h.sep_frames: expected a [R, 2, L] recording, got %s" % (tuple(wave.shape),))
+    if buf.dim() != 3 or buf.shape[1] != 2 or buf.shape[0] < 1 or buf.shape[2] < 1:
+        raise RuntimeError("m2h.sep_frames: expected a [R, 2, L] recording or a [R, 2, cap] window, got %s" % (tuple(buf.shape),))
     if window.numel() != SEP_LD:
         raise RuntimeError("m2h.sep_frames: window must hold %d floats, got %d" % (SEP_LD, window.numel()))
-    R, _, L = wave.shape
-    _sep_chunk("sep_frames", R, L, s0, nseg)
-    rows = nseg * R * 2 * SEP_FRAMES
+    R, _, cap = buf.shape
+    origin, end, whole = _sep_window("sep_frames", cap, hop, s0, nseg, origin, end)
+    rows = max(int(nseg), 0) * R * 2 * SEP_FRAMES
     if out is None:
-        out = torch.empty((rows, SEP_LD), device=wave.device, dtype=torch.float32)
+        out = torch.empty((rows, SEP_LD), device=buf.device, dtype=torch.float32)
     else:
         _chk(out, "sep_frames(out)")
         if tuple(out.shape) != (rows, SEP_LD):
             raise RuntimeError("m2h.sep_frames: out must be [%d, %d], got %s" % (rows, SEP_LD, tuple(out.shape)))
-    with torch.cuda.device(wave.device):
-        _lib.check(_lib.load().m2h_sep_frames(_ptr(wave), _ptr(window), _ptr(out), R, L, s0, nseg, _stream(wave)), "m2h_sep_frames")
+    lib = _lib.load()
+    with torch.cuda.device(buf.device):
+        if whole:
+            _lib.check(lib.m2h_sep_frames_hop(_ptr(buf), _ptr(window), _ptr(out), R, cap, hop, s0, nseg, _stream(buf)), "m2h_sep_frames_hop")
+        else:
+            _lib.check(lib.m2h_sep_frames_win(_ptr(buf), _ptr(window), _ptr(out), R, cap, origin, end, int(hop), int(s0), int(nseg), _stream(buf)),
+                       "m2h_sep_frames_win")
     return out
 
 
@@ -1178,76 +1196,54 @@ def sep_bin_rows(spec, masks, out=None):
     return out
 
 
-def sep_istft_ola(frames, window, y, s0, nseg):
+def sep_istft_ola(frames, window, y, s0, nseg, origin=0, end=None):
     """The inverse GEMM's rows [nseg*R*32, 1024] -> windowed overlap-add of segments [s0, s0+nseg) written at their offsets of
-    y [R, L], cut at L (m2h_sep_istft_ola).  window: periodic Hann(1022)."""
+    y [R, cap], cut at `end`.  window: periodic Hann(1022).  y is the whole recording (m2h_sep_istft_ola) or, with `end`, the window
+    [origin, origin + cap) of a recording of which `end` samples have arrived (m2h_sep_istft_ola_win)."""
     _chk(frames, "sep_istft_ola(frames)")
     _chk(window, "sep_istft_ola(window)")
     _chk(y, "sep_istft_ola(y)")
-    if y.dim() != 2:
-        raise RuntimeError("m2h.sep_istft_ola: y must be [R, L], got %s" % (tuple(y.shape),))
-    R, L = y.shape
-    _sep_chunk("sep_istft_ola", R, L, s0, nseg)
+    if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
+        raise RuntimeError("m2h.sep_istft_ola: y must be [R, L] or a window [R, cap], got %s" % (tuple(y.shape),))
+    R, cap = y.shape
+    origin, end, whole = _sep_window("sep_istft_ola", cap, SEP_SEGMENT, s0, nseg, origin, end)
     if tuple(frames.shape) != (nseg * R * SEP_FRAMES, SEP_LD) or window.numel() < 1022:
         raise RuntimeError("m2h.sep_istft_ola: expected frames [%d, %d] and a 1022-point window, got %s and %d points"
                            % (nseg * R * SEP_FRAMES, SEP_LD, tuple(frames.shape), window.numel()))
+    lib = _lib.load()
     with torch.cuda.device(y.device):
-        _lib.check(_lib.load().m2h_sep_istft_ola(_ptr(frames), _ptr(window), _ptr(y), R, L, s0, nseg, _stream(y)), "m2h_sep_istft_ola")
+        if whole:
+            _lib.check(lib.m2h_sep_istft_ola(_ptr(frames), _ptr(window), _ptr(y), R, cap, s0, nseg, _stream(y)), "m2h_sep_istft_ola")
+        else:
+            _lib.check(lib.m2h_sep_istft_ola_win(_ptr(frames), _ptr(window), _ptr(y), R, cap, origin, end, int(s0), int(nseg), _stream(y)), "m2h_sep_istft_ola_win")
     return y
 
 
-SEP_HOPS = (16000, 8000, 4000)
-
-
-def _sep_chunk_hop(name, R, L, hop, s0, nseg):
-    if hop not in SEP_HOPS:
-        raise RuntimeError("m2h.%s: hop must be one of %s, got %s" % (name, SEP_HOPS, hop))
-    S = -(-L // hop)
-    if R < 1 or L < 1 or s0 < 0 or nseg < 1 or s0 + nseg > S:
-        raise RuntimeError("m2h.%s: segments [%d, %d) do not lie inside a [%d, 2, %d] recording of %d segments at hop %d" % (name, s0, s0 + nseg, R, L, S, hop))
-
-
-def sep_frames_hop(wave, window, hop, s0, nseg, out=None):
-    """sep_frames for overlapped segments: segment s covers samples [s*hop, s*hop + 16000) of the recording, hop in SEP_HOPS, and
-    there are ceil(L / hop) of them (m2h_sep_frames_hop)."""
-    _chk(wave, "sep_frames_hop(wave)")
-    _chk(window, "sep_frames_hop(window)")
-    if wave.dim() != 3 or wave.shape[1] != 2:
-        raise RuntimeError("m2h.sep_frames_hop: expected a [R, 2, L] recording, got %s" % (tuple(wave.shape),))
-    if window.numel() != SEP_LD:
-        raise RuntimeError("m2h.sep_frames_hop: window must hold %d floats, got %d" % (SEP_LD, window.numel()))
-    R, _, L = wave.shape
-    _sep_chunk_hop("sep_frames_hop", R, L, hop, s0, nseg)
-    rows = nseg * R * 2 * SEP_FRAMES
-    if out is None:
-        out = torch.empty((rows, SEP_LD), device=wave.device, dtype=torch.float32)
-    else:
-        _chk(out, "sep_frames_hop(out)")
-        if tuple(out.shape) != (rows, SEP_LD):
-            raise RuntimeError("m2h.sep_frames_hop: out must be [%d, %d], got %s" % (rows, SEP_LD, tuple(out.shape)))
-    with torch.cuda.device(wave.device):
-        _lib.check(_lib.load().m2h_sep_frames_hop(_ptr(wave), _ptr(window), _ptr(out), R, L, hop, s0, nseg, _stream(wave)), "m2h_sep_frames_hop")
-    return out
-
-
-def sep_istft_xfade(frames, window, xwin, y, hop, s0, nseg):
+def sep_istft_xfade(frames, window, xwin, y, hop, s0, nseg, origin=0, end=None):
     """The inverse GEMM's rows [nseg*R*32, 1024] of the overlapped segments [s0, s0+nseg) -> their windowed overlap-add, weighted with
-    xwin / (the sum of xwin over every segment of the recording that covers the sample) and added into y [R, L]
-    (m2h_sep_istft_xfade).  The chunks of a recording are called in ascending order; y needs no clearing.  window: periodic
-    Hann(1022); xwin: the [16000] cross-fade window, strictly positive."""
+    xwin / (the sum of xwin over every segment of the recording that covers the sample) and added into y [R, cap].  The chunks of a
+    recording are called in ascending order; y needs no clearing.  window: periodic Hann(1022); xwin: the [16000] cross-fade window,
+    strictly positive.  y is the whole recording (m2h_sep_istft_xfade) or, with `end`, the window [origin, origin + cap) of a recording
+    of which `end` samples have arrived; it keeps, between calls, the partial sums of the samples that later segments still cover
+    (m2h_sep_istft_xfade_win)."""
     _chk(frames, "sep_istft_xfade(frames)")
     _chk(window, "sep_istft_xfade(window)")
     _chk(xwin, "sep_istft_xfade(xwin)")
     _chk(y, "sep_istft_xfade(y)")
-    if y.dim() != 2:
-        raise RuntimeError("m2h.sep_istft_xfade: y must be [R, L], got %s" % (tuple(y.shape),))
-    R, L = y.shape
-    _sep_chunk_hop("sep_istft_xfade", R, L, hop, s0, nseg)
+    if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
+        raise RuntimeError("m2h.sep_istft_xfade: y must be [R, L] or a window [R, cap], got %s" % (tuple(y.shape),))
+    R, cap = y.shape
+    origin, end, whole = _sep_window("sep_istft_xfade", cap, hop, s0, nseg, origin, end)
     if tuple(frames.shape) != (nseg * R * SEP_FRAMES, SEP_LD) or window.numel() < 1022 or xwin.numel() != SEP_SEGMENT:
         raise RuntimeError("m2h.sep_istft_xfade: expected frames [%d, %d], a 1022-point window and a %d-point cross-fade window, got %s, %d and %d points"
                            % (nseg * R * SEP_FRAMES, SEP_LD, SEP_SEGMENT, tuple(frames.shape), window.numel(), xwin.numel()))
+    lib = _lib.load()
     with torch.cuda.device(y.device):
-        _lib.check(_lib.load().m2h_sep_istft_xfade(_ptr(frames), _ptr(window), _ptr(xwin), _ptr(y), R, L, hop, s0, nseg, _stream(y)), "m2h_sep_istft_xfade")
+        if whole:
+            _lib.check(lib.m2h_sep_istft_xfade(_ptr(frames), _ptr(window), _ptr(xwin), _ptr(y), R, cap, hop, s0, nseg, _stream(y)), "m2h_sep_istft_xfade")
+        else:
+            _lib.check(lib.m2h_sep_istft_xfade_win(_ptr(frames), _ptr(window), _ptr(xwin), _ptr(y), R, cap, origin, end, int(hop), int(s0), int(nseg), _stream(y)),
+                       "m2h_sep_istft_xfade_win")
     return y
 
 
@@ -1255,113 +1251,42 @@ def sep_istft_xfade(frames, window, xwin, y, hop, s0, nseg):
 RESAMPLE_MAX_RATIO = 1024
 
 
-def resample_poly(x, G, up, down, out=None):
-    """x [rows, L_in] -> [rows, ceil(L_in * up / down)]: the polyphase FIR of m2h_resample_poly over every row, one launch.
-    G: the [up, T] table of the ratio up / down (m2h.audio.resample.polyphase_table of design()'s taps)."""
+def resample_poly(x, G, up, down, out=None, origin=0, end=None, n_first=0, count=None):
+    """The polyphase FIR of csrc/resample.hip over every row, one launch.  G: the [up, T] table of the ratio up / down
+    (m2h.audio.resample.polyphase_table of design()'s taps).  x [rows, L_in] is the whole of every row -> [rows, ceil(L_in * up / down)]
+    (m2h_resample_poly); or, with `end`, x [rows, cap] is the window [origin, origin + cap) of rows of which `end` samples have
+    arrived -> the outputs [n_first, n_first + count) of the same definition, [rows, count], bit-identical to those of one call over
+    the whole rows (m2h_resample_poly_win; the library refuses, before any launch, outputs that read outside the window)."""
     _chk(x, "resample_poly(x)")
     _chk(G, "resample_poly(G)")
     up, down = int(up), int(down)
     if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise RuntimeError("m2h.resample_poly: expected rows of samples [rows, L] with L >= 1, got %s" % (tuple(x.shape),))
+        raise RuntimeError("m2h.resample_poly: expected rows of samples [rows, L] or a window [rows, cap], L and cap >= 1, got %s" % (tuple(x.shape),))
     if up < 1 or down < 1 or G.dim() != 2 or G.shape[0] != up:
         raise RuntimeError("m2h.resample_poly: expected a [up, T] table for the ratio %d/%d, got %s" % (up, down, tuple(G.shape)))
     if G.device != x.device:
         raise RuntimeError("m2h.resample_poly: the table lives on %s, x on %s" % (G.device, x.device))
-    rows, L_in = x.shape
-    L_out = -(-L_in * up // down)
-    if out is None:
-        out = torch.empty((rows, L_out), device=x.device, dtype=torch.float32)
-    else:
-        _chk(out, "resample_poly(out)")
-        if tuple(out.shape) != (rows, L_out) or out.device != x.device:
-            raise RuntimeError("m2h.resample_poly: out must be [%d, %d] on %s, got %s on %s" % (rows, L_out, x.device, tuple(out.shape), out.device))
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().m2h_resample_poly(_ptr(x), _ptr(G), _ptr(out), rows, L_in, L_out, up, down, G.shape[1], _stream(x)), "m2h_resample_poly")
-    return out
-
-
-# ---- window forms for a recording that arrives block by block (include/m2h.h, "Window forms"; m2h/separate.py: SeparatorStream) ----
-def sep_frames_win(buf, window, origin, end, hop, s0, nseg, out=None):
-    """sep_frames_hop's rows for segments [s0, s0+nseg) from a window: buf [R, 2, cap] holds the absolute samples [origin, origin + cap)
-    of a recording of which `end` samples have arrived; samples at or past end are zero (m2h_sep_frames_win).  The library refuses a
-    call whose reads would leave the window."""
-    _chk(buf, "sep_frames_win(buf)")
-    _chk(window, "sep_frames_win(window)")
-    if buf.dim() != 3 or buf.shape[1] != 2 or buf.shape[0] < 1 or buf.shape[2] < 1:
-        raise RuntimeError("m2h.sep_frames_win: expected a [R, 2, cap] window, got %s" % (tuple(buf.shape),))
-    if window.numel() != SEP_LD:
-        raise RuntimeError("m2h.sep_frames_win: window must hold %d floats, got %d" % (SEP_LD, window.numel()))
-    R, _, cap = buf.shape
-    rows = max(int(nseg), 0) * R * 2 * SEP_FRAMES
-    if out is None:
-        out = torch.empty((rows, SEP_LD), device=buf.device, dtype=torch.float32)
-    else:
-        _chk(out, "sep_frames_win(out)")
-        if tuple(out.shape) != (rows, SEP_LD):
-            raise RuntimeError("m2h.sep_frames_win: out must be [%d, %d], got %s" % (rows, SEP_LD, tuple(out.shape)))
-    with torch.cuda.device(buf.device):
-        _lib.check(_lib.load().m2h_sep_frames_win(_ptr(buf), _ptr(window), _ptr(out), R, cap, int(origin), int(end), int(hop), int(s0), int(nseg), _stream(buf)),
-                   "m2h_sep_frames_win")
-    return out
-
-
-def sep_istft_ola_win(frames, window, y, origin, end, s0, nseg):
-    """sep_istft_ola into a window: y [R, cap] holds the absolute samples [origin, origin + cap), cut at end (m2h_sep_istft_ola_win)."""
-    _chk(frames, "sep_istft_ola_win(frames)")
-    _chk(window, "sep_istft_ola_win(window)")
-    _chk(y, "sep_istft_ola_win(y)")
-    if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
-        raise RuntimeError("m2h.sep_istft_ola_win: y must be [R, cap], got %s" % (tuple(y.shape),))
-    R, cap = y.shape
-    if tuple(frames.shape) != (nseg * R * SEP_FRAMES, SEP_LD) or window.numel() < 1022:
-        raise RuntimeError("m2h.sep_istft_ola_win: expected frames [%d, %d] and a 1022-point window, got %s and %d points"
-                           % (nseg * R * SEP_FRAMES, SEP_LD, tuple(frames.shape), window.numel()))
-    with torch.cuda.device(y.device):
-        _lib.check(_lib.load().m2h_sep_istft_ola_win(_ptr(frames), _ptr(window), _ptr(y), R, cap, int(origin), int(end), int(s0), int(nseg), _stream(y)),
-                   "m2h_sep_istft_ola_win")
-    return y
-
-
-def sep_istft_xfade_win(frames, window, xwin, y, origin, end, hop, s0, nseg):
-    """sep_istft_xfade into a window: y [R, cap] holds the absolute samples [origin, origin + cap) and keeps, between calls, the partial
-    sums of the samples that later segments still cover (m2h_sep_istft_xfade_win)."""
-    _chk(frames, "sep_istft_xfade_win(frames)")
-    _chk(window, "sep_istft_xfade_win(window)")
-    _chk(xwin, "sep_istft_xfade_win(xwin)")
-    _chk(y, "sep_istft_xfade_win(y)")
-    if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
-        raise RuntimeError("m2h.sep_istft_xfade_win: y must be [R, cap], got %s" % (tuple(y.shape),))
-    R, cap = y.shape
-    if tuple(frames.shape) != (nseg * R * SEP_FRAMES, SEP_LD) or window.numel() < 1022 or xwin.numel() != SEP_SEGMENT:
-        raise RuntimeError("m2h.sep_istft_xfade_win: expected frames [%d, %d], a 1022-point window and a %d-point cross-fade window, got %s, %d and %d points"
-                           % (nseg * R * SEP_FRAMES, SEP_LD, SEP_SEGMENT, tuple(frames.shape), window.numel(), xwin.numel()))
-    with torch.cuda.device(y.device):
-        _lib.check(_lib.load().m2h_sep_istft_xfade_win(_ptr(frames), _ptr(window), _ptr(xwin), _ptr(y), R, cap, int(origin), int(end), int(hop), int(s0),
-                                                       int(nseg), _stream(y)), "m2h_sep_istft_xfade_win")
-    return y
-
-
-def resample_poly_win(x, G, up, down, origin, end, n_first, count, out=None):
-    """Outputs [n_first, n_first + count) of resample_poly's definition, [rows, count], from the window x [rows, cap] that holds the
-    absolute samples [origin, origin + cap) of rows of which `end` samples have arrived (m2h_resample_poly_win).  Bit-identical to the
-    same outputs of one resample_poly call over the whole rows."""
-    _chk(x, "resample_poly_win(x)")
-    _chk(G, "resample_poly_win(G)")
-    up, down, count = int(up), int(down), int(count)
-    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise RuntimeError("m2h.resample_poly_win: expected a window [rows, cap] with cap >= 1, got %s" % (tuple(x.shape),))
-    if up < 1 or down < 1 or G.dim() != 2 or G.shape[0] != up:
-        raise RuntimeError("m2h.resample_poly_win: expected a [up, T] table for the ratio %d/%d, got %s" % (up, down, tuple(G.shape)))
-    if G.device != x.device:
-        raise RuntimeError("m2h.resample_poly_win: the table lives on %s, x on %s" % (G.device, x.device))
     rows, cap = x.shape
+    if end is None:
+        if origin or n_first or count is not None:
+            raise RuntimeError("m2h.resample_poly: origin, n_first and count need the window's end")
+        count = -(-cap * up // down)
+    elif count is None:
+        raise RuntimeError("m2h.resample_poly: a window needs the count of outputs")
+    count = int(count)
     if out is None:
         out = torch.empty((rows, max(count, 0)), device=x.device, dtype=torch.float32)
     else:
-        _chk(out, "resample_poly_win(out)")
+        _chk(out, "resample_poly(out)")
         if tuple(out.shape) != (rows, count) or out.device != x.device:
-            raise RuntimeError("m2h.resample_poly_win: out must be [%d, %d] on %s, got %s on %s" % (rows, count, x.device, tuple(out.shape), out.device))
+            raise RuntimeError("m2h.resample_poly: out must be [%d, %d] on %s, got %s on %s" % (rows, count, x.device, tuple(out.shape), out.device))
+    lib = _lib.load()
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().m2h_resample_poly_win(_ptr(x), _ptr(G), _ptr(out), rows, cap, int(origin), int(end), int(n_first), count, up, down, G.shape[1],
-                                                     _stream(x)), "m2h_resample_poly_win")
+        if end is None:
+            _lib.check(lib.m2h_resample_poly(_ptr(x), _ptr(G), _ptr(out), rows, cap, count, up, down, G.shape[1], _stream(x)), "m2h_resample_poly")
+        else:
+            _lib.check(lib.m2h_resample_poly_win(_ptr(x), _ptr(G), _ptr(out), rows, cap, int(origin), int(end), int(n_first), count, up, down, G.shape[1],
+                                                 _stream(x)), "m2h_resample_poly_win")
     return out
+
+

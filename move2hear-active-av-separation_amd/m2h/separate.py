@@ -77,8 +77,9 @@ separation for a recording that arrives block by block.  st.push(block [R, 2, n]
   * the memory keeps one state per chain c = s mod overlap, zeros at the start, carried across pushes; the segments that complete in one
     push are one segment-major U-Net batch, split at max_segments rows; several streams of one Separator do not disturb each other;
   * the input and the cross-fade's partial sums live in windows [rows][cap] of absolute samples [origin, origin + cap) read and written
-    by the window forms of the glue kernels (m2h_sep_frames_win, m2h_sep_istft_ola_win, m2h_sep_istft_xfade_win, m2h_resample_poly_win:
-    the offline kernels' arithmetic, bit for bit); a push costs O(block + one second).  return_spectrograms is not offered.
+    by the window entry points of the glue kernels (m2h_sep_frames_win, m2h_sep_istft_ola_win, m2h_sep_istft_xfade_win,
+    m2h_resample_poly_win: the offline kernels themselves, a recording being the window that holds all of it); a push costs
+    O(block + one second).  return_spectrograms is not offered.
 
 The two DFTs are dense 1024 x 1024 GEMMs (ops.linear) and follow the calling thread's arithmetic like the U-Nets; framing, the
 magnitude / phasor store, the inverse transform's operand and the overlap-add are the HIP kernels of csrc/separate.hip, which
@@ -222,6 +223,113 @@ class Separator:
             self._resamplers[key] = (Resampler(key, SAMPLE_RATE, self.device), Resampler(SAMPLE_RATE, key, self.device))
         return self._resamplers[key]
 
+    def _arguments(self, use_memory, overlap, output, recordings=1):
+        """separate()'s and stream()'s checks of what they share, before anything else is looked at -> (use_memory, want_mono, want_bin)."""
+        if isinstance(overlap, bool) or overlap not in OVERLAPS:
+            raise ValueError("m2h.Separator: overlap must be one of %s, got %r" % (OVERLAPS, overlap))
+        if not isinstance(output, str) or output not in OUTPUTS:
+            raise ValueError("m2h.Separator: output must be one of %s, got %r" % (OUTPUTS, output))
+        want_mono, want_bin = output != "binaural", output != "mono"
+        if not want_mono and use_memory:
+            raise ValueError("m2h.Separator: output=\"binaural\" runs no acoustic memory (it refines the mono prediction only); "
+                             "leave use_memory at None or False, or ask for output=\"both\"")
+        if isinstance(recordings, bool) or int(recordings) != recordings or recordings < 1:
+            raise ValueError("m2h.Separator: recordings must be a positive int, got %r" % (recordings,))
+        if use_memory is None:
+            use_memory = want_mono and self.memory is not None
+        if use_memory and self.memory is None:
+            raise RuntimeError("m2h.Separator: use_memory=True, but the checkpoint has no acoustic_mem.cnn.* weights")
+        return bool(use_memory), want_mono, want_bin
+
+    def _target_classes(self, target_class, R):
+        """One class per recording, [R] int64 on the device, from one int or R of them."""
+        tc = torch.as_tensor(target_class, dtype=torch.int64).reshape(-1)
+        if tc.numel() == 1:
+            tc = tc.expand(R)
+        if tc.numel() != R:
+            raise RuntimeError("m2h.Separator: target_class must be one int or one per recording (%d), got %d values" % (R, tc.numel()))
+        return tc.to(self.device).contiguous()
+
+    def _xfade_window(self):
+        if self._win_xfade is None:
+            self._win_xfade = torch.from_numpy(crossfade_window()).to(self.device)
+        return self._win_xfade
+
+    def _memory_steps(self, P, c0, cn, R, k, states):
+        """The memory over the rows P of segments [c0, c0 + cn), k interleaved chains: segment s belongs to chain s mod k and its predecessor
+        is segment s - k, so one step is up to k consecutive segments, one per chain, and one memory call.  states[c] = (rows, i): chain
+        c's state is rows[i * R:(i + 1) * R] of an earlier step's output; None, zeros, at the start.  Updated in place."""
+        steps = []
+        with self._memory_scope(k * R):
+            for sl in range(0, cn, k):
+                n = min(k, cn - sl)
+                pm = P[sl * R:(sl + n) * R]
+                st = [states[(c0 + sl + i) % k] for i in range(n)]
+                if all(s is None for s in st):
+                    prev = torch.zeros_like(pm)
+                elif all(s is not None and s[0] is st[0][0] and s[1] == i for i, s in enumerate(st)):
+                    prev = st[0][0][:n * R]      # one earlier step wrote these chains in this order (always so in a file): its rows as they are
+                else:
+                    prev = torch.cat([torch.zeros_like(pm[:R]) if s is None else s[0][s[1] * R:(s[1] + 1) * R] for s in st])
+                out = self.memory(pm, prev)
+                for i in range(n):
+                    states[(c0 + sl + i) % k] = (out, i)
+                steps.append(out)
+        return torch.cat(steps) if len(steps) > 1 else steps[0]
+
+    def _chunk(self, c0, cn, hop, tc, source, sinks, states=None, keep=None):
+        """Segments [c0, c0 + cn) at `hop` as one U-Net batch: frames, DFT, the U-Nets, the memory, inverse DFT, overlap-add or cross-fade.
+        source = (buf [R, 2, cap], origin, end): the absolute samples [origin, origin + cap) of a recording of which `end` have arrived;
+        sinks = (mono rows [R, cap'] or None, binaural rows [2R, cap'] or None, origin, end) likewise.  end = None: the whole recording
+        (ops.sep_frames).  states: the memory's per-chain states (_memory_steps), None to run without it.  keep: three lists that take
+        the chunk's P, phasor and masks."""
+        buf, origin, end = source
+        y, yb, y_origin, y_end = sinks
+        R = buf.shape[0]
+
+        def place(out_frames, rows):
+            if hop == SEGMENT:
+                ops.sep_istft_ola(out_frames, self._win_inv, rows, c0, cn, origin=y_origin, end=y_end)
+            else:
+                ops.sep_istft_xfade(out_frames, self._win_inv, self._xfade_window(), rows, hop, c0, cn, origin=y_origin, end=y_end)
+
+        frames = ops.sep_frames(buf, self._win_fwd, c0, cn, hop=hop, origin=origin, end=end)
+        spec = ops.linear(frames, self._W_fwd, None, name="separate.dft")
+        mag, phasor = ops.sep_stft_post(spec, cn * R)
+        del frames
+        if yb is None:
+            del spec
+        self._mark("stft")
+        masks = self.policy.get_binSepMasks({"mixed_bin_audio_mag": mag, "target_class": tc.repeat(cn)})
+        if yb is not None:
+            # finished before the second U-Net: the spectrum buffer is not held alongside that U-Net's activations.
+            # The inverse GEMM's rows are those of 2R mono recordings: ((sl*R + r)*2 + c)*32 + t = ((sl*2R + (2r + c))*32 + t.
+            self._mark("unets")
+            masks = masks.contiguous()
+            rows = ops.sep_bin_rows(spec, masks)
+            del spec
+            out_frames = ops.linear(rows, self._W_inv, None, name="separate.idft")
+            del rows
+            place(out_frames, yb)
+            del out_frames
+            self._mark("istft_bin")
+            if keep is not None:
+                keep[2].append(masks.reshape(cn, R, ops.SEP_BINS, ops.SEP_FRAMES, 2))
+            if y is None:
+                return
+        P = self.policy.convert_bin2mono(masks, mixed_audio=mag)
+        self._mark("unets")
+        if states is not None:
+            P = self._memory_steps(P, c0, cn, R, SEGMENT // hop, states)
+            self._mark("memory")
+        rows = ops.sep_istft_pre(P, phasor)
+        out_frames = ops.linear(rows, self._W_inv, None, name="separate.idft")
+        place(out_frames, y)
+        self._mark("istft")
+        if keep is not None:
+            keep[0].append(P.reshape(cn, R, ops.SEP_BINS, ops.SEP_FRAMES))
+            keep[1].append(phasor.reshape(cn, R, ops.SEP_BINS, ops.SEP_FRAMES, 2))
+
     @torch.no_grad()
     def separate(self, wave, target_class, use_memory=None, return_spectrograms=False, sample_rate=SAMPLE_RATE, overlap=1, output="mono"):
         """wave [R, 2, L] or [2, L] fp32 on this separator's device, L >= 1; target_class: an int or one per recording.
@@ -234,15 +342,8 @@ class Separator:
         ears [R, 2, L] ([2, L] for a [2, L] input), with return_spectrograms also the first U-Net's masks [R, S, 512, 32, 2]; it runs
         no memory, and use_memory=True given with it is a ValueError.  "both" returns (mono, binaural), with return_spectrograms
         (mono, binaural, P, phasor, masks); its mono is the "mono" call's bit for bit."""
-        if isinstance(overlap, bool) or overlap not in OVERLAPS:
-            raise ValueError("m2h.Separator: overlap must be one of %s, got %r" % (OVERLAPS, overlap))
+        use_memory, want_mono, want_bin = self._arguments(use_memory, overlap, output)
         overlap = int(overlap)
-        if not isinstance(output, str) or output not in OUTPUTS:
-            raise ValueError("m2h.Separator: output must be one of %s, got %r" % (OUTPUTS, output))
-        want_mono, want_bin = output != "binaural", output != "mono"
-        if not want_mono and use_memory:
-            raise ValueError("m2h.Separator: output=\"binaural\" runs no acoustic memory (it refines the mono prediction only); "
-                             "leave use_memory at None or False, or ask for output=\"both\"")
         if not torch.is_tensor(wave):
             raise RuntimeError("m2h.Separator: wave must be a torch tensor, got %s" % type(wave).__name__)
         single = wave.dim() == 2
@@ -254,10 +355,7 @@ class Separator:
             raise RuntimeError("m2h.Separator: wave must be float32, got %s" % wave.dtype)
         if wave.device != self.device:
             raise RuntimeError("m2h.Separator: wave lives on %s, the separator on %s" % (wave.device, self.device))
-        if use_memory is None:
-            use_memory = want_mono and self.memory is not None
-        if use_memory and self.memory is None:
-            raise RuntimeError("m2h.Separator: use_memory=True, but the checkpoint has no acoustic_mem.cnn.* weights")
+        tc = self._target_classes(target_class, wave.shape[0])
         wave = wave.contiguous()
         to16 = back = None
         if sample_rate != SAMPLE_RATE:
@@ -269,78 +367,17 @@ class Separator:
                 wave = to16(wave)
                 self._mark("resample_in")
         R, _, L = wave.shape
-        tc = torch.as_tensor(target_class, dtype=torch.int64).reshape(-1)
-        if tc.numel() == 1:
-            tc = tc.expand(R)
-        if tc.numel() != R:
-            raise RuntimeError("m2h.Separator: target_class must be one int or one per recording (%d), got %d values" % (R, tc.numel()))
-        tc = tc.to(self.device).contiguous()
         y = torch.empty((R, L), device=self.device, dtype=torch.float32) if want_mono else None
         yb = torch.empty((R, 2, L), device=self.device, dtype=torch.float32) if want_bin else None
-        keep_P, keep_ph, keep_m = [], [], []
-        prev = None
-        hop = SEGMENT // overlap
-        if overlap > 1 and self._win_xfade is None:
-            self._win_xfade = torch.from_numpy(crossfade_window()).to(self.device)
+        keep = ([], [], []) if return_spectrograms else None
+        states = [None] * overlap
         with torch.cuda.device(self.device), ops.math_scope(self.math):
             if to16 is None:
                 self._mark("start")
+            # the recording itself is the source window and the outputs themselves the sinks (end = None: the whole of it)
             for s0, ns in overlap_plan(L, overlap, max(1, self.max_segments // R)):
-                N = ns * R
-                if overlap == 1:
-                    frames = ops.sep_frames(wave, self._win_fwd, s0, ns)
-                else:
-                    frames = ops.sep_frames_hop(wave, self._win_fwd, hop, s0, ns)
-                spec = ops.linear(frames, self._W_fwd, None, name="separate.dft")
-                mag, phasor = ops.sep_stft_post(spec, N)
-                del frames
-                if not want_bin:
-                    del spec
-                self._mark("stft")
-                obs = {"mixed_bin_audio_mag": mag, "target_class": tc.repeat(ns)}
-                masks = self.policy.get_binSepMasks(obs)
-                if want_bin:
-                    # finished before the second U-Net: the spectrum buffer is not held alongside that U-Net's activations.
-                    # The inverse GEMM's rows are those of 2R mono recordings: ((sl*R + r)*2 + c)*32 + t = ((sl*2R + (2r + c))*32 + t.
-                    self._mark("unets")
-                    masks = masks.contiguous()
-                    rows = ops.sep_bin_rows(spec, masks)
-                    del spec
-                    out_frames = ops.linear(rows, self._W_inv, None, name="separate.idft")
-                    del rows
-                    if overlap == 1:
-                        ops.sep_istft_ola(out_frames, self._win_inv, yb.view(2 * R, L), s0, ns)
-                    else:
-                        ops.sep_istft_xfade(out_frames, self._win_inv, self._win_xfade, yb.view(2 * R, L), hop, s0, ns)
-                    del out_frames
-                    self._mark("istft_bin")
-                    if return_spectrograms:
-                        keep_m.append(masks.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES, 2))
-                    if not want_mono:
-                        continue
-                P = self.policy.convert_bin2mono(masks, mixed_audio=mag)
-                self._mark("unets")
-                if use_memory:
-                    steps = []
-                    with self._memory_scope(overlap * R):
-                        # one step = the `overlap` segments of one second, one per chain; a chunk starts at a multiple of `overlap`,
-                        # and only the recording's last step may hold fewer chains
-                        for sl in range(0, ns, overlap):
-                            pm = P[sl * R:min(sl + overlap, ns) * R]
-                            prev = self.memory(pm, prev[:pm.shape[0]] if prev is not None else torch.zeros_like(pm))
-                            steps.append(prev)
-                    P = torch.cat(steps) if len(steps) > 1 else steps[0]
-                    self._mark("memory")
-                rows = ops.sep_istft_pre(P, phasor)
-                out_frames = ops.linear(rows, self._W_inv, None, name="separate.idft")
-                if overlap == 1:
-                    ops.sep_istft_ola(out_frames, self._win_inv, y, s0, ns)
-                else:
-                    ops.sep_istft_xfade(out_frames, self._win_inv, self._win_xfade, y, hop, s0, ns)
-                self._mark("istft")
-                if return_spectrograms:
-                    keep_P.append(P.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES))
-                    keep_ph.append(phasor.reshape(ns, R, ops.SEP_BINS, ops.SEP_FRAMES, 2))
+                self._chunk(s0, ns, SEGMENT // overlap, tc, (wave, 0, None), (y, yb.view(2 * R, L) if want_bin else None, 0, None),
+                            states if use_memory else None, keep)
             if back is not None:
                 if want_mono:
                     y = back(y)[:, :L_given].contiguous()      # ceil(ceil(L a / b) b / a) >= L: never short
@@ -350,9 +387,9 @@ class Separator:
         res = ((y,) if want_mono else ()) + ((yb,) if want_bin else ())
         if return_spectrograms:
             if want_mono:
-                res += (torch.cat(keep_P).transpose(0, 1).contiguous(), torch.cat(keep_ph).transpose(0, 1).contiguous())
+                res += (torch.cat(keep[0]).transpose(0, 1).contiguous(), torch.cat(keep[1]).transpose(0, 1).contiguous())
             if want_bin:
-                res += (torch.cat(keep_m).transpose(0, 1).contiguous(),)
+                res += (torch.cat(keep[2]).transpose(0, 1).contiguous(),)
         if single:
             res = tuple(a[0] for a in res)
         return res[0] if len(res) == 1 else res
@@ -392,36 +429,16 @@ class SeparatorStream:
 
     def __init__(self, sep, target_class, recordings, use_memory=None, sample_rate=SAMPLE_RATE, overlap=1, output="mono"):
         from .audio.resample import SampleWindow
-        if isinstance(overlap, bool) or overlap not in OVERLAPS:
-            raise ValueError("m2h.Separator: overlap must be one of %s, got %r" % (OVERLAPS, overlap))
-        if not isinstance(output, str) or output not in OUTPUTS:
-            raise ValueError("m2h.Separator: output must be one of %s, got %r" % (OUTPUTS, output))
-        self.want_mono, self.want_bin = output != "binaural", output != "mono"
-        if not self.want_mono and use_memory:
-            raise ValueError("m2h.Separator: output=\"binaural\" runs no acoustic memory (it refines the mono prediction only); "
-                             "leave use_memory at None or False, or ask for output=\"both\"")
-        if isinstance(recordings, bool) or int(recordings) != recordings or recordings < 1:
-            raise ValueError("m2h.Separator: recordings must be a positive int, got %r" % (recordings,))
-        if use_memory is None:
-            use_memory = self.want_mono and sep.memory is not None
-        if use_memory and sep.memory is None:
-            raise RuntimeError("m2h.Separator: use_memory=True, but the checkpoint has no acoustic_mem.cnn.* weights")
-        self.sep, self.R, self.overlap, self.hop, self.use_memory = sep, int(recordings), int(overlap), SEGMENT // int(overlap), bool(use_memory)
+        self.use_memory, self.want_mono, self.want_bin = sep._arguments(use_memory, overlap, output, recordings)
+        self.sep, self.R, self.overlap, self.hop = sep, int(recordings), int(overlap), SEGMENT // int(overlap)
         R, dev = self.R, sep.device
-        tc = torch.as_tensor(target_class, dtype=torch.int64).reshape(-1)
-        if tc.numel() == 1:
-            tc = tc.expand(R)
-        if tc.numel() != R:
-            raise RuntimeError("m2h.Separator: target_class must be one int or one per recording (%d), got %d values" % (R, tc.numel()))
-        self.tc = tc.to(dev).contiguous()
+        self.tc = sep._target_classes(target_class, R)
         self.to16 = self.back_mono = self.back_bin = None
         if sample_rate != SAMPLE_RATE:
             to16, back = sep.resamplers(sample_rate)
             self.to16 = to16.stream((R, 2))
             self.back_mono = back.stream((R,)) if self.want_mono else None
             self.back_bin = back.stream((R, 2)) if self.want_bin else None
-        if self.overlap > 1 and sep._win_xfade is None:
-            sep._win_xfade = torch.from_numpy(crossfade_window()).to(dev)
         self.win_in = SampleWindow((R, 2), dev)
         self.win_mono = SampleWindow((R,), dev) if self.want_mono and self.overlap > 1 else None
         self.win_bin = SampleWindow((R, 2), dev) if self.want_bin and self.overlap > 1 else None
@@ -444,29 +461,6 @@ class SeparatorStream:
         dev = self.sep.device
         return ((torch.empty((self.R, 0), device=dev),) if self.want_mono else ()) + ((torch.empty((self.R, 2, 0), device=dev),) if self.want_bin else ())
 
-    def _memory(self, P, c0, cn):
-        """The memory over the rows of segments [c0, c0 + cn): up to `overlap` consecutive segments -- one per chain -- per call, each on its
-        own chain's state."""
-        R, k, mem = self.R, self.overlap, self.sep.memory
-        steps = []
-        with self.sep._memory_scope(k * R):
-            for sl in range(0, cn, k):
-                segs = range(c0 + sl, c0 + min(sl + k, cn))
-                pm = P[sl * R:(sl + len(segs)) * R]
-                prev = [self.states[s % k] if self.states[s % k] is not None else torch.zeros_like(pm[:R]) for s in segs]
-                out = mem(pm, prev[0] if len(prev) == 1 else torch.cat(prev))
-                for i, s in enumerate(segs):
-                    self.states[s % k] = out[i * R:(i + 1) * R]
-                steps.append(out)
-        return torch.cat(steps) if len(steps) > 1 else steps[0]
-
-    def _write(self, out_frames, win, y, rows, origin, end, c0, cn):
-        sep = self.sep
-        if self.overlap == 1:
-            ops.sep_istft_ola_win(out_frames, sep._win_inv, y.view(rows, -1), origin, end, c0, cn)
-        else:
-            ops.sep_istft_xfade_win(out_frames, sep._win_inv, sep._win_xfade, win.buf.view(rows, win.cap), origin, end, self.hop, c0, cn)
-
     def _core(self, block, final):
         """One block [R, 2, n] at 16 kHz -> the samples that became final, as a tuple (mono?, binaural?)."""
         sep, R, k, H = self.sep, self.R, self.overlap, self.hop
@@ -482,40 +476,18 @@ class SeparatorStream:
         stop = min(end, (s1 + ns - 1) * H + SEGMENT)                 # the samples these segments cover: [origin, stop)
         m = (stop if final else (s1 + ns) * H) - origin              # of which final
         y = yb = None
-        if k == 1:
+        if k == 1:                                                   # written straight into the returned tensors, the window [origin, origin + m)
             y = torch.empty((R, m), device=sep.device, dtype=torch.float32) if self.want_mono else None
             yb = torch.empty((R, 2, m), device=sep.device, dtype=torch.float32) if self.want_bin else None
-        else:
+            sinks = (y, yb.view(2 * R, m) if yb is not None else None, origin, end)
+        else:                                                        # added onto the partial sums
             for w in (self.win_mono, self.win_bin):
                 if w is not None:
                     w.advance(origin, extra=stop - origin - w.fill)
+            sinks = (self.win_mono.buf.view(R, -1) if self.want_mono else None, self.win_bin.buf.view(2 * R, -1) if self.want_bin else None, origin, end)
         per = max(1, sep.max_segments // R)
         for c0 in range(s1, s1 + ns, per):
-            cn = min(per, s1 + ns - c0)
-            N = cn * R
-            frames = ops.sep_frames_win(self.win_in.buf, sep._win_fwd, self.win_in.origin, end, H, c0, cn)
-            spec = ops.linear(frames, sep._W_fwd, None, name="separate.dft")
-            mag, phasor = ops.sep_stft_post(spec, N)
-            del frames
-            if not self.want_bin:
-                del spec
-            masks = sep.policy.get_binSepMasks({"mixed_bin_audio_mag": mag, "target_class": self.tc.repeat(cn)})
-            if self.want_bin:
-                masks = masks.contiguous()
-                rows = ops.sep_bin_rows(spec, masks)
-                del spec
-                out_frames = ops.linear(rows, sep._W_inv, None, name="separate.idft")
-                del rows
-                self._write(out_frames, self.win_bin, yb, 2 * R, origin, end, c0, cn)
-                del out_frames
-                if not self.want_mono:
-                    continue
-            P = sep.policy.convert_bin2mono(masks, mixed_audio=mag)
-            if self.use_memory:
-                P = self._memory(P, c0, cn)
-            rows = ops.sep_istft_pre(P, phasor)
-            out_frames = ops.linear(rows, sep._W_inv, None, name="separate.idft")
-            self._write(out_frames, self.win_mono, y, R, origin, end, c0, cn)
+            sep._chunk(c0, min(per, s1 + ns - c0), H, self.tc, (self.win_in.buf, self.win_in.origin, end), sinks, self.states if self.use_memory else None)
         self.next_seg = s1 + ns
         if k > 1:
             res = ()

@@ -68,7 +68,7 @@ def test_frames_with_a_hop_match_np_stft_of_the_shifted_recordings(dev, transfor
     parts = []
     assert sum(ns for _, ns in calls) == S
     for s0, ns in calls:
-        frames = ops.sep_frames_hop(w, win, hop, s0, ns)
+        frames = ops.sep_frames(w, win, s0, ns, hop=hop)
         spec = ops.linear(frames, Wf, None, name="test.dft")
         parts.append(ops.sep_stft_post(spec, ns * R))
     mag = torch.cat([p[0] for p in parts]).cpu().numpy().reshape(S, R, 512, 32, 2)

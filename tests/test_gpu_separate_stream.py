@@ -3,7 +3,7 @@ csrc/resample.hip) against the one-call path on the same recording -- no other o
 m2h/separate.py and checked by tests/test_gpu_separate*.py.
 
 Bit for bit wherever the stream runs the same rows through the same kernels (the rate conversion for any blocking, the window kernels,
-overlap 1 with one segment per push against max_segments = R).  Where the blocking changes the U-Nets' batch size the bound is the
+overlap 1 with one segment per push against max_segments = R, overlap 2 and 4 with the pushes that complete overlap_plan's chunks).  Where the blocking changes the U-Nets' batch size the bound is the
 existing one for "the same rows at another batch size" (tests/test_gpu_separate.py): 2e-5 on P, times 2.5, plus 5e-5 = 1e-4 on the
 waveform in fp32, and the project's 1e-3 parity contract in bf16x3.  Weights and inputs as tests/test_gpu_separate.py.
 Measured on MI355X: DESIGN.md section 8.4.
@@ -123,17 +123,17 @@ def test_frames_from_a_window(dev, transforms):
     wave = _wave(R, L, 21)
     buf = torch.full((R, 2, cap), float("nan"), device=dev)
     buf[:, :, :L - origin] = wave[:, :, origin:]
-    want = ops.sep_frames_hop(wave, win, hop, 2, 5)                      # segments 2 .. 6, the last one cut after one sample
-    got = ops.sep_frames_win(buf, win, origin, L, hop, 2, 5)
+    want = ops.sep_frames(wave, win, 2, 5, hop=hop)                      # segments 2 .. 6, the last one cut after one sample
+    got = ops.sep_frames(buf, win, 2, 5, hop=hop, origin=origin, end=L)
     assert ops.last_kernel() == "sep_frames_win"
     assert torch.isfinite(got).all() and torch.equal(got, want)
     # an earlier `end`: the samples from there on are zero, as in a recording that ends there
-    short = ops.sep_frames_win(buf, win, origin, 20001, hop, 2, 4)
-    assert torch.equal(short, ops.sep_frames_hop(wave[:, :, :20001].contiguous(), win, hop, 2, 4))
+    short = ops.sep_frames(buf, win, 2, 4, hop=hop, origin=origin, end=20001)
+    assert torch.equal(short, ops.sep_frames(wave[:, :, :20001].contiguous(), win, 2, 4, hop=hop))
     lib = _lib.load()
     n0 = lib.m2h_launch_count()
     with pytest.raises(RuntimeError, match="leave the window"):
-        ops.sep_frames_win(buf, win, origin, L, hop, 1, 2)               # segment 1 starts at 4000, before the window
+        ops.sep_frames(buf, win, 1, 2, hop=hop, origin=origin, end=L)    # segment 1 starts at 4000, before the window
     assert lib.m2h_launch_count() == n0
 
 
@@ -160,9 +160,9 @@ def test_inverse_into_a_sliding_window(dev, transforms, L, k):
             moved[:, :cap - H] = y[:, H:]
             y = moved
         if k == 1:
-            ops.sep_istft_ola_win(frames[s * rows:(s + 1) * rows], win, y, origin, end, s, 1)
+            ops.sep_istft_ola(frames[s * rows:(s + 1) * rows], win, y, s, 1, origin=origin, end=end)
         else:
-            ops.sep_istft_xfade_win(frames[s * rows:(s + 1) * rows], win, xwin, y, origin, end, H, s, 1)
+            ops.sep_istft_xfade(frames[s * rows:(s + 1) * rows], win, xwin, y, H, s, 1, origin=origin, end=end)
         parts.append(y[:, :(H if s < S - 1 else L - origin)].clone())
     got = torch.cat(parts, dim=1)
     assert got.shape == want.shape and torch.isfinite(got).all() and torch.isfinite(want).all()
@@ -209,6 +209,27 @@ def test_any_blocking_with_overlap(dev, overlap, use_memory, math, bound):
     print("stream overlap %d, memory %s, %s: rel-L1 to separate() %.3e" % (overlap, "on" if use_memory else "off", "fp32" if math == ops.MATH_FP32 else "bf16x3", e))
     assert got.shape == (R, L) and torch.isfinite(got).all() and torch.isfinite(want).all()
     assert e < bound
+
+
+@pytest.mark.parametrize("overlap,sizes", [(2, (24000, 16000, 4001)), (4, (28000, 16000, 1))], ids=["k2", "k4"])
+def test_same_batches_with_overlap_are_bit_identical(dev, overlap, sizes):
+    """The pushes and the flush complete segments [0, k), [k, 2k), [2k, 3k): overlap_plan(44001, k, k), the batches separate() runs
+    at max_segments = k * R, through the same chunk method, the same kernels and the same memory steps."""
+    R, L = 2, 44001
+    wave = _wave(R, L, 53)
+    sep = _sep(ops.MATH_FP32, overlap * R)
+    want = sep.separate(wave, TC, use_memory=True, overlap=overlap)
+    st = sep.stream(TC, recordings=R, use_memory=True, overlap=overlap)
+    batches = []
+
+    def check(P, E):
+        assert E == stream_emitted(P, overlap), (P, E)
+        batches.append(st.next_seg)
+
+    (got,) = _run_stream(st, wave, sizes, check)
+    assert batches == [overlap, 2 * overlap, 2 * overlap, 2 * overlap] and st.next_seg == 3 * overlap     # (the last push of _run_stream is empty)
+    assert got.shape == (R, L) and torch.isfinite(got).all()
+    assert torch.equal(got, want)
 
 
 # ---- 5. other sample rates

@@ -65,6 +65,7 @@ def test_entry_points_reject_bad_arguments_without_a_launch():
         ("m2h_sep_frames", (p, p, p, 0, 16000, 0, 1, None), b"sep_frames: bad sizes"),
         ("m2h_sep_frames", (p, p, p, 1, 0, 0, 1, None), b"sep_frames: bad sizes"),
         ("m2h_sep_frames", (p, p, p, 1, 16001, 1, 2, None), b"sep_frames: bad sizes"),          # segments [1, 3) of 2
+        ("m2h_sep_frames", (p, p, p, 1, (1 << 40) + 1, 0, 1, None), b"sep_frames: bad sizes"),  # the window forms' limit, L <= 2^40
         ("m2h_sep_frames", (p, p + 4, p, 1, 16000, 0, 1, None), b"sep_frames: window"),
         ("m2h_sep_stft_post", (p, None, p, 1, None), b"sep_stft_post: null"),
         ("m2h_sep_stft_post", (p, p, p, 0, None), b"sep_stft_post: bad sizes"),
@@ -74,6 +75,7 @@ def test_entry_points_reject_bad_arguments_without_a_launch():
         ("m2h_sep_istft_ola", (p, None, p, 1, 16000, 0, 1, None), b"sep_istft_ola: null"),
         ("m2h_sep_istft_ola", (p, p, p, 1, 16000, 0, 2, None), b"sep_istft_ola: bad sizes"),
         ("m2h_sep_istft_ola", (p, p, p, 1, 16000, -1, 1, None), b"sep_istft_ola: bad sizes"),
+        ("m2h_sep_istft_ola", (p, p, p, 1, (1 << 40) + 1, 0, 1, None), b"sep_istft_ola: bad sizes"),
     ]
     for name, args, msg in cases:
         assert getattr(lib, name)(*args) < 0, (name, args)

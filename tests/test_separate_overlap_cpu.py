@@ -113,6 +113,7 @@ def test_new_entry_points_reject_bad_arguments_without_a_launch():
         ("m2h_sep_frames_hop", (p, p, p, 1, 16001, 8000, 2, 2, None), b"sep_frames_hop: bad sizes"),      # segments [2, 4) of 3
         ("m2h_sep_frames_hop", (p, p, p, 1, 16000, 4000, 4, 1, None), b"sep_frames_hop: bad sizes"),      # segment 4 of 4
         ("m2h_sep_frames_hop", (p, p, p, 1, 16000, 4000, -1, 1, None), b"sep_frames_hop: bad sizes"),
+        ("m2h_sep_frames_hop", (p, p, p, 1, (1 << 40) + 1, 8000, 0, 1, None), b"sep_frames_hop: bad sizes"),   # the window forms' limit, L <= 2^40
         ("m2h_sep_frames_hop", (p, p + 4, p, 1, 16000, 8000, 0, 1, None), b"sep_frames_hop: window"),
         ("m2h_sep_istft_xfade", (None, p, p, p, 1, 16000, 8000, 0, 1, None), b"sep_istft_xfade: null"),
         ("m2h_sep_istft_xfade", (p, None, p, p, 1, 16000, 8000, 0, 1, None), b"sep_istft_xfade: null"),
@@ -122,6 +123,7 @@ def test_new_entry_points_reject_bad_arguments_without_a_launch():
         ("m2h_sep_istft_xfade", (p, p, p, p, 1, 16000, 8000, 0, 3, None), b"sep_istft_xfade: bad sizes"),  # segments [0, 3) of 2
         ("m2h_sep_istft_xfade", (p, p, p, p, 1, 24001, 4000, 7, 1, None), b"sep_istft_xfade: bad sizes"),  # segment 7 of 7
         ("m2h_sep_istft_xfade", (p, p, p, p, 1, 16000, 8000, 0, 0, None), b"sep_istft_xfade: bad sizes"),
+        ("m2h_sep_istft_xfade", (p, p, p, p, 1, (1 << 40) + 1, 8000, 0, 1, None), b"sep_istft_xfade: bad sizes"),
         ("m2h_sep_istft_xfade", (p, p, p + 4, p, 1, 16000, 8000, 0, 1, None), b"sep_istft_xfade: the cross-fade window"),
     ]
     for name, args, msg in cases:
