@@ -760,6 +760,33 @@ int m2h_score_gram(const float* refs, long long refs_sr, long long refs_ss, long
 int m2h_score_windows(const double* tiles, double* out, long long RC, long long J, int K, long long M, long long window, long long hop,
                       m2h_stream stream);
 
+/* Scorer, time alignment (m2h/audio/score.py, "Alignment"; csrc/align.hip, csrc/score.hip).  D is the largest lag searched, 1 .. 8192
+ * samples; the scored region is the samples [D, L - D) of every row, Lr = L - 2 D >= 2 of them, cut into tiles of `tile` samples with
+ * tile + 2 D <= 32768, J = ceil(Lr / tile).  refs, est and the strides are m2h_score_gram's (elements, 64-bit, any value; rows of L fp32
+ * samples at unit stride, read in place at any alignment).
+ *
+ * m2h_align_corr: the raw cross-correlation (no mean is removed) of the target s = refs[r][target_r][c] and x = est[r][c] per tile,
+ *   out [R][C][J][2 D + 1] fp64:  out[r][c][j][d + D] = sum_t s[t] x[t + d],  t over tile j of the region, d = -D .. D,
+ * computed as one 32768-point circular correlation per (r, c, j) in fp32 (the packed 16384-point transform in 128 KB of LDS, one
+ * 1024-thread workgroup; no wrap-around reaches these outputs) and converted to fp64 on the way out; no atomics, the same bits on every
+ * run and for any batch around a recording.  target: [R] 64-bit reference indices ON THE DEVICE (clamped to [0, S) before use), or
+ * NULL: target0 for every recording.  twiddles: the Auralizer's [2][16384] complex table (m2h_render_spectra).  R <= 65535.
+ *
+ * m2h_score_gram_lag: m2h_score_gram of the region, with the estimate read lag[r * C + c] samples later:
+ *   the signals of (r, c) are refs[r][s][c][D + t], est[r][c][D + lag + t], mix[r][0 / 1][D + t], t < Lr; out [R][C][J][N + N(N+1)/2].
+ * lag: [R * C] int32 ON THE DEVICE; what is read from it is clamped to [-D, D], so no value in it becomes a read outside a row.  The
+ * kernel, the summation order and the checks are m2h_score_gram's (that entry point is this one with D = 0 and no lag): on slices cut
+ * by hand at the same lags m2h_score_gram returns the same bits.
+ * Both return a negative status and launch nothing for a null pointer, S outside 1 .. 6, C outside {1, 2}, R < 1, D outside 1 .. 8192,
+ * tile < 1, L too short (m2h_align_corr: L < 2 D + 2; m2h_score_gram_lag: L < 2 D + 1), and m2h_align_corr also for tile + 2 D > 32768,
+ * a target0 outside [0, S) when target is NULL, R > 65535. */
+int m2h_align_corr(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                   const long long* target, int target0, const float* twiddles, double* out, int R, int S, int C, long long L, int tile, int D,
+                   m2h_stream stream);
+int m2h_score_gram_lag(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                       const float* mix, long long mix_sr, long long mix_sc, double* out, int R, int S, int C, long long L, int tile, const int* lag, int D,
+                       m2h_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-network runner: one C call enqueues every kernel of one separator U-Net forward (K1/K2 slice, 5 down stages, 5 up
  * stages, head) = PassiveSepEncCNN.forward + PassiveSepDecCNN.forward (separator_cnn.py:70-108,153-170) in eval mode.  Same

@@ -15,6 +15,10 @@
 // four 4-byte loads otherwise; a thread's samples and their order are the same on both paths, so the result does not depend on the
 // alignment.  Samples past the tile's end enter as zeros, which change no accumulator.
 //
+// m2h_score_gram_lag (the Scorer's alignment) is the same kernel on the region [D, L - D) of every row, with the estimate of (r, c) read
+// lag[r C + c] samples later; the lag comes from device memory and is clamped to [-D, D].  m2h_score_gram passes no lag and D = 0: the
+// addresses, the samples of a thread and their order are what they were.
+//
 // m2h_score_windows adds the tiles of every window in tile order: a window's Gram is never a difference of prefix sums, so a
 // window's score does not depend on what precedes it.
 #include "m2h_internal.h"
@@ -36,20 +40,27 @@ struct ScoreSignals {
 
 template <int N>
 __global__ __launch_bounds__(SCORE_THREADS) void score_gram_kernel(ScoreSignals a, double* __restrict__ out, int C, long long L, int tile,
-                                                                   long long J) {
+                                                                   long long J, const int* __restrict__ lag, int D) {
   constexpr int S = N - 3, K = N + N * (N + 1) / 2;
   __shared__ double sh[SCORE_THREADS / 64][K];
   const long long b = blockIdx.x;                      // = (r * C + c) * J + j
   const long long j = b % J, rc = b / J;
   const long long c = rc % C, r = rc / C;
-  const long long t0 = j * (long long)tile;
-  const long long left = L - t0;
+  // m2h_score_gram_lag: the scored region starts at sample D of every row and the estimate is read lag[r C + c] samples later; what is
+  // read from `lag` is clamped to [-D, D] (device data never becomes an address outside the row).  m2h_score_gram: lag is null, D is 0.
+  long long shift = 0;
+  if (lag) {
+    const int v = lag[rc];
+    shift = v < -D ? -D : (v > D ? D : v);
+  }
+  const long long t0 = j * (long long)tile + D;
+  const long long left = L - j * (long long)tile;
   const int n = left < tile ? (int)left : tile;        // samples of this tile, >= 1
 
   const float* p[N];
 #pragma unroll
   for (int i = 0; i < S; ++i) p[i] = a.refs + r * a.refs_sr + i * a.refs_ss + c * a.refs_sc + t0;
-  p[S] = a.est + r * a.est_sr + c * a.est_sc + t0;
+  p[S] = a.est + r * a.est_sr + c * a.est_sc + t0 + shift;
   p[S + 1] = a.mix + r * a.mix_sr + t0;
   p[S + 2] = a.mix + r * a.mix_sr + a.mix_sc + t0;
   bool aligned[N];
@@ -123,8 +134,34 @@ __global__ __launch_bounds__(256) void score_windows_kernel(const double* __rest
 }
 
 template <int N>
-static void launch_score_gram(const ScoreSignals& a, double* out, int C, long long L, int tile, long long J, unsigned blocks, hipStream_t st) {
-  M2H_LAUNCH(score_gram_kernel<N>, dim3(blocks), dim3(SCORE_THREADS), 0, st, a, out, C, L, tile, J);
+static void launch_score_gram(const ScoreSignals& a, double* out, int C, long long L, int tile, long long J, unsigned blocks, const int* lag, int D,
+                              hipStream_t st) {
+  M2H_LAUNCH(score_gram_kernel<N>, dim3(blocks), dim3(SCORE_THREADS), 0, st, a, out, C, L, tile, J, lag, D);
+}
+
+// The checks and the launch behind both entry points: L is the number of scored samples per row, which start at sample D.
+static int score_gram_launch(const char* what, const ScoreSignals& a, double* out, int R, int S, int C, long long L, int tile, const int* lag, int D,
+                             m2h_stream stream) {
+  M2H_REQUIRE(a.refs && a.est && a.mix && out, "%s: null pointer (refs %p, est %p, mix %p, out %p)", what, (const void*)a.refs, (const void*)a.est,
+              (const void*)a.mix, (void*)out);
+  M2H_REQUIRE(S >= 1 && S <= 6, "%s: S = %d reference sources; 1 .. 6 are supported", what, S);
+  M2H_REQUIRE(C == 1 || C == 2, "%s: C = %d channels; 1 or 2 are supported", what, C);
+  M2H_REQUIRE(L >= 1, "%s: L = %lld samples; at least 1 is required", what, L + 2ll * D);
+  M2H_REQUIRE(tile >= 1, "%s: tile = %d samples; at least 1 is required", what, tile);
+  M2H_REQUIRE(R >= 1, "%s: R = %d recordings; at least 1 is required", what, R);
+  const long long J = (L + tile - 1) / tile;
+  M2H_REQUIRE(J <= 0x7fffffffLL / ((long long)R * C), "%s: R * C * ceil(L / tile) = %d * %d * %lld workgroups exceed a grid of 2^31 - 1", what, R, C, J);
+  const unsigned blocks = (unsigned)(J * R * C);
+  const hipStream_t st = as_stream(stream);
+  switch (S + 3) {
+    case 4: launch_score_gram<4>(a, out, C, L, tile, J, blocks, lag, D, st); break;
+    case 5: launch_score_gram<5>(a, out, C, L, tile, J, blocks, lag, D, st); break;
+    case 6: launch_score_gram<6>(a, out, C, L, tile, J, blocks, lag, D, st); break;
+    case 7: launch_score_gram<7>(a, out, C, L, tile, J, blocks, lag, D, st); break;
+    case 8: launch_score_gram<8>(a, out, C, L, tile, J, blocks, lag, D, st); break;
+    default: launch_score_gram<9>(a, out, C, L, tile, J, blocks, lag, D, st); break;
+  }
+  return launch_status(what);
 }
 
 }  // namespace m2h
@@ -135,27 +172,18 @@ extern "C" {
 
 int m2h_score_gram(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
                    const float* mix, long long mix_sr, long long mix_sc, double* out, int R, int S, int C, long long L, int tile, m2h_stream stream) {
-  M2H_REQUIRE(refs && est && mix && out, "score_gram: null pointer (refs %p, est %p, mix %p, out %p)", (const void*)refs, (const void*)est,
-              (const void*)mix, (void*)out);
-  M2H_REQUIRE(S >= 1 && S <= 6, "score_gram: S = %d reference sources; 1 .. 6 are supported", S);
-  M2H_REQUIRE(C == 1 || C == 2, "score_gram: C = %d channels; 1 or 2 are supported", C);
-  M2H_REQUIRE(L >= 1, "score_gram: L = %lld samples; at least 1 is required", L);
-  M2H_REQUIRE(tile >= 1, "score_gram: tile = %d samples; at least 1 is required", tile);
-  M2H_REQUIRE(R >= 1, "score_gram: R = %d recordings; at least 1 is required", R);
-  const long long J = (L + tile - 1) / tile;
-  M2H_REQUIRE(J <= 0x7fffffffLL / ((long long)R * C), "score_gram: R * C * ceil(L / tile) = %d * %d * %lld workgroups exceed a grid of 2^31 - 1", R, C, J);
   const ScoreSignals a{refs, refs_sr, refs_ss, refs_sc, est, est_sr, est_sc, mix, mix_sr, mix_sc};
-  const unsigned blocks = (unsigned)(J * R * C);
-  const hipStream_t st = as_stream(stream);
-  switch (S + 3) {
-    case 4: launch_score_gram<4>(a, out, C, L, tile, J, blocks, st); break;
-    case 5: launch_score_gram<5>(a, out, C, L, tile, J, blocks, st); break;
-    case 6: launch_score_gram<6>(a, out, C, L, tile, J, blocks, st); break;
-    case 7: launch_score_gram<7>(a, out, C, L, tile, J, blocks, st); break;
-    case 8: launch_score_gram<8>(a, out, C, L, tile, J, blocks, st); break;
-    default: launch_score_gram<9>(a, out, C, L, tile, J, blocks, st); break;
-  }
-  return launch_status("score_gram");
+  return score_gram_launch("score_gram", a, out, R, S, C, L, tile, nullptr, 0, stream);
+}
+
+int m2h_score_gram_lag(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                       const float* mix, long long mix_sr, long long mix_sc, double* out, int R, int S, int C, long long L, int tile, const int* lag, int D,
+                       m2h_stream stream) {
+  M2H_REQUIRE(lag, "score_gram_lag: null pointer (lag)");
+  M2H_REQUIRE(D >= 1 && D <= 8192, "score_gram_lag: D = %d samples; 1 .. 8192 are supported", D);
+  M2H_REQUIRE(L >= 2ll * D + 1, "score_gram_lag: L = %lld samples; at least 2 D + 1 = %lld are required", L, 2ll * D + 1);
+  const ScoreSignals a{refs, refs_sr, refs_ss, refs_sc, est, est_sr, est_sc, mix, mix_sr, mix_sc};
+  return score_gram_launch("score_gram_lag", a, out, R, S, C, L - 2ll * D, tile, lag, D, stream);
 }
 
 int m2h_score_windows(const double* tiles, double* out, long long RC, long long J, int K, long long M, long long window, long long hop,

@@ -40,6 +40,7 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
+from .twiddles import device_twiddles
 
 BLOCK = 16000
 NFFT = 32768
@@ -97,14 +98,7 @@ class Auralizer:
         """[2, 16384, 2] fp32: exp(-2 pi i k / 32768), k < 16384, interleaved, built in float64 on the host (the feeder's table at this
         length), and the same fp32 values again in the order the transform's stages read them (include/m2h.h, "Auralizer")."""
         if self._twiddles is None:
-            M = NFFT // 2
-            k = np.arange(M, dtype=np.float64)
-            t = np.stack([np.cos(2.0 * np.pi * k / NFFT), -np.sin(2.0 * np.pi * k / NFFT)], axis=1).astype(np.float32)
-            staged = np.zeros_like(t)
-            for s in range(M.bit_length() - 1):
-                half = M >> (s + 1)
-                staged[M - (M >> s):M - (M >> s) + half] = t[(np.arange(half) << s) * 2]
-            self._twiddles = torch.from_numpy(np.stack([t, staged])).to(self.device).contiguous()
+            self._twiddles = device_twiddles(self.device, NFFT)
         return self._twiddles
 
     def _mark(self, stage):

@@ -27,7 +27,8 @@ target, x the estimate, P the references' Gram matrix,
   b = solve(P, refs^T (x - alpha s)) + EPS       e_interf = refs b            e_artif = x - alpha s - e_interf + EPS
   si_sir = 10 log10(|alpha s|^2 / |e_interf|^2)                               si_sar = 10 log10(|alpha s|^2 / |e_artif|^2)
 
-then si_sdri, sd_sdri, snri, si_siri, si_sari: the estimate's number minus the baseline's.  No time alignment is made.
+then si_sdri, sd_sdri, snri, si_siri, si_sari: the estimate's number minus the baseline's.  No time alignment is made unless `align`
+is given (below).
 
 Degenerate cases.  A source whose centred energy in the window is 0 (digital silence, or not positive after rounding) is left out of the
 projection: its coefficient is 0.  If the target's energy is 0 or n < 2, all eleven numbers are NaN.  If the reduced normal equations
@@ -41,16 +42,42 @@ residuals are quadratic forms.  m2h_score_gram reads every signal once and write
 exact products (an fp32 Gram loses the noise norm, a difference of Gram entries, exactly where a good separator scores: DESIGN.md §8.6);
 m2h_score_windows adds a window's tiles in tile order -- never a difference of prefix sums, so a window's score does not depend on what
 precedes it -- and metrics_from_gram does the algebra in torch float64, batched over recordings, channels and windows.
+
+Alignment.  score(..., align=None) is all of the above, unchanged.  align=D, a Python int in 1 .. 8192, is the largest lag searched, in
+samples; it requires tile + 2 D <= 32768 and L >= 2 D + 2 (a ValueError that names the values, before any launch).  For recording r and
+channel c let s = references[r, target_r, c] and x = estimate[r, c].  The scored region is the reference samples t in [D, L - D): the
+same for every recording and every lag, so the plan never depends on device data.  Lr = L - 2 D; tiles and windows are
+score_plan(Lr, tile, window, hop) counted from sample D, and align_plan(L, D, tile, window, hop) returns them in pure Python:
+score_plan's dict plus "offset": D, with "samples" in coordinates of the input.
+
+  ct[r, c, j, d + D] = sum_t s[t] x[t + d]        t over tile j of the region, d = -D .. D
+
+The signals are raw: no mean is removed, so a DC offset adds a pedestal n . mean(s) . mean(x) to every lag and flattens the peak.  A
+window's correlation is the sum of its tiles' ct in tile order, in float64; the whole recording's is the sum over all J tiles.  The lag
+of a window is the d that maximises |c[d]|; among equal maxima the smallest |d| wins, then the negative one, so digital silence gives
+lag 0 (lags_from_corr).  Every window and the whole recording are then scored exactly as above on references[..., D : L - D],
+mixture[..., D : L - D] and estimate[r, c, D + lag_rc : L - D + lag_rc], where lag_rc is the WHOLE-RECORDING lag of that recording and
+channel: the two ears are aligned independently.  The windows' own lags are reported ("lag_track") but not used for scoring: they show
+drift.  m2h_align_corr (csrc/align.hip) computes ct by one 32768-point circular correlation per tile in fp32 (the Auralizer's transform,
+fft_lds.h; no wrap-around reaches the lags kept) and writes it as float64; m2h_score_windows adds the tiles; m2h_score_gram_lag is
+m2h_score_gram reading the region with the estimate moved by the lag, which it takes from device memory and clamps to [-D, D].
+Recordings are processed in groups whose ct stays under `max_corr_bytes` (a single recording above it goes alone); they are
+independent, so grouping changes no bit.  No host synchronisation, and no copy from the host apart from the twiddle table on a
+Scorer's first aligned call.  Not done: sub-sample lags, caller-supplied lags, inputs of unequal length.
 """
 import operator
 
 import torch
 
 from .. import ops
+from .twiddles import device_twiddles
 from ..common.eval_metrics import EPS, METRIC_ORDER
 
 DEFAULT_TILE = 16000
 MAX_SOURCES = 6
+MAX_ALIGN = 8192             # the largest `align`, in samples
+ALIGN_NFFT = 32768           # the correlation's transform: tile + 2 align samples must fit
+DEFAULT_MAX_CORR_BYTES = 1 << 30
 _NAN = float("nan")
 
 
@@ -73,6 +100,45 @@ def score_plan(L, tile=DEFAULT_TILE, window=1, hop=1):
     tiles = [(min(m * hop, J), min(m * hop + window, J)) for m in range(M)]
     return {"L": L, "tile": tile, "window": window, "hop": hop, "J": J, "M": M, "tiles": tiles,
             "samples": [(min(j0 * tile, L), min(j1 * tile, L)) for j0, j1 in tiles]}
+
+
+def align_plan(L, D, tile=DEFAULT_TILE, window=1, hop=1):
+    """Pure Python: the tiles and windows of one aligned score (module docstring, "Alignment").
+
+    -> score_plan(L - 2 D, tile, window, hop) plus "offset": D, with "samples" moved by D into coordinates of the input ("L" stays the
+    region's length L - 2 D).  Raises on D outside 1 .. 8192, tile + 2 D > 32768 and L < 2 D + 2."""
+    try:
+        d = operator.index(D)
+    except TypeError:
+        raise TypeError("m2h.Scorer: align must be an int or None, got %r" % (D,))
+    if isinstance(D, bool) or not 1 <= d <= MAX_ALIGN:
+        raise ValueError("m2h.Scorer: align must be in 1 .. %d samples, got %r" % (MAX_ALIGN, D))
+    L = score_plan(L, tile, window, hop)["L"]                                           # raises on L, tile, window, hop
+    if L < 2 * d + 2:
+        raise ValueError("m2h.Scorer: L = %d samples; align = %d needs at least 2 * %d + 2 = %d" % (L, d, d, 2 * d + 2))
+    plan = score_plan(L - 2 * d, tile, window, hop)
+    if plan["tile"] + 2 * d > ALIGN_NFFT:
+        raise ValueError("m2h.Scorer: tile + 2 align = %d + 2 * %d = %d exceeds the transform's %d points" % (plan["tile"], d, plan["tile"] + 2 * d, ALIGN_NFFT))
+    plan["offset"] = d
+    plan["samples"] = [(t0 + d, t1 + d) for t0, t1 in plan["samples"]]
+    return plan
+
+
+def lags_from_corr(c):
+    """c [..., 2 D + 1] float64, column d + D the correlation at lag d -> the lag of largest |c| as int32 [...]: among equal maxima the
+    smallest |d|, then the negative one (the columns reordered as 0, -1, +1, -2, +2, ... and the first maximum taken), so all zeros give
+    0.  Torch on c's device; no synchronisation."""
+    if not isinstance(c, torch.Tensor) or c.dtype != torch.float64:
+        raise TypeError("m2h.Scorer: a correlation must be a float64 torch tensor, got %s" % (c.dtype if isinstance(c, torch.Tensor) else type(c).__name__))
+    K = c.shape[-1] if c.dim() else 0
+    if K < 1 or K % 2 == 0:
+        raise ValueError("m2h.Scorer: a correlation holds 2 D + 1 lags, not %d" % K)
+    D = K // 2
+    i = torch.arange(K, device=c.device, dtype=torch.int64)
+    half = (i + 1) // 2
+    lag = torch.where(i % 2 == 1, -half, half)                                          # 0, -1, +1, -2, +2, ...
+    first = torch.argmax(c.abs().index_select(-1, lag + D), dim=-1)                     # the first of equal maxima
+    return lag[first].to(torch.int32)
 
 
 def gram_signals(K):
@@ -228,9 +294,19 @@ def target_energy(gram, n, target):
 
 
 class Scorer:
-    def __init__(self, device):
+    def __init__(self, device, max_corr_bytes=DEFAULT_MAX_CORR_BYTES):
+        if isinstance(max_corr_bytes, bool) or int(max_corr_bytes) < 1:
+            raise ValueError("m2h.Scorer: max_corr_bytes must be positive, got %r" % (max_corr_bytes,))
         self.device = torch.device(device)
+        self.max_corr_bytes = int(max_corr_bytes)   # align: recordings are processed in groups whose tile correlations stay under this
+        self._twiddles = None
         self._timing = None          # tools/score_bench.py: a list that receives (stage, event) marks
+
+    def _twiddle_table(self):
+        """the transform's [2, 16384, 2] table on the device (m2h.audio.twiddles), copied from the host once"""
+        if self._twiddles is None:
+            self._twiddles = device_twiddles(self.device, ALIGN_NFFT)
+        return self._twiddles
 
     def _mark(self, stage):
         if self._timing is not None:
@@ -238,7 +314,7 @@ class Scorer:
             ev.record(torch.cuda.current_stream(self.device))
             self._timing.append((stage, ev))
 
-    def _check(self, estimate, references, mixture, target, tile, window, hop):
+    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None):
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("m2h.Scorer: %s must be a torch tensor, got %s" % (name, type(t).__name__))
@@ -289,36 +365,58 @@ class Scorer:
                 raise ValueError("m2h.Scorer: target %d is not one of the S = %d references (0 .. %d)" % (t, S, S - 1))
         if not isinstance(target, int) and len(set(target)) == 1:
             target = target[0]
-        plan = score_plan(L, tile, window, hop)                                         # raises on tile, window, hop
+        plan = score_plan(L, tile, window, hop) if align is None else align_plan(L, align, tile, window, hop)      # raises on tile, window, hop, align
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not t.is_cuda or t.device != self.device:
                 raise ValueError("m2h.Scorer: %s must live on %s, got %s; the scorer has no CPU path" % (name, self.device, t.device))
         return refs, est, target, plan
 
-    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1):
+    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None):
         """-> {"whole": [R, C, 11], "track": [R, C, M, 11], "active": [R, C, M] bool, "plan": score_plan(...)}; float64 on the device, in
-        eval_metrics.METRIC_ORDER; no host synchronisation.  The module docstring holds the definition."""
-        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop)
+        eval_metrics.METRIC_ORDER; no host synchronisation.  With align=D (an int, the largest lag searched in samples) the estimate is
+        aligned to its target first: also "lag": [R, C] int32 and "lag_track": [R, C, M] int32 on the device, and "plan" is
+        align_plan(...).  The module docstring holds the definition."""
+        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align)
         R, S, C, L = refs.shape
         J, M, tile, window, hop = (plan[k] for k in ("J", "M", "tile", "window", "hop"))
+        D = plan.get("offset", 0)
+        Ls = L - 2 * D                                                                  # the scored samples per row
         dev = self.device
+        out = {}
         with torch.cuda.device(dev):
             if not isinstance(target, int):                                            # R small fills: no copy from the host
                 tt = torch.empty((R,), dtype=torch.int64, device=dev)
                 for r, t in enumerate(target):
                     tt[r].fill_(t)
                 target = tt
+            if align is not None:
+                tw = self._twiddle_table()
             self._mark("start")
-            tiles = ops.score_gram(refs, est, mixture, tile)                            # [R, C, J, K]
+            if align is None:
+                tiles = ops.score_gram(refs, est, mixture, tile)                        # [R, C, J, K]
+            else:
+                step = max(1, self.max_corr_bytes // (C * J * (2 * D + 1) * 8))         # recordings per group
+                lags = []
+                for r0 in range(0, R, step):
+                    r1 = min(r0 + step, R)
+                    ct = ops.align_corr(refs[r0:r1], est[r0:r1], target if isinstance(target, int) else target[r0:r1], tile, D, tw)     # [r, C, J, 2 D + 1]
+                    self._mark("align_corr")
+                    lags.append(lags_from_corr(torch.cat([ops.score_windows(ct, 1, J, 1), ops.score_windows(ct, M, window, hop)], dim=2)))
+                    del ct
+                    self._mark("lag_pick")
+                lags = lags[0] if len(lags) == 1 else torch.cat(lags)                   # [R, C, 1 + M]: whole, then the track
+                out["lag"], out["lag_track"] = lags[:, :, 0].contiguous(), lags[:, :, 1:]
+                tiles = ops.score_gram_lag(refs, est, mixture, tile, out["lag"], D)
             self._mark("score_gram")
             gram = torch.cat([ops.score_windows(tiles, 1, J, 1), ops.score_windows(tiles, M, window, hop)], dim=2)      # whole, then the track
             m = torch.arange(M, device=dev, dtype=torch.int64) * hop
-            n = (torch.clamp((m + window) * tile, max=L) - torch.clamp(m * tile, max=L)).to(torch.float64)
-            n = torch.cat([torch.full((1,), float(L), dtype=torch.float64, device=dev), n])
+            n = (torch.clamp((m + window) * tile, max=Ls) - torch.clamp(m * tile, max=Ls)).to(torch.float64)
+            n = torch.cat([torch.full((1,), float(Ls), dtype=torch.float64, device=dev), n])
             scores = metrics_from_gram(gram, n, target, C)
             active = target_energy(gram[:, :, 1:], n[1:], target) > 0
             self._mark("metrics")
-        return {"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan}
+        out.update({"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan})
+        return out
 
 
 def summarize(result):

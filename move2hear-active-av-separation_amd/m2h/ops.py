@@ -756,6 +756,71 @@ def score_gram(refs, est, mix, tile):
     return out
 
 
+def _score_signals(what, refs, est, mix=None):
+    """the shape, dtype and stride checks shared by the Scorer's aligned ops -> (R, S, C, L)"""
+    for t in (refs, est) + (() if mix is None else (mix,)):
+        if not t.is_cuda or t.dtype != torch.float32 or t.device != refs.device:
+            raise RuntimeError("m2h.%s: float32 tensors on one GPU are required (got %s on %s); the m2h ops have no CPU path" % (what, t.dtype, t.device))
+    if refs.dim() != 4 or est.dim() != 3 or (mix is not None and mix.dim() != 3):
+        raise RuntimeError("m2h.%s: refs [R, S, C, L], est [R, C, L] and mix [R, 2, L] are required" % what)
+    R, S, C, L = refs.shape
+    if tuple(est.shape) != (R, C, L) or (mix is not None and tuple(mix.shape) != (R, 2, L)) or R < 1:
+        raise RuntimeError("m2h.%s: refs %s, est %s%s do not agree" % (what, tuple(refs.shape), tuple(est.shape), "" if mix is None else " and mix %s" % (tuple(mix.shape),)))
+    if any(t.stride(-1) != 1 for t in (refs, est) + (() if mix is None else (mix,))):
+        raise RuntimeError("m2h.%s: the last stride must be 1" % what)
+    if not 1 <= S <= 6 or C not in (1, 2):
+        raise RuntimeError("m2h.%s: S = %d in 1 .. 6 and C = %d in {1, 2} are required" % (what, S, C))
+    return R, S, C, L
+
+
+def align_corr(refs, est, target, tile, D, twiddles):
+    """Tile cross-correlations of the Scorer's alignment (m2h/audio/score.py): refs [R, S, C, L], est [R, C, L] fp32 with unit last stride
+    (views are read in place); target an int, or an int64 tensor [R] on the device; twiddles: the [2, 16384, 2] table of
+    m2h.audio.twiddles -> [R, C, J, 2 D + 1] fp64, J = ceil((L - 2 D) / tile):  out[r, c, j, d + D] = sum_t s[t] x[t + d] over tile j of
+    the region [D, L - D) (include/m2h.h)."""
+    R, S, C, L = _score_signals("align_corr", refs, est)
+    tile, D = int(tile), int(D)
+    if not 1 <= D <= 8192 or tile < 1 or tile + 2 * D > 32768 or L < 2 * D + 2:
+        raise RuntimeError("m2h.align_corr: D = %d in 1 .. 8192, tile = %d >= 1 with tile + 2 D <= 32768 and L = %d >= 2 D + 2 are required" % (D, tile, L))
+    _chk(twiddles, "align_corr(twiddles)")
+    if tuple(twiddles.shape) != (2, 16384, 2) or twiddles.device != refs.device:
+        raise RuntimeError("m2h.align_corr: twiddles must be the [2, 16384, 2] table on %s" % (refs.device,))
+    if isinstance(target, torch.Tensor):
+        if target.dtype != torch.int64 or tuple(target.shape) != (R,) or target.device != refs.device or not target.is_contiguous():
+            raise RuntimeError("m2h.align_corr: a tensor `target` must be a contiguous int64 [R] = [%d] on %s" % (R, refs.device))
+        tptr, t0 = _ptr(target), 0
+    else:
+        tptr, t0 = None, int(target)
+        if not 0 <= t0 < S:
+            raise RuntimeError("m2h.align_corr: target = %d is not one of the S = %d references" % (t0, S))
+    out = torch.empty((R, C, -(-(L - 2 * D) // tile), 2 * D + 1), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_align_corr(_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1), tptr, t0,
+                                      _ptr(twiddles), _ptr(out), R, S, C, L, tile, D, _stream(refs)), "m2h_align_corr")
+    return out
+
+
+def score_gram_lag(refs, est, mix, tile, lag, D):
+    """score_gram of the region [D, L - D) with the estimate of (r, c) read lag[r, c] samples later: lag [R, C] int32 on the device
+    (clamped to [-D, D] by the kernel) -> [R, C, J, N + N(N+1)/2] fp64, J = ceil((L - 2 D) / tile) (include/m2h.h)."""
+    R, S, C, L = _score_signals("score_gram_lag", refs, est, mix)
+    tile, D = int(tile), int(D)
+    if not 1 <= D <= 8192 or tile < 1 or L < 2 * D + 1:
+        raise RuntimeError("m2h.score_gram_lag: D = %d in 1 .. 8192, tile = %d >= 1 and L = %d >= 2 D + 1 are required" % (D, tile, L))
+    _chk(lag, "score_gram_lag(lag)", torch.int32)
+    if tuple(lag.shape) != (R, C) or lag.device != refs.device:
+        raise RuntimeError("m2h.score_gram_lag: lag must be [R, C] = [%d, %d] int32 on %s" % (R, C, refs.device))
+    N = S + 3
+    out = torch.empty((R, C, -(-(L - 2 * D) // tile), N + N * (N + 1) // 2), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_score_gram_lag(_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1),
+                                          _ptr(mix), mix.stride(0), mix.stride(1), _ptr(out), R, S, C, L, tile, _ptr(lag), D, _stream(refs)),
+                   "m2h_score_gram_lag")
+    return out
+
+
 def score_windows(tiles, M, window, hop):
     """tiles [R, C, J, K] fp64 -> [R, C, M, K]: every window's tiles added in tile order (window m: tiles m * hop .. m * hop + window - 1)."""
     _chk(tiles, "score_windows", torch.float64)

@@ -2,15 +2,18 @@
 """Score a separated recording of any length against its ground truth:
 
     python score.py --estimate out.wav --mixture mix.wav --reference target.wav [--reference other.wav ...] [--window W --hop H]
-                    [--json scores.json]
+                    [--align D] [--json scores.json]
 
 ``--reference``: the sources as they are in the mixture, at most six; the FIRST one is the target the estimate is scored against, the
 others are the interferers (they enter SI-SIR and SI-SAR).  ``render.py --out-target / --out-image`` writes such files.  ``--mixture``:
 the two-channel recording the separator was given; the improvements (SI-SDRi, ...) are measured against it.  The estimate and every
 reference have the same channel count: mono files are scored against the mean of the mixture's channels (separate.py's default
 output), two-channel files ear by ear (``separate.py --output binaural``).  All files are 16 kHz, int16 or float32, and have the
-same length; anything else is an error.  NO TIME ALIGNMENT is made: a dry source scored against a reverberant estimate is the
-caller's business.
+same length; anything else is an error.  Time alignment: none unless ``--align``.  ``--align D`` searches the lags -D .. D samples
+(D at most 8192) for the one at which the estimate correlates best with the target, ear by ear, over the whole recording, and scores
+the samples [D, L - D) of the references and the mixture against the estimate read that many samples later; the lag of every channel
+is printed in samples and milliseconds, and the lag of every window is written to the JSON (it shows drift; it is not used for
+scoring).  The files still need equal lengths.
 
 The recording is scored as a whole and in windows of ``--window`` seconds, one every ``--hop`` seconds (defaults 1 and 1).  Printed:
 the whole-recording metrics, then the mean and the median of every metric over the active windows (those in which the target is not
@@ -47,6 +50,7 @@ def main():
     parser.add_argument("--reference", action="append", required=True, help="a source as it is in the mixture (repeat; the first is the target)")
     parser.add_argument("--window", type=int, default=1, help="window length in seconds")
     parser.add_argument("--hop", type=int, default=1, help="a window every HOP seconds")
+    parser.add_argument("--align", type=int, default=None, metavar="D", help="align the estimate to the target first: the largest lag searched, in samples (1 .. 8192)")
     parser.add_argument("--json", default=None, help="write every number here")
     args = parser.parse_args()
     import numpy as np
@@ -61,7 +65,7 @@ def main():
                              % (args.estimate, est.shape[0], "" if est.shape[0] == 1 else "s", path, x.shape[0]))
     for path, x in [(args.mixture, mix)] + list(zip(args.reference, refs)):
         if x.shape[1] != est.shape[1]:
-            raise SystemExit("score.py: %s is %d samples long and %s is %d; equal lengths are required (no alignment is made)"
+            raise SystemExit("score.py: %s is %d samples long and %s is %d; equal lengths are required (with --align too)"
                              % (args.estimate, est.shape[1], path, x.shape[1]))
 
     import torch
@@ -69,7 +73,7 @@ def main():
     dev = torch.device("cuda", 0)
     try:
         res = Scorer(dev).score(torch.from_numpy(np.ascontiguousarray(est)).to(dev)[None], torch.from_numpy(np.stack(refs)).to(dev)[None],
-                                torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop)
+                                torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop, align=args.align)
     except (ValueError, TypeError) as e:
         raise SystemExit("score.py: %s" % e)
     s = summarize(res)
@@ -78,6 +82,12 @@ def main():
     print("score.py: %s against %s (%d samples at %d Hz, %.2f s, %d reference%s, %d window%s of %d s every %d s)" % (
         args.estimate, args.reference[0], L, separate.SAMPLE_RATE, L / separate.SAMPLE_RATE, len(refs), "" if len(refs) == 1 else "s",
         plan["M"], "" if plan["M"] == 1 else "s", args.window, args.hop))
+    if args.align is not None:
+        lag = res["lag"][0].cpu().tolist()
+        t0, t1 = plan["offset"], L - plan["offset"]
+        print("score.py: --align %d: samples [%d, %d) of the references and the mixture are scored" % (args.align, t0, t1))
+        for c in range(C):
+            print("%-8s lag %d samples (%.4f ms)" % (names[c], lag[c], 1000.0 * lag[c] / separate.SAMPLE_RATE))
     print("%-8s %-14s" % ("channel", "") + " ".join("%13s" % m for m in s["metrics"]))
     for c in range(C):
         for label, key in (("whole", "whole"), ("window mean", "track_mean"), ("window median", "track_median")):
@@ -89,6 +99,8 @@ def main():
                "whole": s["whole"][0], "track_mean": s["track_mean"][0], "track_median": s["track_median"][0],
                "active_windows": s["active_windows"][0], "windows": [list(w) for w in plan["samples"]],
                "track": res["track"][0].cpu().numpy().tolist(), "active": res["active"][0].cpu().numpy().tolist()}
+        if args.align is not None:
+            out.update({"align": args.align, "region": [t0, t1], "lag": lag, "lag_track": res["lag_track"][0].cpu().tolist()})
         with open(args.json, "w") as f:
             json.dump(out, f, indent=1)       # (NaN and Infinity as Python's json writes them)
             f.write("\n")

@@ -3,6 +3,8 @@
 
     python tools/score_bench.py --out profiles/score_bench.json      # every case, each in a child process under a timeout
     python tools/score_bench.py --case 16x3x600c2                    # one case in this process
+    python tools/score_bench.py --align 1024 --align 8192 --out profiles/score_align_bench.json     # the aligned scorer, every case at every D
+    python tools/score_bench.py --case 1x2x60c2 --align 8192         # one case of it in this process
 
 Cases (R recordings x S sources x seconds, C channels): 16x3x600 and 1x2x60, each with C = 1 and C = 2; per-second windows.  Timing: HIP
 events on the stream around the Gram launch and around everything after it (Scorer._timing), summed over the repetitions.
@@ -15,6 +17,14 @@ events on the stream around the Gram launch and around everything after it (Scor
   torch_gram_ms           the same tile Grams from torch: the signals stacked, .double(), one batched matmul over the tiles and a sum; timed
                           before and after the new path (two recordings at a time above 4 GiB of float64 operands); its largest
                           relative difference from the kernel's Grams is recorded
+With --align D (Scorer.score(..., align=D); the estimate is the unaligned case's, rolled by 137 samples):
+  align_corr_ms           the m2h_align_corr launches of one call (one per group of recordings under max_corr_bytes)
+  lag_pick_ms             the two m2h_score_windows over the tile correlations and lags_from_corr
+  gram_lag_ms, post_ms    the m2h_score_gram_lag launch, and everything after it
+  corr_flops_per_s        three 32768-point real transforms per (recording, channel, tile) at 2.5 n log2 n flops, over align_corr_ms
+  torch_fft_corr_ms       the whole-recording correlation from torch.fft in the same run, before and after: rfft of the target and of the
+                          estimate zero-padded to the next power of two at or above 2 L, conj(S) X, irfft, the lags -D .. D sliced out
+                          (two recordings at a time above 2^26 points); whether its lags equal the Scorer's is recorded
 No threshold is set anywhere: the file reports what came out.  Every GPU step runs under its own timeout and the driver stops at the
 first failure.
 """
@@ -114,18 +124,95 @@ def run_case(case):
     return res
 
 
+def run_align_case(case, D):
+    import torch
+    from m2h.audio.score import Scorer, lags_from_corr
+    if not torch.cuda.is_available():
+        raise SystemExit("score_bench: no GPU; this measurement has no CPU path")
+    R, S, seconds, C, reps = CASES[case]
+    dev = torch.device("cuda", 0)
+    L = seconds * SEG
+    g = torch.Generator(device=dev).manual_seed(7)
+    refs = torch.randn((R, S, C, L), device=dev, generator=g) * 0.1 + 0.01
+    mix = torch.stack([refs[:, :, 0].mean(1), refs[:, :, C - 1].mean(1)], dim=1) + 0.02 * torch.randn((R, 2, L), device=dev, generator=g)
+    est = torch.roll(0.8 * refs[:, 0] + 0.03 * torch.randn((R, C, L), device=dev, generator=g), 137, dims=-1)
+    sc = Scorer(dev)
+    nfft = 1 << (2 * L - 1).bit_length()
+    step = R if R * nfft <= (1 << 26) else 2
+
+    def torch_corr():
+        """[R, C, 2 D + 1]: sum_t s[t] x[t + d] over the whole recording, d = -D .. D, from torch.fft"""
+        rows = []
+        for r0 in range(0, R, step):
+            s, x = torch.fft.rfft(refs[r0:r0 + step, 0], nfft), torch.fft.rfft(est[r0:r0 + step], nfft)
+            c = torch.fft.irfft(torch.conj(s) * x, nfft)
+            rows.append(torch.cat([c[..., nfft - D:], c[..., :D + 1]], dim=-1))
+        return torch.cat(rows)
+
+    def timed_torch():
+        n = max(1, reps // 2)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            torch_corr()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def timed_scorer():
+        marks = []
+        sc._timing = marks
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            sc.score(est, refs, mix, align=D)
+        torch.cuda.synchronize()
+        sc._timing = None
+        ms = dict.fromkeys(("align_corr", "lag_pick", "score_gram", "metrics"), 0.0)
+        for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
+            if name != "start":
+                ms[name] += e0.elapsed_time(e1)
+        return {k: v / reps for k, v in ms.items()}
+
+    res0 = sc.score(est, refs, mix, align=D)                                            # warm-up of every shape
+    lag = res0["lag"]
+    torch_lag = lags_from_corr(torch_corr().double())
+    torch.cuda.synchronize()
+    before = timed_torch()
+    t = timed_scorer()
+    after = timed_torch()
+    J = res0["plan"]["J"]
+    flops = 3 * R * C * J * 2.5 * 32768 * 15
+    total = sum(t.values())
+    res = {"case": case, "align": D, "R": R, "S": S, "C": C, "audio_seconds_per_recording": seconds, "reps": reps, "ms_per_call": total,
+           "align_corr_ms": t["align_corr"], "lag_pick_ms": t["lag_pick"], "gram_lag_ms": t["score_gram"], "post_ms": t["metrics"],
+           "corr_bytes": R * C * J * (2 * D + 1) * 8, "corr_groups": -(-R // max(1, sc.max_corr_bytes // (C * J * (2 * D + 1) * 8))),
+           "corr_flops_per_s": flops / (t["align_corr"] * 1e-3), "audio_s_per_s": R * seconds / (total * 1e-3),
+           "torch_fft_corr_ms": [before, after], "torch_fft_points": nfft, "torch_fft_recordings_per_step": step,
+           "torch_fft_over_align_corr_and_pick": 0.5 * (before + after) / (t["align_corr"] + t["lag_pick"]),
+           "lags_all_137": bool((lag == 137).all()), "torch_fft_lags_equal": bool((torch_lag == lag).all()),
+           "whole_scores_finite": bool(torch.isfinite(res0["whole"]).all()), "whole_si_sdr_db": float(res0["whole"][0, 0, 0])}
+    print(json.dumps(res))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", choices=sorted(CASES), default=None)
+    ap.add_argument("--align", type=int, action="append", default=None, metavar="D", help="measure the aligned scorer at this largest lag (repeat)")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=120, help="driver mode: seconds per case")
     args = ap.parse_args()
     if args.case is not None:
-        run_case(args.case)
+        if args.align:
+            for D in args.align:
+                run_align_case(args.case, D)
+        else:
+            run_case(args.case)
         return
     results = []
-    for case in ORDER:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case]
+    for case, D in [(case, D) for D in (args.align or [None]) for case in ORDER]:
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case] + ([] if D is None else ["--align", str(D)])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             print(r.stdout[-4000:])
