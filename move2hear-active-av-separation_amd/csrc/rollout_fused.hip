@@ -10,19 +10,11 @@
 // per-env scalar work.  Hand-off = the guide's counter form (cdna_hip_programming.md, Guideline 16): plain partial stores ->
 // vmcnt(0) -> block barrier -> lane 0: agent-scope release fence, vmcnt(0), relaxed agent-scope fetch_add; the last arriver:
 // agent-scope acquire fence, then plain loads.  The counter is left at zero for the next launch.
-#include "m2h_internal.h"
+#include "rl_common.h"
 
 namespace m2h {
 
-namespace {
 constexpr int NQ = 8;   // partial sums per block: next (p-g)^2, next g^2, cur (p-g)^2, cur g^2, bin ch0, bin ch1, mono, mem
-
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-}  // namespace
 
 template <int CH>
 __global__ __launch_bounds__(256) void rollout_step_stats_kernel(const m2h_step_stats_args a) {
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(256) void rollout_step_stats_kernel(const m2h_step_
   }
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
-    const float t = wave_sum64(s[q]);
+    const float t = wave_sum(s[q]);
     if (lane == 0) sh[wave][q] = t;
   }
   __syncthreads();
@@ -107,7 +99,7 @@ __global__ __launch_bounds__(256) void rollout_step_stats_kernel(const m2h_step_
   a.losses[e] = bin_loss;
   a.losses[a.N + e] = mono_loss;
   a.losses[2 * a.N + e] = mem_loss;
-  // per-episode statistics: the arithmetic of episode_stats_kernel (rl_ops.hip), same operation order, no fused multiply-adds
+  // per-episode statistics: the arithmetic of episode_stats_kernel (rollout_ops.hip), same operation order, no fused multiply-adds
   const m2h_episode_stats& st = a.stats;
   const int A = a.A;
   if (a.ndgs) st.episode_ndgs[e] = __fadd_rn(st.episode_ndgs[e], __fmul_rn(nd, a.ndgs[e]));

@@ -473,7 +473,7 @@ def patch_engine_layer(x, w, transposed, whole):
 
 
 def philox_exp1(seed, counter):
-    """numpy restatement of csrc/rl_ops.hip philox_exp1 (Philox4x32-10, word 0, 23 bits -> (0, 1) -> -log).  -> (noise, u)."""
+    """numpy restatement of csrc/policy_heads.hip philox_exp1 (Philox4x32-10, word 0, 23 bits -> (0, 1) -> -log).  -> (noise, u)."""
     M32 = np.uint64(0xFFFFFFFF)
     counter = np.asarray(counter, dtype=np.uint64)
     c0, c1 = counter & M32, counter >> np.uint64(32)

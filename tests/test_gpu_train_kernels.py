@@ -1,4 +1,4 @@
-"""GPU: the training kernels beyond the convolutions -- csrc/bn.hip and the training half of csrc/rl_ops.hip (GRU step / cell / BPTT kernels, the
+"""GPU: the training kernels beyond the convolutions -- csrc/bn.hip and the training units csrc/rnn.hip, policy_heads.hip, losses.hip and optim.hip (GRU step / cell / BPTT kernels, the
 LSTM cell, the policy heads with their backward and weight gradient, the L1 / binaural / PPO losses, gradient clipping and Adam) -- on every
 route and edge of tests/train_kernels.py's table, every output element against the float64 reference of the same float32 inputs:
 |g_e - r_e| <= tau * s_e (elem_bound.bound; the scales and their one rule: tests/train_kernels.py, pinned on the CPU by

@@ -1,4 +1,5 @@
-"""The training kernels beyond the convolutions (TEST INFRASTRUCTURE): csrc/bn.hip and the training half of csrc/rl_ops.hip -- their
+"""The training kernels beyond the convolutions (TEST INFRASTRUCTURE): csrc/bn.hip and the training units csrc/rnn.hip,
+policy_heads.hip, losses.hip and optim.hip -- their
 restated dispatch, the table of test rows, the float64 reference of every row with its element-wise error scale, float32 numpy
 restatements of each kernel's algorithm, and mutants of those restatements that the bound must reject.
 
@@ -71,7 +72,7 @@ def _t64(a):
 
 
 def grid_for(total, cap=4096):
-    """rl_ops.hip grid_for: blocks of 256 threads, capped."""
+    """rl_common.h grid_for: blocks of 256 threads, capped."""
     return max(1, min(cdiv(total, 256), cap))
 
 
@@ -91,7 +92,7 @@ def wave_tree(v):
 
 
 def block_sum256(v):
-    """rl_ops.hip block_sum: per-wave tree, then the four waves left to right.  v [256, ...]."""
+    """rl_common.h block_sum: per-wave tree, then the four waves left to right.  v [256, ...]."""
     w = [wave_tree(v[64 * i:64 * i + 64]) for i in range(4)]
     return ((w[0] + w[1]) + w[2]) + w[3]
 
@@ -410,7 +411,7 @@ def bn_fp32(row, inp, mutant=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
-# GRU kernels, one step (rl_ops.hip: gru_gates, gru_step, gru_cell, gru_gates_bwd, gru_bwd_rec / gru_bwd_step, gru_bwd_combine)
+# GRU kernels, one step (rnn.hip: gru_gates, gru_step, gru_cell, gru_gates_bwd, gru_bwd_rec / gru_bwd_step, gru_bwd_combine)
 # ----------------------------------------------------------------------------------------------------------------------------------
 GRU_STEP_MAX_ROWS = 16
 GRU_WAVES = {"gru_step": 8, "gru_cell": 16, "gru_bwd_rec": 16, "gru_bwd_step": 16}    # GS_NW, GC_NW, GB_NW
@@ -872,7 +873,7 @@ def seq_fp32(row, inp, mutant=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
-# LSTM cell (rl_ops.hip lstm_cell_kernel / lstm_cell_bwd_kernel)
+# LSTM cell (rnn.hip lstm_cell_kernel / lstm_cell_bwd_kernel)
 # ----------------------------------------------------------------------------------------------------------------------------------
 def _lstm_row(M, H, variant):
     return dict(id="lstm.M%d.H%d.%s" % (M, H, variant), family="lstm", M=M, H=H, variant=variant)
@@ -956,7 +957,7 @@ def lstm_fp32(row, inp, mutant=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
-# Policy heads (rl_ops.hip policy_heads_kernel / policy_heads_bwd_kernel / policy_heads_wgrad_kernel)
+# Policy heads (policy_heads.hip policy_heads_kernel / policy_heads_bwd_kernel / policy_heads_wgrad_kernel)
 # ----------------------------------------------------------------------------------------------------------------------------------
 def heads_route(H, A):
     """policy_heads_kernel's load path, the backward's dz row length, and where functional.PolicyHeads.backward takes the parameter gradients."""
@@ -1171,7 +1172,7 @@ def heads_fp32(row, inp, mutant=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
-# Losses (rl_ops.hip l1_loss_kernel, l1_nhwc16_kernel, bin_l1_kernel, ppo_loss_kernel)
+# Losses (losses.hip l1_loss_kernel, l1_nhwc16_kernel, bin_l1_kernel, ppo_loss_kernel)
 # ----------------------------------------------------------------------------------------------------------------------------------
 PARTS = 1024      # M2H_PARTS: the block cap of l1_loss / bin_l1_loss / grad_clip_coef
 LOSS_MUTANTS = ("1/n in place of 1/(2 npix)", "the tie gradient not zero")
@@ -1384,7 +1385,7 @@ def loss_fp32(row, inp, mutant=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
-# Gradient clipping + Adam (rl_ops.hip sumsq_kernel, clip_coef_kernel, adam_kernel)
+# Gradient clipping + Adam (optim.hip sumsq_kernel, clip_coef_kernel, adam_kernel)
 # ----------------------------------------------------------------------------------------------------------------------------------
 ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = 2.5e-4, 0.9, 0.999, 1e-5
 ADAM_CAP = 2048       # adam_kernel's block cap
