@@ -787,6 +787,28 @@ int m2h_score_gram_lag(const float* refs, long long refs_sr, long long refs_ss, 
                        const float* mix, long long mix_sr, long long mix_sc, double* out, int R, int S, int C, long long L, int tile, const int* lag, int D,
                        m2h_stream stream);
 
+/* Scorer, STFT distance (m2h/audio/score.py, "Spectral"; csrc/score_spectral.hip).  Tiles are one second, 16000 samples, of the region
+ * [D, L - D) of every row (D = 0 and lag = NULL: the whole row), J = ceil((L - 2 D) / 16000).  For (r, c) the three signals, taken raw,
+ * are g = refs[r][target_r][c][D + t], e = est[r][c][D + lag[r * C + c] + t] and the baseline b = mix[r][c][D + t] for C = 2,
+ * 0.5 (mix[r][0] + mix[r][1])[D + t] for C = 1.  A tile's spectrogram is the Separator's: the tile zero-extended to 16000 samples,
+ * reflect-padded by 511 inside the tile, 32 frames of 1023 samples every 512, periodic Hann, 1023-point DFT, bins 0 .. 511.
+ *   out [R][C][J][7] fp64, sums over the 512 x 32 bins of a tile:
+ *     0 |G|^2   1 |E|^2   2 |B|^2   3 (|E| - |G|)^2   4 |E - G|^2   5 (|B| - |G|)^2   6 |B - G|^2
+ * The transform runs on the exact fp32 matrix instruction; magnitudes and differences are fp32, every square is converted to fp64
+ * before it is added; the summation order is fixed (no atomics) and does not depend on the batch, the strides or a row's alignment.
+ * dft: the folded transform table, window included, 32 * 128 * 2 * 64 floats ON THE DEVICE (m2h.audio.score.spectral_table):
+ *   dft[((bt * 128 + ks) * 2 + q) * 64 + l] = w[n] cos(2 pi k n / 1023) for q = 0, -w[n] sin(2 pi k n / 1023) for q = 1,
+ *   n = 4 ks + (l >> 4), k = 16 bt + (l & 15), w = float32(periodic Hann of 1023 points); computed in fp64 and rounded once.
+ * (The kernel applies row n to x[n] + x[1023 - n] for q = 0 and to x[n] - x[1023 - n] for q = 1; w[0] = 0.)
+ * refs, est, mix and the strides are m2h_score_gram's (elements, 64-bit, any value; rows read in place at any alignment; no read leaves
+ * [row start, row start + L)).  target: [R] 64-bit reference indices ON THE DEVICE (clamped to [0, S) before use), or NULL: target0
+ * for every recording.  lag: [R * C] int32 ON THE DEVICE, clamped to [-D, D] before use, with 1 <= D <= 8192; or NULL with D = 0.
+ * Returns a negative status and launches nothing for a null pointer, S outside 1 .. 6, C outside {1, 2}, R < 1, D outside 0 .. 8192
+ * or not matching lag, L < 2 D + 1, a target0 outside [0, S) when target is NULL, or more than 2^31 - 1 (r, c, j) triples. */
+int m2h_score_spectral(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                       const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0, const float* dft, double* out,
+                       int R, int S, int C, long long L, const int* lag, int D, m2h_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-network runner: one C call enqueues every kernel of one separator U-Net forward (K1/K2 slice, 5 down stages, 5 up
  * stages, head) = PassiveSepEncCNN.forward + PassiveSepDecCNN.forward (separator_cnn.py:70-108,153-170) in eval mode.  Same

@@ -64,6 +64,35 @@ m2h_score_gram reading the region with the estimate moved by the lag, which it t
 Recordings are processed in groups whose ct stays under `max_corr_bytes` (a single recording above it goes alone); they are
 independent, so grouping changes no bit.  No host synchronisation, and no copy from the host apart from the twiddle table on a
 Scorer's first aligned call.  Not done: sub-sample lags, caller-supplied lags, inputs of unequal length.
+
+Spectral.  score(..., spectral=True) adds the paper's other number, the STFT distance (common/eval_metrics.py:306-366,
+STFT_L2_distance), per window and over the whole recording, next to the eleven above, which do not change by a bit.  The tile must be
+16000 (one second, the Separator's segment): any other tile is a ValueError that names it, before any launch.  For recording r and
+channel c the three signals are taken RAW -- no mean is removed, because the reference's spectrograms are of the raw audio:
+g = references[r, target_r, c], e = estimate[r, c], and the baseline b = 0.5 (mixture[r, 0] + mixture[r, 1]) for C = 1, mixture[r, c]
+for C = 2.  Tiles and windows are score_plan's / align_plan's; with align=D the same region [D, L - D) is used and the estimate is read
+lag[r, c] samples later, exactly as m2h_score_gram_lag reads it.  The spectrogram of a tile is the one the Separator's U-Net sees for
+that second (m2h/separate.py, m2h.audio.stft.STFT, oracle.np_stft): the tile's samples zero-extended to 16000 where the recording ends,
+reflect-padded by 511 on both sides INSIDE THE TILE (np.pad(mode="reflect"); neighbouring seconds are never read), 32 frames of 1023
+samples every 512, the periodic Hann window rounded to float32, a 1023-point DFT, bins 0 .. 511: F = 512, T = 32.  With G, E, B the
+complex spectrograms of g, e, b, a tile's seven sums over its F T bins are
+
+  0 sum |G|^2   1 sum |E|^2   2 sum |B|^2   3 sum (|E| - |G|)^2   4 sum |E - G|^2   5 sum (|B| - |G|)^2   6 sum |B - G|^2
+
+and a window's sums are its tiles' sums added in tile order (m2h_score_windows).  With Q the window's tile count (J for the whole
+recording) the eight numbers, in SPECTRAL_ORDER, float64:
+
+  stft_l2 = sums[3] / (2 F T Q)          stft_l2_complex = sums[4] / (2 F T Q)          sc = sqrt(sums[3] / sums[0])
+  stft_l2_base, stft_l2_complex_base, sc_base: the same with sums 5, 6 and 5 / 0
+  stft_l2i = stft_l2_base - stft_l2      stft_l2_complexi = stft_l2_complex_base - stft_l2_complex     (positive: better than the mixture)
+
+stft_l2 is the reference's mono number: the mean over (re, im), F and T of the squared distance with the ground truth's phase on both
+sides, which reduces to (|E| - |G|)^2; for a one-second recording it is STFT_L2_distance(...)[1] with pred_mono = |STFT(e)| and
+gt_mono_comps = (|G|, angle G).  For C = 2 the paper's binaural number is the two ears' stft_l2 ADDED; that addition is left to the
+caller.  Q = 0 gives NaN; otherwise IEEE rules apply (a silent target makes sc NaN or inf).  m2h_score_spectral (csrc/score_spectral.hip)
+computes the seven sums of every tile straight from the waveforms -- the transform on the exact fp32 matrix instruction, squares added
+in fp64, no frame or spectrum ever in memory -- and spectral_from_sums does the rest in torch float64.  No host synchronisation, and no
+copy from the host apart from the transform table on a Scorer's first spectral call.
 """
 import operator
 
@@ -79,6 +108,9 @@ MAX_ALIGN = 8192             # the largest `align`, in samples
 ALIGN_NFFT = 32768           # the correlation's transform: tile + 2 align samples must fit
 DEFAULT_MAX_CORR_BYTES = 1 << 30
 _NAN = float("nan")
+SPECTRAL_ORDER = ("stft_l2", "stft_l2_complex", "sc", "stft_l2_base", "stft_l2_complex_base", "sc_base", "stft_l2i", "stft_l2_complexi")
+SPECTRAL_TILE = 16000        # spectral=True: one second, the Separator's segment
+SPECTRAL_BINS, SPECTRAL_FRAMES, SPECTRAL_NFFT = 512, 32, 1023
 
 
 def score_plan(L, tile=DEFAULT_TILE, window=1, hop=1):
@@ -293,6 +325,35 @@ def target_energy(gram, n, target):
     return energy[..., int(target)]
 
 
+def spectral_table():
+    """m2h_score_spectral's transform table (include/m2h.h), numpy float32 [32, 128, 2, 64]: the window folded into the DFT rows,
+    t[bt, ks, 0, l] = w[n] cos(2 pi k n / 1023), t[bt, ks, 1, l] = -w[n] sin(2 pi k n / 1023) with n = 4 ks + (l >> 4),
+    k = 16 bt + (l & 15), w the periodic Hann window rounded to float32; built in float64 (the angle reduced in integers) and rounded
+    once.  Rows n = 1 .. 511 serve their mirror images 1023 - n too: w and cos are even and sin is odd about 1023 / 2, and w[0] = 0."""
+    import numpy as np
+    N, nb = SPECTRAL_NFFT, SPECTRAL_BINS
+    n, k = np.arange(nb), np.arange(nb)
+    w = (0.5 - 0.5 * np.cos(2.0 * np.pi * n / N)).astype(np.float32).astype(np.float64)
+    ang = 2.0 * np.pi * ((k[:, None] * n[None, :]) % N) / N                             # [k, n]
+    t = np.stack([w * np.cos(ang), -w * np.sin(ang)])                                   # [q, k, n]
+    t = t.reshape(2, nb // 16, 16, nb // 4, 4).transpose(1, 3, 0, 4, 2)                 # [q, bt, k & 15, ks, n & 3] -> [bt, ks, q, n & 3, k & 15]
+    return np.ascontiguousarray(t.reshape(nb // 16, nb // 4, 2, 64).astype(np.float32))
+
+
+def spectral_from_sums(sums, Q):
+    """The eight spectral numbers (module docstring, "Spectral") from the seven sums, element-wise in torch float64 on sums' device.
+
+    sums [..., 7] float64; Q the tile count: a number, or a tensor that broadcasts against sums.shape[:-1] -> [..., 8] in SPECTRAL_ORDER."""
+    if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64:
+        raise TypeError("m2h.Scorer: spectral sums must be a float64 torch tensor, got %s" % (sums.dtype if isinstance(sums, torch.Tensor) else type(sums).__name__))
+    if sums.dim() < 1 or sums.shape[-1] != 7:
+        raise ValueError("m2h.Scorer: spectral sums hold 7 numbers per row, got a tensor of shape %s" % (tuple(sums.shape),))
+    den = 2.0 * SPECTRAL_BINS * SPECTRAL_FRAMES * _count(Q, sums.device).expand(sums.shape[:-1])
+    l2, l2c, sc = sums[..., 3] / den, sums[..., 4] / den, torch.sqrt(sums[..., 3] / sums[..., 0])
+    l2b, l2cb, scb = sums[..., 5] / den, sums[..., 6] / den, torch.sqrt(sums[..., 5] / sums[..., 0])
+    return torch.stack([l2, l2c, sc, l2b, l2cb, scb, l2b - l2, l2cb - l2c], dim=-1)
+
+
 class Scorer:
     def __init__(self, device, max_corr_bytes=DEFAULT_MAX_CORR_BYTES):
         if isinstance(max_corr_bytes, bool) or int(max_corr_bytes) < 1:
@@ -300,6 +361,7 @@ class Scorer:
         self.device = torch.device(device)
         self.max_corr_bytes = int(max_corr_bytes)   # align: recordings are processed in groups whose tile correlations stay under this
         self._twiddles = None
+        self._dft = None
         self._timing = None          # tools/score_bench.py: a list that receives (stage, event) marks
 
     def _twiddle_table(self):
@@ -307,6 +369,12 @@ class Scorer:
         if self._twiddles is None:
             self._twiddles = device_twiddles(self.device, ALIGN_NFFT)
         return self._twiddles
+
+    def _spectral_table(self):
+        """spectral_table() on the device, copied from the host once"""
+        if self._dft is None:
+            self._dft = torch.from_numpy(spectral_table()).to(self.device)
+        return self._dft
 
     def _mark(self, stage):
         if self._timing is not None:
@@ -371,12 +439,15 @@ class Scorer:
                 raise ValueError("m2h.Scorer: %s must live on %s, got %s; the scorer has no CPU path" % (name, self.device, t.device))
         return refs, est, target, plan
 
-    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None):
+    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None, spectral=False):
         """-> {"whole": [R, C, 11], "track": [R, C, M, 11], "active": [R, C, M] bool, "plan": score_plan(...)}; float64 on the device, in
         eval_metrics.METRIC_ORDER; no host synchronisation.  With align=D (an int, the largest lag searched in samples) the estimate is
         aligned to its target first: also "lag": [R, C] int32 and "lag_track": [R, C, M] int32 on the device, and "plan" is
-        align_plan(...).  The module docstring holds the definition."""
+        align_plan(...).  With spectral=True (tile must be 16000) also "spectral_whole": [R, C, 8] and "spectral_track": [R, C, M, 8],
+        float64 in SPECTRAL_ORDER.  The module docstring holds the definition."""
         refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align)
+        if spectral and plan["tile"] != SPECTRAL_TILE:
+            raise ValueError("m2h.Scorer: spectral=True needs tile = %d (one second), got %d" % (SPECTRAL_TILE, plan["tile"]))
         R, S, C, L = refs.shape
         J, M, tile, window, hop = (plan[k] for k in ("J", "M", "tile", "window", "hop"))
         D = plan.get("offset", 0)
@@ -415,6 +486,14 @@ class Scorer:
             scores = metrics_from_gram(gram, n, target, C)
             active = target_energy(gram[:, :, 1:], n[1:], target) > 0
             self._mark("metrics")
+            if spectral:
+                sums = ops.score_spectral(refs, est, mixture, target, self._spectral_table(), out.get("lag"), D)        # [R, C, J, 7]
+                self._mark("score_spectral")
+                sums = torch.cat([ops.score_windows(sums, 1, J, 1), ops.score_windows(sums, M, window, hop)], dim=2)
+                q = (torch.clamp(m + window, max=J) - torch.clamp(m, max=J)).to(torch.float64)
+                spec = spectral_from_sums(sums, torch.cat([torch.full((1,), float(J), dtype=torch.float64, device=dev), q]))
+                out.update({"spectral_whole": spec[:, :, 0], "spectral_track": spec[:, :, 1:]})
+                self._mark("spectral_metrics")
         out.update({"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan})
         return out
 
@@ -432,5 +511,17 @@ def summarize(result):
                 rows = track[r, c][active[r, c]]
                 if rows.shape[0]:
                     mean[r, c], median[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
-    return {"metrics": list(METRIC_ORDER), "whole": whole.tolist(), "track_mean": mean.tolist(), "track_median": median.tolist(),
-            "active_windows": active.sum(axis=-1).tolist()}
+    out = {"metrics": list(METRIC_ORDER), "whole": whole.tolist(), "track_mean": mean.tolist(), "track_median": median.tolist(),
+           "active_windows": active.sum(axis=-1).tolist()}
+    if "spectral_whole" in result:                                                      # score(..., spectral=True): the same over the same windows
+        sw, st = result["spectral_whole"].cpu().numpy(), result["spectral_track"].cpu().numpy()
+        smean, smedian = np.full((R, C, 8), np.nan), np.full((R, C, 8), np.nan)
+        with np.errstate(all="ignore"):
+            for r in range(R):
+                for c in range(C):
+                    rows = st[r, c][active[r, c]]
+                    if rows.shape[0]:
+                        smean[r, c], smedian[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
+        out.update({"spectral_metrics": list(SPECTRAL_ORDER), "spectral_whole": sw.tolist(), "spectral_track_mean": smean.tolist(),
+                    "spectral_track_median": smedian.tolist()})
+    return out

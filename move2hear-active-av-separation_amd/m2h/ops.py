@@ -821,6 +821,42 @@ def score_gram_lag(refs, est, mix, tile, lag, D):
     return out
 
 
+SPECTRAL_TABLE_SHAPE = (32, 128, 2, 64)      # m2h_score_spectral's folded transform table (include/m2h.h)
+
+
+def score_spectral(refs, est, mix, target, dft, lag=None, D=0):
+    """Tile sums of the Scorer's STFT distance (m2h/audio/score.py, "Spectral"): refs [R, S, C, L], est [R, C, L], mix [R, 2, L] fp32 with
+    unit last stride (views are read in place); target an int, or an int64 tensor [R] on the device; dft: the [32, 128, 2, 64] table of
+    m2h.audio.score.spectral_table on the device; lag [R, C] int32 on the device with D in 1 .. 8192 (the region [D, L - D), the estimate
+    read lag[r, c] samples later), or None with D = 0 -> [R, C, J, 7] fp64, J = ceil((L - 2 D) / 16000) (include/m2h.h)."""
+    R, S, C, L = _score_signals("score_spectral", refs, est, mix)
+    D = int(D)
+    if not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
+        raise RuntimeError("m2h.score_spectral: D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required" % (D, L))
+    _chk(dft, "score_spectral(dft)")
+    if tuple(dft.shape) != SPECTRAL_TABLE_SHAPE or dft.device != refs.device:
+        raise RuntimeError("m2h.score_spectral: dft must be the %s table on %s" % (list(SPECTRAL_TABLE_SHAPE), refs.device))
+    if lag is not None:
+        _chk(lag, "score_spectral(lag)", torch.int32)
+        if tuple(lag.shape) != (R, C) or lag.device != refs.device:
+            raise RuntimeError("m2h.score_spectral: lag must be [R, C] = [%d, %d] int32 on %s" % (R, C, refs.device))
+    if isinstance(target, torch.Tensor):
+        if target.dtype != torch.int64 or tuple(target.shape) != (R,) or target.device != refs.device or not target.is_contiguous():
+            raise RuntimeError("m2h.score_spectral: a tensor `target` must be a contiguous int64 [R] = [%d] on %s" % (R, refs.device))
+        tptr, t0 = _ptr(target), 0
+    else:
+        tptr, t0 = None, int(target)
+        if not 0 <= t0 < S:
+            raise RuntimeError("m2h.score_spectral: target = %d is not one of the S = %d references" % (t0, S))
+    out = torch.empty((R, C, -(-(L - 2 * D) // 16000), 7), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_score_spectral(_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1),
+                                          _ptr(mix), mix.stride(0), mix.stride(1), tptr, t0, _ptr(dft), _ptr(out), R, S, C, L,
+                                          None if lag is None else _ptr(lag), D, _stream(refs)), "m2h_score_spectral")
+    return out
+
+
 def score_windows(tiles, M, window, hop):
     """tiles [R, C, J, K] fp64 -> [R, C, M, K]: every window's tiles added in tile order (window m: tiles m * hop .. m * hop + window - 1)."""
     _chk(tiles, "score_windows", torch.float64)

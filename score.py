@@ -2,7 +2,7 @@
 """Score a separated recording of any length against its ground truth:
 
     python score.py --estimate out.wav --mixture mix.wav --reference target.wav [--reference other.wav ...] [--window W --hop H]
-                    [--align D] [--json scores.json]
+                    [--align D] [--spectral] [--json scores.json]
 
 ``--reference``: the sources as they are in the mixture, at most six; the FIRST one is the target the estimate is scored against, the
 others are the interferers (they enter SI-SIR and SI-SAR).  ``render.py --out-target / --out-image`` writes such files.  ``--mixture``:
@@ -18,6 +18,11 @@ scoring).  The files still need equal lengths.
 The recording is scored as a whole and in windows of ``--window`` seconds, one every ``--hop`` seconds (defaults 1 and 1).  Printed:
 the whole-recording metrics, then the mean and the median of every metric over the active windows (those in which the target is not
 silent).  ``--json`` writes everything, the per-window track included.  Definition: m2h/audio/score.py.
+
+``--spectral`` adds the paper's STFT distance and its relatives (``stft_l2``, the complex distance, the spectral convergence, the same
+for the mixture as the estimate, and the two improvements; m2h/audio/score.py, "Spectral") for the same whole recording and the same
+windows, as rows under the table and as ``spectral_*`` keys in the JSON.  For two-channel files the paper's binaural distance is the
+sum of the two ears' ``stft_l2``.
 """
 import argparse
 import json
@@ -51,6 +56,7 @@ def main():
     parser.add_argument("--window", type=int, default=1, help="window length in seconds")
     parser.add_argument("--hop", type=int, default=1, help="a window every HOP seconds")
     parser.add_argument("--align", type=int, default=None, metavar="D", help="align the estimate to the target first: the largest lag searched, in samples (1 .. 8192)")
+    parser.add_argument("--spectral", action="store_true", help="also the STFT distance per window and over the whole recording")
     parser.add_argument("--json", default=None, help="write every number here")
     args = parser.parse_args()
     import numpy as np
@@ -73,7 +79,8 @@ def main():
     dev = torch.device("cuda", 0)
     try:
         res = Scorer(dev).score(torch.from_numpy(np.ascontiguousarray(est)).to(dev)[None], torch.from_numpy(np.stack(refs)).to(dev)[None],
-                                torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop, align=args.align)
+                                torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop, align=args.align,
+                                spectral=args.spectral)
     except (ValueError, TypeError) as e:
         raise SystemExit("score.py: %s" % e)
     s = summarize(res)
@@ -93,12 +100,21 @@ def main():
         for label, key in (("whole", "whole"), ("window mean", "track_mean"), ("window median", "track_median")):
             print("%-8s %-14s" % (names[c], label) + " ".join("%13.7f" % v for v in s[key][0][c]))
         print("%-8s %d of %d windows active" % (names[c], s["active_windows"][0][c], plan["M"]))
+    if args.spectral:
+        print("%-8s %-23s" % ("spectral", "") + " ".join("%20s" % m for m in s["spectral_metrics"]))
+        for c in range(C):
+            for label, key in (("spectral whole", "spectral_whole"), ("spectral window mean", "spectral_track_mean"), ("spectral window median", "spectral_track_median")):
+                print("%-8s %-23s" % (names[c], label) + " ".join("%20.12e" % v for v in s[key][0][c]))
     if args.json is not None:
         out = {"estimate": args.estimate, "mixture": args.mixture, "references": args.reference, "sample_rate": separate.SAMPLE_RATE,
                "samples": L, "channels": list(names), "window_s": args.window, "hop_s": args.hop, "metrics": s["metrics"],
                "whole": s["whole"][0], "track_mean": s["track_mean"][0], "track_median": s["track_median"][0],
                "active_windows": s["active_windows"][0], "windows": [list(w) for w in plan["samples"]],
                "track": res["track"][0].cpu().numpy().tolist(), "active": res["active"][0].cpu().numpy().tolist()}
+        if args.spectral:
+            out.update({"spectral_metrics": s["spectral_metrics"], "spectral_whole": s["spectral_whole"][0],
+                        "spectral_track": res["spectral_track"][0].cpu().numpy().tolist(), "spectral_track_mean": s["spectral_track_mean"][0],
+                        "spectral_track_median": s["spectral_track_median"][0]})
         if args.align is not None:
             out.update({"align": args.align, "region": [t0, t1], "lag": lag, "lag_track": res["lag_track"][0].cpu().tolist()})
         with open(args.json, "w") as f:

@@ -5,6 +5,8 @@
     python tools/score_bench.py --case 16x3x600c2                    # one case in this process
     python tools/score_bench.py --align 1024 --align 8192 --out profiles/score_align_bench.json     # the aligned scorer, every case at every D
     python tools/score_bench.py --case 1x2x60c2 --align 8192         # one case of it in this process
+    python tools/score_bench.py --spectral --out profiles/score_spectral_bench.json                 # the STFT distance, every case
+    python tools/score_bench.py --case 16x3x600c1 --spectral         # one case of it in this process
 
 Cases (R recordings x S sources x seconds, C channels): 16x3x600 and 1x2x60, each with C = 1 and C = 2; per-second windows.  Timing: HIP
 events on the stream around the Gram launch and around everything after it (Scorer._timing), summed over the repetitions.
@@ -25,6 +27,14 @@ With --align D (Scorer.score(..., align=D); the estimate is the unaligned case's
   torch_fft_corr_ms       the whole-recording correlation from torch.fft in the same run, before and after: rfft of the target and of the
                           estimate zero-padded to the next power of two at or above 2 L, conj(S) X, irfft, the lags -D .. D sliced out
                           (two recordings at a time above 2^26 points); whether its lags equal the Scorer's is recorded
+With --spectral (the m2h_score_spectral launch of Scorer.score(..., spectral=True), timed alone with HIP events):
+  spectral_ms             one launch: the seven fp64 sums of every (recording, channel, second) straight from the waveforms
+  flops_unfolded, share_of_fp32_matrix_peak   3 signals x 32 frames x 2 (re, im) x 1023 x 1024 flop per tile -- the count of the unfolded
+                          transform, which the kernel halves by folding x[n] +- x[1023 - n] -- over spectral_ms, against 157.3 TFLOP/s
+  stored_spectrum_ms      the same sums from the existing pieces in the same run, before and after: m2h_stft_frames and the fp32 GEMM of
+                          m2h.audio.stft.STFT on the three signals' seconds (frames and spectra stored), then torch float64 reductions,
+                          one recording at a time; its largest relative difference from the kernel's sums is recorded
+  extra_ms_in_score       what spectral=True adds to one Scorer.score (launch, two m2h_score_windows, spectral_from_sums)
 No threshold is set anywhere: the file reports what came out.  Every GPU step runs under its own timeout and the driver stops at the
 first failure.
 """
@@ -124,6 +134,86 @@ def run_case(case):
     return res
 
 
+FP32_MATRIX_PEAK = 157.3e12
+SPECTRAL_FLOPS_PER_TILE = 3 * 32 * 2 * 1023 * 1024
+
+
+def stored_spectrum_sums(stft, g, e, b):
+    """[R, C, J, 7] float64 from the existing pieces: g, e, b [R, C, L] (L a multiple of a second) -> frames and spectra of every second
+    stored by m2h_stft_frames and the fp32 GEMM of `stft`, then torch float64 reductions; one recording at a time"""
+    import torch
+    from m2h import _lib, ops
+    lib = _lib.load()
+    R, C, L = g.shape
+    J, T, nb = L // SEG, 32, stft.nb
+    out = []
+    for r in range(R):
+        wave = torch.stack([g[r], e[r], b[r]]).reshape(3 * C * J, SEG).contiguous()
+        frames = torch.empty((3 * C * J * T, stft.ld), device=g.device)
+        _lib.check(lib.m2h_stft_frames(ops._ptr(wave), ops._ptr(stft.window), ops._ptr(frames), 3 * C * J, SEG, T, stft.n_fft, stft.hop, stft.ld,
+                                       ops._stream(wave)), "m2h_stft_frames")
+        spec = ops.linear(frames, stft.W, None, name="stft.dft").view(3, C, J, T, stft.ld)
+        re, im = spec[..., :nb].double(), spec[..., nb:2 * nb].double()
+        mag = torch.sqrt(re * re + im * im)
+        tot = lambda x: x.sum(dim=(-2, -1))                                              # noqa: E731
+        dist = lambda i: (tot((mag[i] - mag[0]) ** 2), tot((re[i] - re[0]) ** 2 + (im[i] - im[0]) ** 2))   # noqa: E731
+        out.append(torch.stack([tot(mag[0] ** 2), tot(mag[1] ** 2), tot(mag[2] ** 2), *dist(1), *dist(2)], dim=-1))
+    return torch.stack(out)
+
+
+def run_spectral_case(case):
+    import torch
+    from m2h import ops
+    from m2h.audio.score import Scorer
+    from m2h.audio.stft import STFT
+    if not torch.cuda.is_available():
+        raise SystemExit("score_bench: no GPU; this measurement has no CPU path")
+    R, S, seconds, C, reps = CASES[case]
+    dev = torch.device("cuda", 0)
+    L = seconds * SEG
+    g = torch.Generator(device=dev).manual_seed(7)
+    refs = torch.randn((R, S, C, L), device=dev, generator=g) * 0.1 + 0.01
+    mix = torch.stack([refs[:, :, 0].mean(1), refs[:, :, C - 1].mean(1)], dim=1) + 0.02 * torch.randn((R, 2, L), device=dev, generator=g)
+    est = 0.8 * refs[:, 0] + 0.03 * torch.randn((R, C, L), device=dev, generator=g)
+    sc, stft = Scorer(dev), STFT(dev)
+    table = sc._spectral_table()
+    base = mix if C == 2 else 0.5 * (mix[:, :1] + mix[:, 1:])
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    kernel = lambda: ops.score_spectral(refs, est, mix, 0, table)                       # noqa: E731
+    stored = lambda: stored_spectrum_sums(stft, refs[:, 0], est, base)                  # noqa: E731
+    res0 = sc.score(est, refs, mix, spectral=True)                                      # warm-up of every shape
+    got, want = kernel(), stored()
+    diff = float(((got - want).abs() / want.abs().clamp_min(1e-300)).max())
+    del want
+    torch.cuda.synchronize()
+    n_stored = max(1, reps // 10)
+    before = timed(stored, n_stored)
+    ms = timed(kernel, reps)
+    plain = timed(lambda: sc.score(est, refs, mix), reps)
+    full = timed(lambda: sc.score(est, refs, mix, spectral=True), reps)
+    after = timed(stored, n_stored)
+    ms2 = timed(kernel, reps)
+    flops = R * C * seconds * SPECTRAL_FLOPS_PER_TILE
+    res = {"case": case, "spectral": True, "R": R, "S": S, "C": C, "audio_seconds_per_recording": seconds, "reps": reps, "tiles": R * C * seconds,
+           "spectral_ms": [ms, ms2], "flops_unfolded": flops, "flops_per_s_unfolded": flops / (min(ms, ms2) * 1e-3),
+           "share_of_fp32_matrix_peak": flops / (min(ms, ms2) * 1e-3) / FP32_MATRIX_PEAK, "stored_spectrum_ms": [before, after],
+           "stored_spectrum_reps": n_stored, "stored_over_kernel": 0.5 * (before + after) / (0.5 * (ms + ms2)), "score_ms": plain,
+           "score_spectral_ms": full, "extra_ms_in_score": full - plain, "audio_s_per_s": R * seconds / (full * 1e-3),
+           "kernel_vs_stored_max_rel": diff, "stft_l2_whole": float(res0["spectral_whole"][0, 0, 0])}
+    print(json.dumps(res))
+    return res
+
+
 def run_align_case(case, D):
     import torch
     from m2h.audio.score import Scorer, lags_from_corr
@@ -200,11 +290,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", choices=sorted(CASES), default=None)
     ap.add_argument("--align", type=int, action="append", default=None, metavar="D", help="measure the aligned scorer at this largest lag (repeat)")
+    ap.add_argument("--spectral", action="store_true", help="measure the STFT distance's launch (Scorer.score(..., spectral=True))")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=120, help="driver mode: seconds per case")
     args = ap.parse_args()
+    if args.spectral and args.align:
+        raise SystemExit("score_bench: --spectral and --align are measured separately")
     if args.case is not None:
-        if args.align:
+        if args.spectral:
+            run_spectral_case(args.case)
+        elif args.align:
             for D in args.align:
                 run_align_case(args.case, D)
         else:
@@ -212,7 +307,8 @@ def main():
         return
     results = []
     for case, D in [(case, D) for D in (args.align or [None]) for case in ORDER]:
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case] + ([] if D is None else ["--align", str(D)])
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case] + ([] if D is None else ["--align", str(D)]) + \
+            (["--spectral"] if args.spectral else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             print(r.stdout[-4000:])
@@ -222,7 +318,8 @@ def main():
         print(line, flush=True)
     if args.out:
         with open(args.out, "w") as f:
-            json.dump({"tool": "tools/score_bench.py", "device": "MI355X (gfx950)", "copy_rate_bytes_per_s": COPY_RATE, "results": results}, f, indent=1)
+            json.dump({"tool": "tools/score_bench.py", "device": "MI355X (gfx950)", "copy_rate_bytes_per_s": COPY_RATE,
+                       **({"fp32_matrix_peak_flops_per_s": FP32_MATRIX_PEAK} if args.spectral else {}), "results": results}, f, indent=1)
             f.write("\n")
 
 
