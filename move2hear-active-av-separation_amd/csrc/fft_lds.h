@@ -1,5 +1,10 @@
-// In-LDS radix-2 complex transforms and the packed-real-transform pair algebra, shared by the feeder's one-second convolution
-// (fftconv.hip) and the partitioned renderer (render.hip).
+// In-LDS radix-2 complex transforms, the packed-real-transform pair algebra and what stands around them (the packed load, the
+// bit-reversed slot of a bin, the walk over a thread's pairs, the LDS reservation), shared by three units:
+//   fftconv.hip  the feeder's one-second convolution: bit_rev, load_packed, reserve_transform_lds; the any-block-size fft_dif / ifft_dit on
+//                the natural-order table and a strided pair loop of its own (at LOGM = 10 a block has more threads than pairs)
+//   render.hip   the partitioned renderer: the unrolled transforms; render_spectra_kernel all of the helpers, render_frames_kernel
+//                bit_rev under its own grouped product loop
+//   align.hip    the Scorer's cross-correlation: the unrolled transforms and all of the helpers, twice each
 //
 // A real N-point transform is one complex M = N/2-point transform of z[m] = x[2m] + i x[2m+1] plus an O(N) unpack; the pair
 // (k, M-k) is all that the unpack, a spectrum product and the re-pack for the inverse need:
@@ -7,7 +12,7 @@
 //   inverse : the same butterfly network run backwards with conjugate twiddles: bit-reversed in -> natural order out.
 // Twiddles tw[k] = exp(-2 pi i k / (2M)), k < M, come from a table built on the host in float64.  Arithmetic fp32 throughout.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "m2h_internal.h"
 
 namespace m2h {
 
@@ -40,6 +45,40 @@ __device__ __forceinline__ void rfft_repack(cf t, cf yk, cf ymc, cf& zk, cf& zm)
 
 // Slot 0 of a packed transform holds the two real bins: S[0] = Z0.x + Z0.y, S[M] = Z0.x - Z0.y; and back.
 __device__ __forceinline__ cf rfft_repack_dc(float y0, float ym) { return {0.5f * (y0 + ym), 0.5f * (y0 - ym)}; }
+
+// The forward transform leaves bin k of M = 2^LOGM in slot bit_rev(k), and the inverse reads it there.
+template <int LOGM>
+__device__ __forceinline__ int bit_rev(int k) { return (int)(__brev((unsigned)k) >> (32 - LOGM)); }
+
+// z[m] = {src[2m], src[2m+1]} at element stride es, zero from sample n on; a block of NT threads.
+template <int LOGM, int NT>
+__device__ __forceinline__ void load_packed(cf* z, const float* __restrict__ src, int n, int es = 1) {
+  for (int m = threadIdx.x; m < 1 << LOGM; m += NT)
+    z[m] = {2 * m < n ? src[(size_t)(2 * m) * es] : 0.f, 2 * m + 1 < n ? src[(size_t)(2 * m + 1) * es] : 0.f};
+}
+
+// The pairs (k, M-k) a thread of a block of NT owns: k = tid + NT i < M/2, unrolled -- dc(i) for k = 0 (slot 0 and its two real bins),
+// pair(i, k) for every other k -- and on thread 0 half() for k = M/2, its own partner.
+template <int LOGM, int NT, class DC, class Pair, class Half>
+__device__ __forceinline__ void rfft_own_pairs(DC dc, Pair pair, Half half) {
+  static_assert((1 << LOGM) / 2 % NT == 0, "whole pairs per thread");
+#pragma unroll
+  for (int i = 0; i < (1 << LOGM) / 2 / NT; ++i) {
+    const int k = (int)threadIdx.x + NT * i;
+    if (k == 0) dc(i);
+    else pair(i, k);
+  }
+  if (threadIdx.x == 0) half();
+}
+
+// Host: a kernel that holds the whole transform in dynamic LDS (128 KB at LOGM = 14) has to be given leave for more than 64 KB.
+template <int LOGM, class K>
+int reserve_transform_lds(K* kernel, const char* what) {
+  const size_t lds = sizeof(cf) << LOGM;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return fail((int)e, "%s: cannot reserve %zu bytes of LDS: %s", what, lds, hipGetErrorString(e));
+  return 0;
+}
 }  // namespace
 
 // z: M complex values in LDS.  tw[k] = exp(-2 pi i k / (2M)), k < M.

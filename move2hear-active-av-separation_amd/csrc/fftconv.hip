@@ -12,7 +12,7 @@
 // Twiddles exp(-2 pi i k / N) come from a table built on the host in float64 (setup data, like the DFT matrices of the STFT).
 // Arithmetic fp32 throughout, like the library transform it replaces (rocFFT through torch.fft in round 1).
 #include "m2h_internal.h"
-#include "fft_lds.h"   // cf, fft_dif / ifft_dit, the pair-wise unpack and re-pack
+#include "fft_lds.h"   // cf, fft_dif / ifft_dit, the pair-wise unpack and re-pack, the packed load, bit_rev, the LDS reservation
 
 namespace m2h {
 
@@ -25,11 +25,9 @@ __global__ __launch_bounds__(1024) void fftconv_kernel(const float* __restrict__
   const int cs = blockIdx.x, tid = threadIdx.x;
   const int ear0 = blockIdx.y;   // one workgroup per (clip, source, ear): 2 x CS workgroups fill the chip at the feeder's batch (64 x 2
                                  // sources); each redoes the clip's own transform (3 transforms per workgroup instead of 5 in one)
-  auto br = [](int k) { return (int)(__brev((unsigned)k) >> (32 - LOGM)); };
 
   // ---- spectrum of the mono clip (packed, bit-reversed), kept in global scratch for the two ears ----
-  const float* x = mono + (size_t)cs * L;
-  for (int m = tid; m < M; m += 1024) z[m] = {2 * m < L ? x[2 * m] : 0.f, 2 * m + 1 < L ? x[2 * m + 1] : 0.f};
+  load_packed<LOGM, 1024>(z, mono + (size_t)cs * L, L);
   __syncthreads();
   fft_dif<LOGM>(z, tw);
   cf* zx = xspec + ((size_t)cs * 2 + ear0) * M;
@@ -38,8 +36,7 @@ __global__ __launch_bounds__(1024) void fftconv_kernel(const float* __restrict__
   __syncthreads();
 
   for (int ear = ear0; ear <= ear0; ++ear) {
-    const float* h = rirs + (size_t)cs * Lr * 2 + ear;
-    for (int m = tid; m < M; m += 1024) z[m] = {2 * m < Lr ? h[(size_t)(2 * m) * 2] : 0.f, 2 * m + 1 < Lr ? h[(size_t)(2 * m + 1) * 2] : 0.f};
+    load_packed<LOGM, 1024>(z, rirs + (size_t)cs * Lr * 2 + ear, Lr, 2);
     __syncthreads();
     fft_dif<LOGM>(z, tw);
     // ---- per pair (k, M-k): unpack X and H, multiply, re-pack for the inverse; in place, bit-reversed slots ----
@@ -50,7 +47,7 @@ __global__ __launch_bounds__(1024) void fftconv_kernel(const float* __restrict__
         z[0] = rfft_repack_dc(y0, ym);
         continue;
       }
-      const int ik = br(k), im = br(M - k);
+      const int ik = bit_rev<LOGM>(k), im = bit_rev<LOGM>(M - k);
       const cf t = tw[k];
       const cf zhk = z[ik], zhm = z[im], zxk = zx[ik], zxm = zx[im];
       cf ex, ox, eh, oh, zk, zm;
@@ -78,10 +75,8 @@ template <int LOGM>
 static int launch_fftconv(const float* mono, const float* rirs, const float* tw, float* xspec, float* full, int CS, int L, int Lr, hipStream_t st) {
   const size_t lds = sizeof(cf) << LOGM;
   auto kern = fftconv_kernel<LOGM>;
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return fail((int)e, "fftconv_same: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-  }
+  if (lds > 64 * 1024)
+    if (int rc = reserve_transform_lds<LOGM>(kern, "fftconv_same")) return rc;
   M2H_LAUNCH(kern, dim3(CS, 2), dim3(1024), lds, st, mono, rirs, reinterpret_cast<const cf*>(tw), reinterpret_cast<cf*>(xspec), full, L, Lr);
   return launch_status("fftconv_same");
 }

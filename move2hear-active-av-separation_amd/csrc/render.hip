@@ -32,8 +32,6 @@ constexpr int RLOGM = 14;              // packed transform: 2^14 complex points 
 constexpr int RM = 1 << RLOGM;
 constexpr int RFRAME = 2 * RB;         // samples of a frame that are kept (index 31 999 is the circular result's first zero)
 constexpr int RMAXP = 16;              // RIR partitions: Lr <= 256 000
-
-__device__ __forceinline__ int br14(int k) { return (int)(__brev((unsigned)k) >> (32 - RLOGM)); }
 }  // namespace
 
 // grid (nblk, n_mid * n_inner, n_outer).  Row (o, c, i) starts at x + o * outer_stride + c * mid_stride + i * inner_stride and has row_len
@@ -43,34 +41,26 @@ __global__ __launch_bounds__(1024) void render_spectra_kernel(const float* __res
                                                               long long row_len, int es, int first_block) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   cf* z = reinterpret_cast<cf*>(smem);
-  const int tid = threadIdx.x;
   const int mid = (int)blockIdx.y / n_inner, inner = (int)blockIdx.y - mid * n_inner;
   const float* row = x + (size_t)blockIdx.z * outer_stride + (size_t)mid * mid_stride + (size_t)inner * inner_stride;
   const long long a = (long long)(first_block + (int)blockIdx.x) * RB;
   const long long left = row_len - a;                      // samples of the row from the block's start on (>= 1: checked by the entry point)
   const int n = left < RB ? (int)left : RB;
-  const float* src = row + (size_t)a * es;
-  for (int m = tid; m < RM; m += 1024) z[m] = {2 * m < n ? src[(size_t)(2 * m) * es] : 0.f, 2 * m + 1 < n ? src[(size_t)(2 * m + 1) * es] : 0.f};
+  load_packed<RLOGM, 1024>(z, row + (size_t)a * es, n, es);
   __syncthreads();
   fft_dif_fixed<RLOGM, 1024>(z, tw + RM);                  // (the table's second half: the same twiddles in stage order)
   cf* out = spec + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * RM;
-  auto pair = [&](int k) {
+  auto pair = [&](int, int k) {
     cf e, to;
-    rfft_unpack(tw[k], z[br14(k)], z[br14(RM - k)], e, to);
+    rfft_unpack(tw[k], z[bit_rev<RLOGM>(k)], z[bit_rev<RLOGM>(RM - k)], e, to);
     out[k] = cadd(e, to);                                  // S[k]
     if (k != RM / 2) out[RM - k] = csub(e, to);            // conj(S[M-k])
   };
-#pragma unroll
-  for (int i = 0; i < RM / 2 / 1024; ++i) {                // the pairs k = tid + 1024 i < M/2 ...
-    const int k = tid + 1024 * i;
-    if (k == 0) {
-      const cf z0 = z[0];
-      out[0] = {z0.x + z0.y, z0.x - z0.y};                 // S[0], S[M]: both real
-    } else {
-      pair(k);
-    }
-  }
-  if (tid == 0) pair(RM / 2);                              // ... and k = M/2, its own partner
+  auto dc = [&](int) {
+    const cf z0 = z[0];
+    out[0] = {z0.x + z0.y, z0.x - z0.y};                   // S[0], S[M]: both real
+  };
+  rfft_own_pairs<RLOGM, 1024>(dc, pair, [&] { pair(0, RM / 2); });
 }
 
 // grid (nm, RS, 2 ears).  xspec [RS][nx][M] holds the source blocks jx0 .. jx0 + nx - 1; hspec [RS][nh][2][Pn][M] the RIRs
@@ -123,8 +113,8 @@ __global__ __launch_bounds__(1024) void render_frames_kernel(const cf* __restric
       } else {
         cf zk, zm;
         rfft_repack(tw[k], yk[i], ymc[i], zk, zm);
-        z[br14(k)] = zk;
-        z[br14(RM - k)] = zm;
+        z[bit_rev<RLOGM>(k)] = zk;
+        z[bit_rev<RLOGM>(RM - k)] = zm;
       }
     }
   }
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(1024) void render_frames_kernel(const cf* __restric
       yh = cadd(yh, cmul(X[RM / 2], H[RM / 2]));
     }
     rfft_repack(tw[RM / 2], yh, conj(yh), zk, zm);
-    z[br14(RM / 2)] = zk;
+    z[bit_rev<RLOGM>(RM / 2)] = zk;
   }
   __syncthreads();
   ifft_dit_fixed<RLOGM, 1024>(z, tw + RM);
@@ -184,13 +174,6 @@ __global__ __launch_bounds__(256) void render_mix_kernel(const float* __restrict
   put(mix + ((size_t)r * 2 + ear) * L_out, acc);
 }
 
-static int reserve_transform_lds(const void* kern, const char* what) {
-  const size_t lds = sizeof(cf) << RLOGM;
-  const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return fail((int)e, "%s: cannot reserve %zu bytes of LDS: %s", what, lds, hipGetErrorString(e));
-  return 0;
-}
-
 }  // namespace m2h
 
 using namespace m2h;
@@ -207,7 +190,7 @@ extern "C" int m2h_render_spectra(const float* x, const float* twiddles, float* 
               "render_spectra: window: blocks [%d, %d) of %d samples do not all start inside a row of %lld samples", first_block, first_block + nblk, RB,
               row_len);
   M2H_REQUIRE((reinterpret_cast<size_t>(spec) & 7) == 0 && (reinterpret_cast<size_t>(twiddles) & 7) == 0, "render_spectra: buffers must be 8-byte aligned");
-  if (int rc = reserve_transform_lds(reinterpret_cast<const void*>(render_spectra_kernel), "render_spectra")) return rc;
+  if (int rc = reserve_transform_lds<RLOGM>(render_spectra_kernel, "render_spectra")) return rc;
   M2H_LAUNCH(render_spectra_kernel, dim3(nblk, n_mid * n_inner, n_outer), dim3(1024), sizeof(cf) << RLOGM, as_stream(stream), x,
              reinterpret_cast<const cf*>(twiddles), reinterpret_cast<cf*>(spec), n_inner, outer_stride, mid_stride, inner_stride, row_len, elem_stride,
              first_block);
@@ -234,7 +217,7 @@ extern "C" int m2h_render_frames(const float* xspec, const float* hspec, const f
   M2H_REQUIRE((reinterpret_cast<size_t>(frames) & 15) == 0 && (reinterpret_cast<size_t>(xspec) & 7) == 0 && (reinterpret_cast<size_t>(hspec) & 7) == 0 &&
                   (reinterpret_cast<size_t>(twiddles) & 7) == 0,
               "render_frames: buffers: frames must be 16-byte aligned, spectra and twiddles 8-byte aligned");
-  if (int rc = reserve_transform_lds(reinterpret_cast<const void*>(render_frames_kernel), "render_frames")) return rc;
+  if (int rc = reserve_transform_lds<RLOGM>(render_frames_kernel, "render_frames")) return rc;
   M2H_LAUNCH(render_frames_kernel, dim3(nm, RS, 2), dim3(1024), sizeof(cf) << RLOGM, as_stream(stream), reinterpret_cast<const cf*>(xspec),
              reinterpret_cast<const cf*>(hspec), reinterpret_cast<const cf*>(twiddles), frames, J, Pn, moving, m0, jx0, nx, kh0, nh);
   return launch_status("render_frames");

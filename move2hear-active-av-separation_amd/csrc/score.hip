@@ -21,22 +21,13 @@
 //
 // m2h_score_windows adds the tiles of every window in tile order: a window's Gram is never a difference of prefix sums, so a
 // window's score does not depend on what precedes it.
-#include "m2h_internal.h"
+#include "score_common.h"
 
 #include <cstdint>
 
 namespace m2h {
 
 constexpr int SCORE_THREADS = 256;
-
-struct ScoreSignals {
-  const float* refs;
-  long long refs_sr, refs_ss, refs_sc;
-  const float* est;
-  long long est_sr, est_sc;
-  const float* mix;
-  long long mix_sr, mix_sc;
-};
 
 template <int N>
 __global__ __launch_bounds__(SCORE_THREADS) void score_gram_kernel(ScoreSignals a, double* __restrict__ out, int C, long long L, int tile,
@@ -46,23 +37,19 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_gram_kernel(ScoreSignals 
   const long long b = blockIdx.x;                      // = (r * C + c) * J + j
   const long long j = b % J, rc = b / J;
   const long long c = rc % C, r = rc / C;
-  // m2h_score_gram_lag: the scored region starts at sample D of every row and the estimate is read lag[r C + c] samples later; what is
-  // read from `lag` is clamped to [-D, D] (device data never becomes an address outside the row).  m2h_score_gram: lag is null, D is 0.
-  long long shift = 0;
-  if (lag) {
-    const int v = lag[rc];
-    shift = v < -D ? -D : (v > D ? D : v);
-  }
+  // m2h_score_gram_lag: the scored region starts at sample D of every row and the estimate is read lag[r C + c] samples later, clamped
+  // to [-D, D].  m2h_score_gram: lag is null, D is 0.
+  const long long shift = score_lag(lag, rc, D);
   const long long t0 = j * (long long)tile + D;
   const long long left = L - j * (long long)tile;
   const int n = left < tile ? (int)left : tile;        // samples of this tile, >= 1
 
   const float* p[N];
 #pragma unroll
-  for (int i = 0; i < S; ++i) p[i] = a.refs + r * a.refs_sr + i * a.refs_ss + c * a.refs_sc + t0;
-  p[S] = a.est + r * a.est_sr + c * a.est_sc + t0 + shift;
-  p[S + 1] = a.mix + r * a.mix_sr + t0;
-  p[S + 2] = a.mix + r * a.mix_sr + a.mix_sc + t0;
+  for (int i = 0; i < S; ++i) p[i] = row(a.refs, r, i, c) + t0;
+  p[S] = row(a.est, r, c) + t0 + shift;
+  p[S + 1] = row(a.mix, r, 0) + t0;
+  p[S + 2] = row(a.mix, r, 1) + t0;
   bool aligned[N];
 #pragma unroll
   for (int i = 0; i < N; ++i) aligned[i] = (reinterpret_cast<uintptr_t>(p[i]) & 15) == 0;
@@ -133,34 +120,17 @@ __global__ __launch_bounds__(256) void score_windows_kernel(const double* __rest
   }
 }
 
-template <int N>
-static void launch_score_gram(const ScoreSignals& a, double* out, int C, long long L, int tile, long long J, unsigned blocks, const int* lag, int D,
-                              hipStream_t st) {
-  M2H_LAUNCH(score_gram_kernel<N>, dim3(blocks), dim3(SCORE_THREADS), 0, st, a, out, C, L, tile, J, lag, D);
-}
-
-// The checks and the launch behind both entry points: L is the number of scored samples per row, which start at sample D.
+// The checks and the launch behind both entry points: the L - 2 D samples from sample D on are scored; D is at least min_D.
 static int score_gram_launch(const char* what, const ScoreSignals& a, double* out, int R, int S, int C, long long L, int tile, const int* lag, int D,
-                             m2h_stream stream) {
-  M2H_REQUIRE(a.refs && a.est && a.mix && out, "%s: null pointer (refs %p, est %p, mix %p, out %p)", what, (const void*)a.refs, (const void*)a.est,
-              (const void*)a.mix, (void*)out);
-  M2H_REQUIRE(S >= 1 && S <= 6, "%s: S = %d reference sources; 1 .. 6 are supported", what, S);
-  M2H_REQUIRE(C == 1 || C == 2, "%s: C = %d channels; 1 or 2 are supported", what, C);
-  M2H_REQUIRE(L >= 1, "%s: L = %lld samples; at least 1 is required", what, L + 2ll * D);
-  M2H_REQUIRE(tile >= 1, "%s: tile = %d samples; at least 1 is required", what, tile);
-  M2H_REQUIRE(R >= 1, "%s: R = %d recordings; at least 1 is required", what, R);
-  const long long J = (L + tile - 1) / tile;
-  M2H_REQUIRE(J <= 0x7fffffffLL / ((long long)R * C), "%s: R * C * ceil(L / tile) = %d * %d * %lld workgroups exceed a grid of 2^31 - 1", what, R, C, J);
-  const unsigned blocks = (unsigned)(J * R * C);
-  const hipStream_t st = as_stream(stream);
-  switch (S + 3) {
-    case 4: launch_score_gram<4>(a, out, C, L, tile, J, blocks, lag, D, st); break;
-    case 5: launch_score_gram<5>(a, out, C, L, tile, J, blocks, lag, D, st); break;
-    case 6: launch_score_gram<6>(a, out, C, L, tile, J, blocks, lag, D, st); break;
-    case 7: launch_score_gram<7>(a, out, C, L, tile, J, blocks, lag, D, st); break;
-    case 8: launch_score_gram<8>(a, out, C, L, tile, J, blocks, lag, D, st); break;
-    default: launch_score_gram<9>(a, out, C, L, tile, J, blocks, lag, D, st); break;
-  }
+                             int min_D, m2h_stream stream) {
+  static decltype(&score_gram_kernel<4>) const kernels[] = {score_gram_kernel<4>, score_gram_kernel<5>, score_gram_kernel<6>,
+                                                            score_gram_kernel<7>, score_gram_kernel<8>, score_gram_kernel<9>};      // N = S + 3
+  long long J;
+  if (int rc = check_signals(what, a, true, out, R, S, C, L, D, min_D, 1)) return rc;
+  if (int rc = check_lag(what, lag, D)) return rc;
+  L -= 2ll * D;
+  if (int rc = check_tiles(what, L, tile, (long long)R * C, J)) return rc;
+  M2H_LAUNCH(kernels[S - 1], dim3((unsigned)(J * R * C)), dim3(SCORE_THREADS), 0, as_stream(stream), a, out, C, L, tile, J, lag, D);
   return launch_status(what);
 }
 
@@ -172,18 +142,13 @@ extern "C" {
 
 int m2h_score_gram(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
                    const float* mix, long long mix_sr, long long mix_sc, double* out, int R, int S, int C, long long L, int tile, m2h_stream stream) {
-  const ScoreSignals a{refs, refs_sr, refs_ss, refs_sc, est, est_sr, est_sc, mix, mix_sr, mix_sc};
-  return score_gram_launch("score_gram", a, out, R, S, C, L, tile, nullptr, 0, stream);
+  return score_gram_launch("score_gram", {{refs, refs_sr, refs_ss, refs_sc}, {est, est_sr, est_sc}, {mix, mix_sr, mix_sc}}, out, R, S, C, L, tile, nullptr, 0, 0, stream);
 }
 
 int m2h_score_gram_lag(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
                        const float* mix, long long mix_sr, long long mix_sc, double* out, int R, int S, int C, long long L, int tile, const int* lag, int D,
                        m2h_stream stream) {
-  M2H_REQUIRE(lag, "score_gram_lag: null pointer (lag)");
-  M2H_REQUIRE(D >= 1 && D <= 8192, "score_gram_lag: D = %d samples; 1 .. 8192 are supported", D);
-  M2H_REQUIRE(L >= 2ll * D + 1, "score_gram_lag: L = %lld samples; at least 2 D + 1 = %lld are required", L, 2ll * D + 1);
-  const ScoreSignals a{refs, refs_sr, refs_ss, refs_sc, est, est_sr, est_sc, mix, mix_sr, mix_sc};
-  return score_gram_launch("score_gram_lag", a, out, R, S, C, L - 2ll * D, tile, lag, D, stream);
+  return score_gram_launch("score_gram_lag", {{refs, refs_sr, refs_ss, refs_sc}, {est, est_sr, est_sc}, {mix, mix_sr, mix_sc}}, out, R, S, C, L, tile, lag, D, 1, stream);
 }
 
 int m2h_score_windows(const double* tiles, double* out, long long RC, long long J, int K, long long M, long long window, long long hop,

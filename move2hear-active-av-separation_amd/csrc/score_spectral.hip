@@ -24,7 +24,7 @@
 // Magnitudes and differences are fp32; every square is converted to double before it is added: a lane's 2 x 16 elements in a fixed order,
 // then score.hip's reduction -- the xor butterfly of a wave, then the eight waves in order.  No atomics: the same bits on every run, and
 // for any batch, stride or alignment around a recording (only the staged values enter the arithmetic).
-#include "m2h_internal.h"
+#include "score_common.h"
 
 namespace m2h {
 
@@ -39,20 +39,11 @@ constexpr int SP_TABLE_BT = SP_KSTEPS * 2 * 64;             // table words per 1
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-struct SpectralSignals {
-  const float* refs;
-  long long refs_sr, refs_ss, refs_sc;
-  const float* est;
-  long long est_sr, est_sc;
-  const float* mix;
-  long long mix_sr, mix_sc;
-};
-
 __device__ __forceinline__ double sq(float v) { return (double)v * (double)v; }
 
 }  // namespace
 
-__global__ __launch_bounds__(SP_THREADS) void score_spectral_kernel(SpectralSignals a, const long long* __restrict__ target, int target0, int S,
+__global__ __launch_bounds__(SP_THREADS) void score_spectral_kernel(ScoreSignals a, const long long* __restrict__ target, int target0, int S,
                                                                     const float* __restrict__ dft, double* __restrict__ out, int C, long long L,
                                                                     long long J, const int* __restrict__ lag, int D) {
   extern __shared__ __attribute__((aligned(16))) float smem[];          // [3][SP_ROW]
@@ -61,21 +52,14 @@ __global__ __launch_bounds__(SP_THREADS) void score_spectral_kernel(SpectralSign
   const long long b = blockIdx.x;                                        // = (r * C + c) * J + j
   const long long j = b % J, rc = b / J;
   const long long c = rc % C, r = rc / C;
-  // device data never becomes an address outside a row: the target is clamped to [0, S), the lag to [-D, D]
-  long long t = target ? target[r] : (long long)target0;
-  t = t < 0 ? 0 : (t > S - 1 ? S - 1 : t);
-  long long shift = 0;
-  if (lag) {
-    const int v = lag[rc];
-    shift = v < -D ? -D : (v > D ? D : v);
-  }
+  const long long t = score_target(target, target0, r, S), shift = score_lag(lag, rc, D);       // clamped to [0, S) and to [-D, D]
   const long long t0 = j * (long long)SP_TILE + D;
   const long long left = L - j * (long long)SP_TILE;
   const int n = left < SP_TILE ? (int)left : SP_TILE;                    // samples of this tile, >= 1; the rest of the second is zeros
-  const float* pg = a.refs + r * a.refs_sr + t * a.refs_ss + c * a.refs_sc + t0;
-  const float* pe = a.est + r * a.est_sr + c * a.est_sc + t0 + shift;
-  const float* pm = a.mix + r * a.mix_sr + (C == 2 ? c * a.mix_sc : 0) + t0;
-  const long long mix_other = C == 2 ? 0 : a.mix_sc;                      // C = 1: the baseline is the mean of the two channels
+  const float* pg = row(a.refs, r, t, c) + t0;
+  const float* pe = row(a.est, r, c) + t0 + shift;
+  const float* pm = row(a.mix, r, 0) + (C == 2 ? c * a.mix.sc : 0) + t0;
+  const long long mix_other = C == 2 ? 0 : a.mix.sc;                      // C = 1: the baseline is the mean of the two channels
 
   float* sg = smem;
   float* se = smem + SP_ROW;
@@ -194,23 +178,18 @@ using namespace m2h;
 extern "C" int m2h_score_spectral(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr,
                                   long long est_sc, const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0,
                                   const float* dft, double* out, int R, int S, int C, long long L, const int* lag, int D, m2h_stream stream) {
-  M2H_REQUIRE(refs && est && mix && dft && out, "score_spectral: null pointer (refs %p, est %p, mix %p, dft %p, out %p)", (const void*)refs,
-              (const void*)est, (const void*)mix, (const void*)dft, (void*)out);
-  M2H_REQUIRE(S >= 1 && S <= 6, "score_spectral: S = %d reference sources; 1 .. 6 are supported", S);
-  M2H_REQUIRE(C == 1 || C == 2, "score_spectral: C = %d channels; 1 or 2 are supported", C);
-  M2H_REQUIRE(R >= 1, "score_spectral: R = %d recordings; at least 1 is required", R);
-  M2H_REQUIRE(D >= 0 && D <= 8192, "score_spectral: D = %d samples; 0 .. 8192 are supported", D);
-  M2H_REQUIRE(lag ? D >= 1 : D == 0, "score_spectral: lag %p with D = %d; a lag table needs D >= 1, none needs D = 0", (const void*)lag, D);
-  M2H_REQUIRE(L >= 2ll * D + 1, "score_spectral: L = %lld samples; at least 2 D + 1 = %lld are required", L, 2ll * D + 1);
-  M2H_REQUIRE(target || (target0 >= 0 && target0 < S), "score_spectral: target = %d is not one of the S = %d references", target0, S);
+  const ScoreSignals a{{refs, refs_sr, refs_ss, refs_sc}, {est, est_sr, est_sc}, {mix, mix_sr, mix_sc}};
+  long long J;
+  if (int rc = check_signals("score_spectral", a, true, out, R, S, C, L, D, 0, 1)) return rc;
+  M2H_REQUIRE(dft, "score_spectral: null pointer (dft)");
+  if (int rc = check_lag("score_spectral", lag, D)) return rc;
+  if (int rc = check_target("score_spectral", target, target0, S)) return rc;
   M2H_REQUIRE((reinterpret_cast<size_t>(out) & 7) == 0, "score_spectral: out must be 8-byte aligned");
   const long long Ls = L - 2ll * D;
-  const long long J = (Ls + SP_TILE - 1) / SP_TILE;
-  M2H_REQUIRE(J <= 0x7fffffffLL / ((long long)R * C), "score_spectral: R * C * ceil(L / 16000) = %d * %d * %lld workgroups exceed a grid of 2^31 - 1", R, C, J);
+  if (int rc = check_tiles("score_spectral", Ls, SP_TILE, (long long)R * C, J)) return rc;
   const size_t lds = sizeof(float) * 3 * SP_ROW;
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(score_spectral_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return fail((int)e, "score_spectral: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-  const SpectralSignals a{refs, refs_sr, refs_ss, refs_sc, est, est_sr, est_sc, mix, mix_sr, mix_sc};
   M2H_LAUNCH(score_spectral_kernel, dim3((unsigned)(J * R * C)), dim3(SP_THREADS), lds, as_stream(stream), a, target, target0, S, dft, out, C, Ls, J, lag,
              D);
   return launch_status("score_spectral");

@@ -731,46 +731,64 @@ def bss_metrics(ref, est, mix_l, mix_r=None):
     return out
 
 
-def score_gram(refs, est, mix, tile):
-    """Tile Grams of the Scorer (m2h/audio/score.py): refs [R, S, C, L], est [R, C, L], mix [R, 2, L] fp32 with unit last stride and
-    any other strides (views are read in place) -> [R, C, J, N + N(N+1)/2] fp64, J = ceil(L / tile), N = S + 3 (include/m2h.h)."""
-    for t in (refs, est, mix):
-        if not t.is_cuda or t.dtype != torch.float32 or t.device != refs.device:
-            raise RuntimeError("m2h.score_gram: float32 tensors on one GPU are required (got %s on %s); the m2h ops have no CPU path" % (t.dtype, t.device))
-    if refs.dim() != 4 or est.dim() != 3 or mix.dim() != 3:
-        raise RuntimeError("m2h.score_gram: refs [R, S, C, L], est [R, C, L] and mix [R, 2, L] are required")
-    R, S, C, L = refs.shape
-    if tuple(est.shape) != (R, C, L) or tuple(mix.shape) != (R, 2, L) or L < 1 or R < 1:
-        raise RuntimeError("m2h.score_gram: refs %s, est %s and mix %s do not agree" % (tuple(refs.shape), tuple(est.shape), tuple(mix.shape)))
-    if L > 1 and any(t.stride(-1) != 1 for t in (refs, est, mix)):
-        raise RuntimeError("m2h.score_gram: the last stride must be 1")
-    tile = int(tile)
-    if tile < 1 or not 1 <= S <= 6 or C not in (1, 2):
-        raise RuntimeError("m2h.score_gram: tile = %d >= 1, S = %d in 1 .. 6 and C = %d in {1, 2} are required" % (tile, S, C))
-    N = S + 3
-    out = torch.empty((R, C, -(-L // tile), N + N * (N + 1) // 2), device=refs.device, dtype=torch.float64)
-    lib = _lib.load()
-    with torch.cuda.device(refs.device):
-        _lib.check(lib.m2h_score_gram(_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1),
-                                      _ptr(mix), mix.stride(0), mix.stride(1), _ptr(out), R, S, C, L, tile, _stream(refs)), "m2h_score_gram")
-    return out
-
-
-def _score_signals(what, refs, est, mix=None):
-    """the shape, dtype and stride checks shared by the Scorer's aligned ops -> (R, S, C, L)"""
-    for t in (refs, est) + (() if mix is None else (mix,)):
+def _score_signals(what, refs, est, mix=None, min_L=0):
+    """the shape, dtype and stride checks shared by the Scorer's ops -> (R, S, C, L)"""
+    sigs = (refs, est) + (() if mix is None else (mix,))
+    for t in sigs:
         if not t.is_cuda or t.dtype != torch.float32 or t.device != refs.device:
             raise RuntimeError("m2h.%s: float32 tensors on one GPU are required (got %s on %s); the m2h ops have no CPU path" % (what, t.dtype, t.device))
     if refs.dim() != 4 or est.dim() != 3 or (mix is not None and mix.dim() != 3):
         raise RuntimeError("m2h.%s: refs [R, S, C, L], est [R, C, L] and mix [R, 2, L] are required" % what)
     R, S, C, L = refs.shape
-    if tuple(est.shape) != (R, C, L) or (mix is not None and tuple(mix.shape) != (R, 2, L)) or R < 1:
+    if tuple(est.shape) != (R, C, L) or (mix is not None and tuple(mix.shape) != (R, 2, L)) or R < 1 or L < min_L:
         raise RuntimeError("m2h.%s: refs %s, est %s%s do not agree" % (what, tuple(refs.shape), tuple(est.shape), "" if mix is None else " and mix %s" % (tuple(mix.shape),)))
-    if any(t.stride(-1) != 1 for t in (refs, est) + (() if mix is None else (mix,))):
+    if L > 1 and any(t.stride(-1) != 1 for t in sigs):        # (the last stride of a one-sample row is never used)
         raise RuntimeError("m2h.%s: the last stride must be 1" % what)
     if not 1 <= S <= 6 or C not in (1, 2):
         raise RuntimeError("m2h.%s: S = %d in 1 .. 6 and C = %d in {1, 2} are required" % (what, S, C))
     return R, S, C, L
+
+
+def _score_target(what, target, refs):
+    """`target` of a Scorer op, an int or an int64 tensor [R] on the device -> the (pointer, int) pair of the C ABI"""
+    R, S = refs.shape[:2]
+    if isinstance(target, torch.Tensor):
+        if target.dtype != torch.int64 or tuple(target.shape) != (R,) or target.device != refs.device or not target.is_contiguous():
+            raise RuntimeError("m2h.%s: a tensor `target` must be a contiguous int64 [R] = [%d] on %s" % (what, R, refs.device))
+        return _ptr(target), 0
+    if not 0 <= int(target) < S:
+        raise RuntimeError("m2h.%s: target = %d is not one of the S = %d references" % (what, int(target), S))
+    return None, int(target)
+
+
+def _score_lag(what, lag, refs):
+    """`lag` of a Scorer op: int32 [R, C] on the device -> its pointer"""
+    R, _, C, _ = refs.shape
+    _chk(lag, "%s(lag)" % what, torch.int32)
+    if tuple(lag.shape) != (R, C) or lag.device != refs.device:
+        raise RuntimeError("m2h.%s: lag must be [R, C] = [%d, %d] int32 on %s" % (what, R, C, refs.device))
+    return _ptr(lag)
+
+
+def _score_args(refs, est, mix=None):
+    """the signals' pointers and strides in the order of the C ABI"""
+    args = (_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1))
+    return args if mix is None else args + (_ptr(mix), mix.stride(0), mix.stride(1))
+
+
+def score_gram(refs, est, mix, tile):
+    """Tile Grams of the Scorer (m2h/audio/score.py): refs [R, S, C, L], est [R, C, L], mix [R, 2, L] fp32 with unit last stride and
+    any other strides (views are read in place) -> [R, C, J, N + N(N+1)/2] fp64, J = ceil(L / tile), N = S + 3 (include/m2h.h)."""
+    R, S, C, L = _score_signals("score_gram", refs, est, mix, min_L=1)
+    tile = int(tile)
+    if tile < 1:
+        raise RuntimeError("m2h.score_gram: tile = %d >= 1, S = %d in 1 .. 6 and C = %d in {1, 2} are required" % (tile, S, C))
+    N = S + 3
+    out = torch.empty((R, C, -(-L // tile), N + N * (N + 1) // 2), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_score_gram(*_score_args(refs, est, mix), _ptr(out), R, S, C, L, tile, _stream(refs)), "m2h_score_gram")
+    return out
 
 
 def align_corr(refs, est, target, tile, D, twiddles):
@@ -785,19 +803,11 @@ def align_corr(refs, est, target, tile, D, twiddles):
     _chk(twiddles, "align_corr(twiddles)")
     if tuple(twiddles.shape) != (2, 16384, 2) or twiddles.device != refs.device:
         raise RuntimeError("m2h.align_corr: twiddles must be the [2, 16384, 2] table on %s" % (refs.device,))
-    if isinstance(target, torch.Tensor):
-        if target.dtype != torch.int64 or tuple(target.shape) != (R,) or target.device != refs.device or not target.is_contiguous():
-            raise RuntimeError("m2h.align_corr: a tensor `target` must be a contiguous int64 [R] = [%d] on %s" % (R, refs.device))
-        tptr, t0 = _ptr(target), 0
-    else:
-        tptr, t0 = None, int(target)
-        if not 0 <= t0 < S:
-            raise RuntimeError("m2h.align_corr: target = %d is not one of the S = %d references" % (t0, S))
+    tptr, t0 = _score_target("align_corr", target, refs)
     out = torch.empty((R, C, -(-(L - 2 * D) // tile), 2 * D + 1), device=refs.device, dtype=torch.float64)
     lib = _lib.load()
     with torch.cuda.device(refs.device):
-        _lib.check(lib.m2h_align_corr(_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1), tptr, t0,
-                                      _ptr(twiddles), _ptr(out), R, S, C, L, tile, D, _stream(refs)), "m2h_align_corr")
+        _lib.check(lib.m2h_align_corr(*_score_args(refs, est), tptr, t0, _ptr(twiddles), _ptr(out), R, S, C, L, tile, D, _stream(refs)), "m2h_align_corr")
     return out
 
 
@@ -808,16 +818,12 @@ def score_gram_lag(refs, est, mix, tile, lag, D):
     tile, D = int(tile), int(D)
     if not 1 <= D <= 8192 or tile < 1 or L < 2 * D + 1:
         raise RuntimeError("m2h.score_gram_lag: D = %d in 1 .. 8192, tile = %d >= 1 and L = %d >= 2 D + 1 are required" % (D, tile, L))
-    _chk(lag, "score_gram_lag(lag)", torch.int32)
-    if tuple(lag.shape) != (R, C) or lag.device != refs.device:
-        raise RuntimeError("m2h.score_gram_lag: lag must be [R, C] = [%d, %d] int32 on %s" % (R, C, refs.device))
+    lptr = _score_lag("score_gram_lag", lag, refs)
     N = S + 3
     out = torch.empty((R, C, -(-(L - 2 * D) // tile), N + N * (N + 1) // 2), device=refs.device, dtype=torch.float64)
     lib = _lib.load()
     with torch.cuda.device(refs.device):
-        _lib.check(lib.m2h_score_gram_lag(_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1),
-                                          _ptr(mix), mix.stride(0), mix.stride(1), _ptr(out), R, S, C, L, tile, _ptr(lag), D, _stream(refs)),
-                   "m2h_score_gram_lag")
+        _lib.check(lib.m2h_score_gram_lag(*_score_args(refs, est, mix), _ptr(out), R, S, C, L, tile, lptr, D, _stream(refs)), "m2h_score_gram_lag")
     return out
 
 
@@ -836,24 +842,13 @@ def score_spectral(refs, est, mix, target, dft, lag=None, D=0):
     _chk(dft, "score_spectral(dft)")
     if tuple(dft.shape) != SPECTRAL_TABLE_SHAPE or dft.device != refs.device:
         raise RuntimeError("m2h.score_spectral: dft must be the %s table on %s" % (list(SPECTRAL_TABLE_SHAPE), refs.device))
-    if lag is not None:
-        _chk(lag, "score_spectral(lag)", torch.int32)
-        if tuple(lag.shape) != (R, C) or lag.device != refs.device:
-            raise RuntimeError("m2h.score_spectral: lag must be [R, C] = [%d, %d] int32 on %s" % (R, C, refs.device))
-    if isinstance(target, torch.Tensor):
-        if target.dtype != torch.int64 or tuple(target.shape) != (R,) or target.device != refs.device or not target.is_contiguous():
-            raise RuntimeError("m2h.score_spectral: a tensor `target` must be a contiguous int64 [R] = [%d] on %s" % (R, refs.device))
-        tptr, t0 = _ptr(target), 0
-    else:
-        tptr, t0 = None, int(target)
-        if not 0 <= t0 < S:
-            raise RuntimeError("m2h.score_spectral: target = %d is not one of the S = %d references" % (t0, S))
+    lptr = None if lag is None else _score_lag("score_spectral", lag, refs)
+    tptr, t0 = _score_target("score_spectral", target, refs)
     out = torch.empty((R, C, -(-(L - 2 * D) // 16000), 7), device=refs.device, dtype=torch.float64)
     lib = _lib.load()
     with torch.cuda.device(refs.device):
-        _lib.check(lib.m2h_score_spectral(_ptr(refs), refs.stride(0), refs.stride(1), refs.stride(2), _ptr(est), est.stride(0), est.stride(1),
-                                          _ptr(mix), mix.stride(0), mix.stride(1), tptr, t0, _ptr(dft), _ptr(out), R, S, C, L,
-                                          None if lag is None else _ptr(lag), D, _stream(refs)), "m2h_score_spectral")
+        _lib.check(lib.m2h_score_spectral(*_score_args(refs, est, mix), tptr, t0, _ptr(dft), _ptr(out), R, S, C, L, lptr, D, _stream(refs)),
+                   "m2h_score_spectral")
     return out
 
 

@@ -109,6 +109,40 @@ def test_rollout_structs_match_header_field_order():
     assert lib.m2h_gru_step(8, 8, 8, 8, None, 8, 8, 17, 512, None) < 0 and b"gru_step" in lib.m2h_last_error()
 
 
+def test_scorer_refusals_name_their_own_entry_point():
+    """The four scorer entry points share their argument checks (csrc/score_common.h); a refusal still names the entry that was called.
+    Refusals return before any HIP call, so this runs without a GPU."""
+    lib = _lib.load()
+    p, null = ctypes.c_void_p(256), None          # never dereferenced
+    sig = lambda refs=p, est=p: (refs, 300, 100, 0, est, 100, 0)   # noqa: E731
+    mix = (p, 200, 100)
+    n0 = lib.m2h_launch_count()
+
+    def gram(S=3, C=1, **kw):
+        return lib.m2h_score_gram(*sig(**kw), *mix, p, 2, S, C, 100, 10, None)
+
+    def gram_lag(S=3, C=1, **kw):
+        return lib.m2h_score_gram_lag(*sig(**kw), *mix, p, 2, S, C, 100, 10, p, 5, None)
+
+    def corr(S=3, C=1, target0=0, **kw):
+        return lib.m2h_align_corr(*sig(**kw), None, target0, p, p, 2, S, C, 100, 10, 5, None)
+
+    def spectral(S=3, C=1, target0=0, **kw):
+        return lib.m2h_score_spectral(*sig(**kw), *mix, None, target0, p, p, 2, S, C, 100, None, 0, None)
+
+    for name, call, rows in ((b"score_gram", gram, [(dict(S=7), b"S = 7"), (dict(C=3), b"C = 3"), (dict(refs=null), b"null pointer")]),
+                             (b"score_gram_lag", gram_lag, [(dict(S=7), b"S = 7"), (dict(C=3), b"C = 3"), (dict(est=null), b"null pointer")]),
+                             (b"align_corr", corr, [(dict(S=7), b"S = 7"), (dict(C=3), b"C = 3"), (dict(refs=null), b"null pointer"),
+                                                    (dict(target0=3), b"target = 3"), (dict(target0=-1), b"target = -1")]),
+                             (b"score_spectral", spectral, [(dict(S=7), b"S = 7"), (dict(C=3), b"C = 3"), (dict(est=null), b"null pointer"),
+                                                            (dict(target0=3), b"target = 3"), (dict(target0=-1), b"target = -1")])):
+        for kw, text in rows:
+            assert call(**kw) < 0, (name, kw)
+            msg = lib.m2h_last_error()
+            assert msg.startswith(name + b": ") and text in msg, (name, kw, msg)
+    assert lib.m2h_launch_count() == n0
+
+
 def test_workspace_bytes_reports_the_dma_engines_two_k_halves_launch():
     """m2h_conv_igemm_workspace_bytes (host-only) mirrors the launch rules: for the fourth encoder stage at the benchmark batch in
     bf16x3 arithmetic on split32 operands (128 tiles of 256 x 128, K = 4096) the LDS-DMA engine runs two K-halves per tile into
