@@ -143,6 +143,28 @@ def test_scorer_refusals_name_their_own_entry_point():
     assert lib.m2h_launch_count() == n0
 
 
+def test_rollout_kernel_refusals_name_their_own_entry_point():
+    """Argument refusals of the rollout kernels (tests/rollout_kernels.py has their rows): each returns before any launch and names the
+    entry that was called, so this runs without a GPU."""
+    lib = _lib.load()
+    p = ctypes.c_void_p(256)                      # never dereferenced
+    n0 = lib.m2h_launch_count()
+    many = (_lib.RowCopy * (_lib.ROWS_COPY_MAX + 1))(*[_lib.RowCopy(256, 512, 16, -1, -1) for _ in range(_lib.ROWS_COPY_MAX + 1)])
+    gathers = (_lib.RowCopy * (_lib.ROWS_COPY_MAX + 1))(*[_lib.RowCopy(256, 512, 16, 0, -1) for _ in range(_lib.ROWS_COPY_MAX + 1)])
+    rows = ((b"advantages", lambda: lib.m2h_advantages(p, p, p, p, 1, 0, 1e-5, None), b"bad arguments"),                       # n = 1
+            (b"acoustic_mem_small", lambda: lib.m2h_acoustic_mem_small_fwd(p, p, None, p, p, p, 1, 256, 32, None), b"got 256 x 32"),   # F != 512
+            (b"acoustic_mem_small", lambda: lib.m2h_acoustic_mem_small_fwd(p, p, None, p, p, p, 1, 512, 16, None), b"got 512 x 16"),   # T != 32
+            (b"gather_envs", lambda: lib.m2h_gather_envs(p, p, p, 1, 1, 1, 6, None), b"row_bytes % 4"),
+            (b"rows_copy", lambda: lib.m2h_rows_copy(many, _lib.ROWS_COPY_MAX + 1, None, None), b"1..%d items" % _lib.ROWS_COPY_MAX),
+            (b"synth_env_observe", lambda: lib.m2h_synth_env_observe(gathers, _lib.ROWS_COPY_MAX + 1, p, p, p, 1, None), b"bad arguments"),
+            (b"slice_concat_input", lambda: lib.m2h_slice_concat_input(p, 1, None, 0, None, None, 0, p, 1, 24, 4, None), b"F % 16"))
+    for name, call, text in rows:
+        assert call() < 0, name
+        msg = lib.m2h_last_error()
+        assert msg.startswith(name + b": ") and text in msg, (name, msg)
+    assert lib.m2h_launch_count() == n0
+
+
 def test_workspace_bytes_reports_the_dma_engines_two_k_halves_launch():
     """m2h_conv_igemm_workspace_bytes (host-only) mirrors the launch rules: for the fourth encoder stage at the benchmark batch in
     bf16x3 arithmetic on split32 operands (128 tiles of 256 x 128, K = 4096) the LDS-DMA engine runs two K-halves per tile into
