@@ -14,7 +14,7 @@ import weakref
 
 import torch
 
-from . import _lib, ops
+from . import _lib, conv_launch, ops
 
 
 _carry_tuning = [False]   # set by carry_tuning(): tests / tools that A/B engines through a backward pass
@@ -47,15 +47,11 @@ def carries_math_mode(cls):
     return cls
 
 
-def _conv_args(x, x2, n_out, kh, kw, stride, pad, Ho, Wo):
-    B, H, W, C0 = x.shape
-    a = _lib.ConvArgs()
-    a.src0, a.src1, a.C0, a.C1 = x.data_ptr(), (x2.data_ptr() if x2 is not None else None), C0, (x2.shape[3] if x2 is not None else 0)
-    a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, H, W, Ho, Wo
-    a.stride, a.nth, a.ntw, a.mulh, a.offh, a.mulw, a.offw = stride, kh, kw, 1, -pad, 1, -pad
-    a.conv_transpose, a.N = 0, n_out
-    a.Ho, a.Wo, a.os, a.ph, a.pw, a.ldc, a.out_mode = Ho, Wo, 1, 0, 0, n_out, 0
-    return a
+_convT_phase_args = conv_launch.conv_transpose_phase   # this form and the next under the names they had in this module
+
+
+def _conv_args(x, x2, n_out, kh, kw, stride, pad, Ho, Wo):   # (Ho, Wo follow from the rest)
+    return conv_launch.conv(x, x2, n_out, kh, kw, stride, pad)
 
 
 _flat_optimizers = weakref.WeakSet()   # FlatAdam instances (m2h/optim.py): their flat gradient buffers offer each weight's gradient a home
@@ -203,43 +199,41 @@ def join_wgrad_branches(device=None, forked_from=None):
         cur.wait_stream(_wgrad_pending.pop(key)[0])
 
 
+# the gradient's form -> the C entry, and which of conv_wgrad's operands (dy, ldy, gate, gate slope, dw, torch Ci) it takes
+_WGRAD_ENTRIES = {
+    "packed": ("m2h_conv_wgrad_f32", (0, 1, 4)),
+    "gated": ("m2h_conv_wgrad_gated_f32", (0, 1, 2, 3, 4)),
+    "torch": ("m2h_conv_wgrad_torch_f32", (0, 1, 2, 3, 4, 5)),   # (with or without a gate: null = none)
+}
+
+
+def _wgrad_out(who, out, shape, dev):
+    if out is not None and (tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != torch.float32):
+        raise RuntimeError("m2h.%s: out must be a contiguous fp32 tensor of shape %s" % (who, shape))
+    return out if out is not None else torch.empty(shape, device=dev, dtype=torch.float32)
+
+
 def conv_wgrad(x, x2, dy, n_out, kh, kw, stride, pad, gate=None, gate_slope=1.0, torch_ci=None, out=None):
     """Packed weight gradient [n_out, kh*kw*(C0+C1)] of a conv whose NHWC inputs were x (+x2) and NHWC output grad is dy.
     gate: the layer's forward output y; dy is then read as dy * (y > 0 ? 1 : gate_slope) (m2h_conv_wgrad_gated_f32: image-row shapes only).
     torch_ci: return nn.Conv2d's own layout [n_out, torch_ci, kh, kw] instead (m2h_conv_wgrad_torch_f32: no permute copy afterwards).
     out: write the gradient there (grad_slot(w): the weight's place in its optimizer's flat gradient buffer)."""
     B, Ho, Wo, N = dy.shape
-    a = _conv_args(x, x2, n_out, kh, kw, stride, pad, Ho, Wo)
-    lib = _lib.load()
+    a = conv_launch.conv(x, x2, n_out, kh, kw, stride, pad)
     K = kh * kw * (x.shape[3] + (x2.shape[3] if x2 is not None else 0))
-    shape = (n_out, K) if torch_ci is None else (n_out, int(torch_ci), kh, kw)
-    if out is not None and (tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != torch.float32):
-        raise RuntimeError("m2h.conv_wgrad: out must be a contiguous fp32 tensor of shape %s" % (shape,))
-    dw = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
+    dw = _wgrad_out("conv_wgrad", out, (n_out, K) if torch_ci is None else (n_out, int(torch_ci), kh, kw), x.device)
+    entry, takes = _WGRAD_ENTRIES["torch" if torch_ci is not None else "gated" if gate is not None else "packed"]
+    operands = (ops._ptr(dy), N, ops._ptr(gate), float(gate_slope), ops._ptr(dw), int(torch_ci or 0))
     with torch.cuda.device(x.device):
-        nbytes = lib.m2h_conv_wgrad_workspace_bytes(ctypes.byref(a))
-        ws = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
         M = B * Ho * Wo
         meta = {"kernel": "wgrad_f32", "M": M, "N": n_out, "K": K, "flops": 2.0 * M * n_out * K, "bytes": 4.0 * (x.numel() + dy.numel() + dw.numel())}
-        if torch_ci is not None:
-            ops._timed("conv_wgrad", meta, x.device,
-                       lambda: _lib.check(lib.m2h_conv_wgrad_torch_f32(ctypes.byref(a), ops._ptr(dy), N, ops._ptr(gate) if gate is not None else None,
-                                                                       float(gate_slope), ops._ptr(dw), int(torch_ci), ops._stream(x)), "m2h_conv_wgrad_torch_f32"))
-        elif gate is not None:
-            ops._timed("conv_wgrad", meta, x.device,
-                       lambda: _lib.check(lib.m2h_conv_wgrad_gated_f32(ctypes.byref(a), ops._ptr(dy), N, ops._ptr(gate), float(gate_slope), ops._ptr(dw),
-                                                                       ops._stream(x)), "m2h_conv_wgrad_gated_f32"))
-        else:
-            ops._timed("conv_wgrad", meta, x.device,
-                       lambda: _lib.check(lib.m2h_conv_wgrad_f32(ctypes.byref(a), ops._ptr(dy), N, ops._ptr(dw), ops._stream(x)), "m2h_conv_wgrad_f32"))
+        conv_launch.launch(entry, a, "m2h_conv_wgrad_workspace_bytes", "conv_wgrad", meta, x.device, *[operands[i] for i in takes])
     return dw
 
 
 def conv_wgrad_dgrad_fused_supported(x, n_out=32):
     """True when m2h_conv_wgrad_dgrad_fused_f32 takes a 3x3 / 1 / 1 conv over x [B, H, 32, 32] -> n_out in the calling thread's arithmetic."""
-    B, H, W, _C = x.shape
-    a = _conv_args(x, None, n_out, 3, 3, 1, 1, H, W)
+    a = conv_launch.conv(x, None, n_out, 3, 3, 1, 1)
     return bool(_lib.load().m2h_conv_wgrad_dgrad_fused_supported(ctypes.byref(a)))
 
 
@@ -248,20 +242,13 @@ def conv_wgrad_dgrad_fused(x, dy2, wp_next, gate, gate_slope, torch_ci, out=None
     of the next 3x3 conv, made inside the kernel from dy2 [B, H, W, 16] and that conv's packed weight wp_next [16, 288]
     (m2h_conv_wgrad_dgrad_fused_f32: the 32-channel gradient tensor is never stored).  bf16x3 arithmetic, image-row shapes only."""
     B, H, W, C = x.shape
-    a = _conv_args(x, None, 32, 3, 3, 1, 1, H, W)
-    lib = _lib.load()
-    shape = (32, int(torch_ci), 3, 3)
-    if out is not None and (tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != torch.float32):
-        raise RuntimeError("m2h.conv_wgrad_dgrad_fused: out must be a contiguous fp32 tensor of shape %s" % (shape,))
+    a = conv_launch.conv(x, None, 32, 3, 3, 1, 1)
+    dw = _wgrad_out("conv_wgrad_dgrad_fused", out, (32, int(torch_ci), 3, 3), x.device)
     if tuple(dy2.shape) != (B, H, W, 16) or not dy2.is_contiguous() or wp_next.numel() != 16 * 9 * C or tuple(gate.shape) != (B, H, W, 32):
         raise RuntimeError("m2h.conv_wgrad_dgrad_fused: dy2 must be [B, H, W, 16] contiguous, wp_next [16, 288], gate [B, H, W, 32]")
-    dw = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
     with torch.cuda.device(x.device):
-        nbytes = lib.m2h_conv_wgrad_workspace_bytes(ctypes.byref(a))
-        ws = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-        _lib.check(lib.m2h_conv_wgrad_dgrad_fused_f32(ctypes.byref(a), ops._ptr(dy2), ops._ptr(wp_next), ops._ptr(gate), float(gate_slope), ops._ptr(dw),
-                                                      int(torch_ci), ops._stream(x)), "m2h_conv_wgrad_dgrad_fused_f32")
+        conv_launch.launch("m2h_conv_wgrad_dgrad_fused_f32", a, "m2h_conv_wgrad_workspace_bytes", None, None, x.device,
+                           ops._ptr(dy2), ops._ptr(wp_next), ops._ptr(gate), float(gate_slope), ops._ptr(dw), int(torch_ci))
     return dw
 
 
@@ -279,35 +266,20 @@ def conv_dgrad(dy, w4d, in_hw, stride, pad, ci_out=None, wp=None):
     wp: the weight's phase matrices (m2h_pack_dgrad_weight) when the caller keeps them packed."""
     B, Ho, Wo, Co = dy.shape
     _, Ci, KH, KW = w4d.shape
-    H, W = in_hw
-    s = stride
+    (H, W), s = in_hw, stride
     if wp is None:
         wp = pack_dgrad_weight(w4d, s, pad)
     dx = torch.empty((B, H, W, Ci), device=dy.device, dtype=torch.float32)
-    lib = _lib.load()
+    K = (KH // s) * (KW // s) * Co
     with torch.cuda.device(dy.device):
         for ph in range(s):
             for pw in range(s):
-                Hq, Wq = (H - ph + s - 1) // s, (W - pw + s - 1) // s
-                if Hq <= 0 or Wq <= 0:
+                a = conv_launch.conv_dgrad_phase(dy, in_hw, Ci, KH, KW, s, pad, ph, pw, wp[ph * s + pw], dx)
+                if a is None:
                     continue
-                a = _lib.ConvArgs()
-                a.src0, a.src1, a.C0, a.C1 = dy.data_ptr(), None, Co, 0
-                a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, Ho, Wo, Hq, Wq
-                a.stride, a.nth, a.ntw = 1, KH // s, KW // s
-                a.mulh, a.offh = -1, (ph + pad - (ph + pad) % s) // s
-                a.mulw, a.offw = -1, (pw + pad - (pw + pad) % s) // s
-                a.conv_transpose, a.wp, a.N = 0, wp[ph * s + pw].data_ptr(), Ci
-                a.scale, a.shift, a.slope, a.cls_table, a.cls_val = None, None, 1.0, None, None
-                a.dst, a.Ho, a.Wo, a.os, a.ph, a.pw, a.ldc, a.out_mode = dx.data_ptr(), H, W, s, ph, pw, Ci, 0
-                nbytes = lib.m2h_conv_igemm_workspace_bytes(ctypes.byref(a))
-                ws = torch.empty((nbytes + 3) // 4, device=dy.device, dtype=torch.float32) if nbytes else None
-                a.workspace, a.workspace_bytes = (ws.data_ptr() if ws is not None else None), nbytes
-                M = B * Hq * Wq
-                K = (KH // s) * (KW // s) * Co
+                M = B * a.Hq * a.Wq
                 meta = {"kernel": ops.igemm_config(Ci), "M": M, "N": Ci, "K": K, "flops": 2.0 * M * Ci * K}
-                ops._timed("conv_dgrad", meta, dy.device,
-                           lambda: _lib.check(lib.m2h_conv_igemm_f32(ctypes.byref(a), ops._stream(dy)), "m2h_conv_igemm_f32(dgrad)"))
+                conv_launch.launch("m2h_conv_igemm_f32", a, "m2h_conv_igemm_workspace_bytes", "conv_dgrad", meta, dy.device)
     return dx
 
 
@@ -327,7 +299,7 @@ def act_bwd_bias(dy, y, slope):
     db = torch.empty(N, device=dy.device, dtype=torch.float32)
     lib = _lib.load()
     with torch.cuda.device(dy.device):
-        ws = torch.empty((lib.m2h_bias_grad_workspace_bytes(M, N) + 3) // 4, device=dy.device, dtype=torch.float32)
+        ws, _ = conv_launch.workspace(lib.m2h_bias_grad_workspace_bytes(M, N), dy.device)
         _lib.check(lib.m2h_act_bwd_bias(ops._ptr(dy), ops._ptr(y), float(slope), ops._ptr(out), ops._ptr(db), M, N, ops._ptr(ws), ops._stream(dy)),
                    "m2h_act_bwd_bias")
     return out, db
@@ -338,7 +310,7 @@ def bias_grad(dy2d):
     db = torch.empty(N, device=dy2d.device, dtype=torch.float32)
     lib = _lib.load()
     with torch.cuda.device(dy2d.device):
-        ws = torch.empty((lib.m2h_bias_grad_workspace_bytes(M, N) + 3) // 4, device=dy2d.device, dtype=torch.float32)
+        ws, _ = conv_launch.workspace(lib.m2h_bias_grad_workspace_bytes(M, N), dy2d.device)
         _lib.check(lib.m2h_bias_grad(ops._ptr(dy2d), ops._ptr(db), M, N, ops._ptr(ws), ops._stream(dy2d)), "m2h_bias_grad")
     return db
 
@@ -987,7 +959,7 @@ class BNAct(torch.autograd.Function):
         invstd = torch.empty(C, device=dev)
         lib = _lib.load()
         with torch.cuda.device(dev):
-            ws = torch.empty((lib.m2h_bn_workspace_bytes(M, C) + 3) // 4, device=dev)
+            ws, _ = conv_launch.workspace(lib.m2h_bn_workspace_bytes(M, C), dev)
             _lib.check(lib.m2h_bn_train_fwd(ops._ptr(z), ops._ptr(gamma.detach()), ops._ptr(beta.detach()), float(eps), float(momentum), float(slope),
                                             ops._ptr(running_mean), ops._ptr(running_var), ops._ptr(mean), ops._ptr(invstd), ops._ptr(y), M, C,
                                             ops._ptr(ws), ops._stream(z)), "m2h_bn_train_fwd")
@@ -1007,7 +979,7 @@ class BNAct(torch.autograd.Function):
         dbeta = torch.empty(C, device=dev)
         lib = _lib.load()
         with torch.cuda.device(dev):
-            ws = torch.empty((lib.m2h_bn_workspace_bytes(M, C) + 3) // 4, device=dev)
+            ws, _ = conv_launch.workspace(lib.m2h_bn_workspace_bytes(M, C), dev)
             _lib.check(lib.m2h_bn_train_bwd(ops._ptr(dy), ops._ptr(y), ops._ptr(z), ops._ptr(mean), ops._ptr(invstd), ops._ptr(gamma.detach()),
                                             float(ctx.slope), ops._ptr(dgamma), ops._ptr(dbeta), ops._ptr(dz), M, C, ops._ptr(ws),
                                             ops._stream(z)), "m2h_bn_train_bwd")
@@ -1045,18 +1017,6 @@ def batched_bn_counters():
                 torch._foreach_add_(sink, 1)
 
 
-def _convT_phase_args(x, x2, Co, ph, pw):
-    B, H, W, C0 = x.shape
-    a = _lib.ConvArgs()
-    a.src0, a.src1, a.C0, a.C1 = x.data_ptr(), (x2.data_ptr() if x2 is not None else None), C0, (x2.shape[3] if x2 is not None else 0)
-    a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, H, W, H, W
-    a.stride, a.nth, a.ntw = 1, 2, 2
-    a.mulh, a.offh, a.mulw, a.offw = 2 * ph - 1, 0, 2 * pw - 1, 0
-    a.conv_transpose, a.N = 0, Co
-    a.Ho, a.Wo, a.os, a.ph, a.pw, a.ldc, a.out_mode = 2 * H, 2 * W, 2, ph, pw, Co, 0
-    return a
-
-
 @carries_math_mode
 class ConvTranspose2dNHWC(torch.autograd.Function):
     """z = conv_transpose2d(cat(x, x2), w, stride 2, pad 1, 4x4) on NHWC (no bias / activation): forward = 4 sub-pixel phase
@@ -1083,21 +1043,15 @@ class ConvTranspose2dNHWC(torch.autograd.Function):
         B, H, W, _ = x.shape
         gx = gx2 = gw = None
         if ctx.needs_input_grad[2]:
-            lib = _lib.load()
             slot = grad_slot(w)
 
             def wgrad():
                 with torch.cuda.device(x.device):
-                    a = _convT_phase_args(x, x2, Co, 0, 0)   # the phase geometry; the launch walks all four phases
-                    nbytes = lib.m2h_convT_wgrad_workspace_bytes(ctypes.byref(a))
-                    ws = torch.empty((nbytes + 3) // 4, device=x.device)
-                    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+                    a = conv_launch.conv_transpose_phase(x, x2, Co, 0, 0)   # the phase geometry; the launch walks all four phases
                     M = B * H * W
                     out = slot if slot is not None else torch.empty_like(w)
                     meta = {"kernel": "wgrad_f32", "M": 4 * M, "N": Co, "K": 4 * Cin, "flops": 2.0 * 4 * M * Co * 4 * Cin}
-                    ops._timed("convT_wgrad", meta, x.device,
-                               lambda: _lib.check(lib.m2h_convT_wgrad_f32(ctypes.byref(a), ops._ptr(dz), Co, ops._ptr(out), ops._stream(x)),
-                                                  "m2h_convT_wgrad_f32"))
+                    conv_launch.launch("m2h_convT_wgrad_f32", a, "m2h_convT_wgrad_workspace_bytes", "convT_wgrad", meta, x.device, ops._ptr(dz), Co, ops._ptr(out))
                 return out
 
             gw = _wgrad_launch(x.device, (x, x2, dz), wgrad, slot)

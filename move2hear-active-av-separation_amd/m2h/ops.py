@@ -7,7 +7,7 @@ import threading
 
 import torch
 
-from . import _lib
+from . import _lib, conv_launch
 
 OUT_NHWC = 0
 OUT_DESLICE = 1
@@ -45,7 +45,7 @@ def unet_stage_kernels():
 
 
 def _timed(name, meta, dev, fn):
-    if _timing is None:
+    if _timing is None or name is None:   # (name None: a launch bench.py does not list)
         return fn()
     st = torch.cuda.current_stream(dev)
     e0 = torch.cuda.Event(enable_timing=True)
@@ -59,12 +59,7 @@ def _timed(name, meta, dev, fn):
     return r
 
 
-def _workspace(nbytes, dev):
-    """Split-K scratch from the caching allocator (None when the launch does not split)."""
-    if nbytes == 0:
-        return None, 0
-    ws = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.float32)
-    return ws, nbytes
+_workspace = conv_launch.workspace   # split-K scratch from the caching allocator ((None, 0) when the launch does not split)
 
 
 def debug_set(knob, value):
@@ -351,23 +346,6 @@ def unet_head_fwd(x, wp, bias, Co):
     return out
 
 
-def conv_igemm_f32(**kw):
-    """Generic implicit-GEMM conv (m2h_conv_igemm_f32); keyword names = fields of m2h_conv_args, tensors
-    for the pointer fields."""
-    a = _lib.ConvArgs()
-    dev_t = kw["src0"]
-    for name, _ in _lib.ConvArgs._fields_:
-        v = kw.get(name, None)
-        if name in ("src0", "src1", "wp", "scale", "shift", "cls_table", "cls_val", "dst", "workspace"):
-            _chk(v, "conv_igemm_f32(%s)" % name)
-            setattr(a, name, v.data_ptr() if v is not None else None)
-        elif v is not None:
-            setattr(a, name, v)
-    lib = _lib.load()
-    with torch.cuda.device(dev_t.device):
-        _lib.check(lib.m2h_conv_igemm_f32(ctypes.byref(a), _stream(dev_t)), "m2h_conv_igemm_f32")
-
-
 # ----------------------------------------------------------------------------------------------------------------
 # generic conv / linear on the igemm engine, and the RL-path ops
 # ----------------------------------------------------------------------------------------------------------------
@@ -401,26 +379,12 @@ def conv2d_nhwc(x, wp, n_out, kh, kw, stride=1, pad=0, bias=None, scale=None, sl
         out = torch.empty((B, 16 * Ho, Wo, n_out // 16), device=x.device, dtype=torch.float32)
     else:
         out = torch.empty((B, Ho, Wo, n_out), device=x.device, dtype=torch.float32)
-    a = _lib.ConvArgs()
-    a.src0, a.src1, a.C0, a.C1 = x.data_ptr(), (x2.data_ptr() if x2 is not None else None), C0, C1
-    a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, H, W, Ho, Wo
-    a.stride, a.nth, a.ntw, a.mulh, a.offh, a.mulw, a.offw = stride, kh, kw, 1, -pad, 1, -pad
-    a.conv_transpose, a.wp, a.N = 0, wp.data_ptr(), n_out
-    a.scale = scale.data_ptr() if scale is not None else None
-    a.shift = bias.data_ptr() if bias is not None else None
-    a.slope = float(slope)
-    a.cls_table, a.cls_val = None, None
-    a.dst, a.Ho, a.Wo, a.os, a.ph, a.pw, a.ldc = out.data_ptr(), Ho, Wo, 1, 0, 0, ldc
-    a.out_mode = OUT_DESLICE if deslice else OUT_NHWC
-    a.operand_format = int(operand_format)   # FMT_* bits: split32 operands / output (bf16x3 math only)
-    lib = _lib.load()
+    a = conv_launch.conv(x, x2, n_out, kh, kw, stride, pad, wp, out, scale, bias, slope, operand_format, ldc, OUT_DESLICE if deslice else OUT_NHWC)
     with torch.cuda.device(x.device):
-        ws, wsb = _workspace(lib.m2h_conv_igemm_workspace_bytes(ctypes.byref(a)), x.device)
-        a.workspace, a.workspace_bytes = (ws.data_ptr() if ws is not None else None), wsb
         M = B * Ho * Wo
         meta = {"kernel": igemm_config(n_out), "M": M, "N": n_out, "K": kh * kw * (C0 + C1), "flops": 2.0 * M * n_out * kh * kw * (C0 + C1),
                 "bytes": 4.0 * (x.numel() + (x2.numel() if x2 is not None else 0) + out.numel() + wp.numel())}
-        _timed(name, meta, x.device, lambda: _lib.check(lib.m2h_conv_igemm_f32(ctypes.byref(a), _stream(x)), "m2h_conv_igemm_f32"))
+        conv_launch.launch("m2h_conv_igemm_f32", a, "m2h_conv_igemm_workspace_bytes", name, meta, x.device)
     return out
 
 
@@ -1135,20 +1099,11 @@ def unet_up_fwd_raw(x, skip, wp, Co):
     if wp.numel() != 16 * Co * (C0 + C1):
         raise RuntimeError("m2h.unet_up_fwd_raw: packed weight size")
     y = torch.empty((B, 2 * H, 2 * W, Co), device=x.device, dtype=torch.float32)
-    a = _lib.ConvArgs()
-    a.src0, a.src1, a.C0, a.C1 = x.data_ptr(), (skip.data_ptr() if skip is not None else None), C0, C1
-    a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, H, W, H, W
-    a.stride, a.nth, a.ntw, a.mulh, a.offh, a.mulw, a.offw = 1, 2, 2, 0, 0, 0, 0
-    a.conv_transpose, a.wp, a.N = 1, wp.data_ptr(), Co
-    a.scale, a.shift, a.slope, a.cls_table, a.cls_val = None, None, 1.0, None, None
-    a.dst, a.Ho, a.Wo, a.os, a.ph, a.pw, a.ldc, a.out_mode = y.data_ptr(), 2 * H, 2 * W, 2, 0, 0, Co, OUT_NHWC
-    lib = _lib.load()
+    a = conv_launch.conv_transpose(x, skip, Co, wp, y)
     with torch.cuda.device(x.device):
-        ws, wsb = _workspace(lib.m2h_conv_igemm_workspace_bytes(ctypes.byref(a)), x.device)
-        a.workspace, a.workspace_bytes = (ws.data_ptr() if ws is not None else None), wsb
         M = B * H * W
         meta = {"kernel": igemm_config(Co), "M": 4 * M, "N": Co, "K": 4 * (C0 + C1), "flops": 2.0 * 4 * M * Co * 4 * (C0 + C1)}
-        _timed("unet_up_fwd_raw", meta, x.device, lambda: _lib.check(lib.m2h_conv_igemm_f32(ctypes.byref(a), _stream(x)), "m2h_conv_igemm_f32"))
+        conv_launch.launch("m2h_conv_igemm_f32", a, "m2h_conv_igemm_workspace_bytes", "unet_up_fwd_raw", meta, x.device)
     return y
 
 

@@ -30,25 +30,12 @@ def unsplit32(t):
 
 def _layer(x, x2, wp, Co, transposed, scale, shift, slope):
     """One split32 layer through m2h_conv_igemm_f32; returns (NHWC fp32 values, label of the kernel that ran)."""
-    from m2h import _lib, ops
+    from m2h import _lib, conv_launch, ops
     B, H, W, C0 = x.shape
-    C1 = x2.shape[3] if x2 is not None else 0
     Ho, Wo = (2 * H, 2 * W) if transposed else (H // 2, W // 2)
     out = torch.empty((B, Ho, Wo, Co), device=x.device, dtype=torch.float32)
-    a = _lib.ConvArgs()
-    a.src0, a.src1, a.C0, a.C1 = x.data_ptr(), (x2.data_ptr() if x2 is not None else None), C0, C1
-    if transposed:
-        a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, H, W, H, W
-        a.stride, a.nth, a.ntw, a.mulh, a.offh, a.mulw, a.offw = 1, 2, 2, 0, 0, 0, 0
-        a.conv_transpose, a.os = 1, 2
-    else:
-        a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, H, W, Ho, Wo
-        a.stride, a.nth, a.ntw, a.mulh, a.offh, a.mulw, a.offw = 2, 4, 4, 1, -1, 1, -1
-        a.conv_transpose, a.os = 0, 1
-    a.wp, a.N = wp.data_ptr(), Co
-    a.scale, a.shift, a.slope, a.cls_table, a.cls_val = scale.data_ptr(), shift.data_ptr(), float(slope), None, None
-    a.dst, a.Ho, a.Wo, a.ph, a.pw, a.ldc, a.out_mode = out.data_ptr(), Ho, Wo, 0, 0, Co, ops.OUT_NHWC
-    a.operand_format = ops.FMT_SRC_SPLIT | ops.FMT_W_SPLIT | ops.FMT_DST_SPLIT
+    operands = dict(wp=wp, dst=out, scale=scale, shift=shift, slope=slope, operand_format=ops.FMT_SRC_SPLIT | ops.FMT_W_SPLIT | ops.FMT_DST_SPLIT)
+    a = conv_launch.conv_transpose(x, x2, Co, **operands) if transposed else conv_launch.conv(x, x2, Co, 4, 4, 2, 1, **operands)
     lib = _lib.load()
     with torch.cuda.device(x.device):
         ws, wsb = ops._workspace(lib.m2h_conv_igemm_workspace_bytes(ctypes.byref(a)), x.device)

@@ -21,27 +21,15 @@ SLAB_WT_KNOB = 43
 
 def _conv(x, x2, wp, Co, transposed, scale, shift, slope, fmt, S, deslice=False, cls=None, knobs=None, ws_floats=None):
     """One layer through m2h_conv_igemm_f32 with a workspace for S slabs per phase; returns (raw destination words on the CPU, label)."""
-    from m2h import _lib, ops
+    from m2h import _lib, conv_launch, ops
     B, H, W, C0 = x.shape
-    C1 = x2.shape[3] if x2 is not None else 0
     Ho, Wo = (2 * H, 2 * W) if transposed else (H // 2, W // 2)
     Hq, Wq = (H, W) if transposed else (Ho, Wo)
     out = torch.zeros((B, 16 * Ho, Wo, Co // 16) if deslice else (B, Ho, Wo, Co), device=x.device, dtype=torch.float32)
-    a = _lib.ConvArgs()
-    a.src0, a.src1, a.C0, a.C1 = x.data_ptr(), (x2.data_ptr() if x2 is not None else None), C0, C1
-    a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, H, W, Hq, Wq
-    if transposed:
-        a.stride, a.nth, a.ntw, a.mulh, a.offh, a.mulw, a.offw = 1, 2, 2, 0, 0, 0, 0
-        a.conv_transpose, a.os = 1, 2
-    else:
-        a.stride, a.nth, a.ntw, a.mulh, a.offh, a.mulw, a.offw = 2, 4, 4, 1, -1, 1, -1
-        a.conv_transpose, a.os = 0, 1
-    a.wp, a.N = wp.data_ptr(), Co
-    a.scale, a.shift, a.slope = scale.data_ptr(), shift.data_ptr(), float(slope)
+    operands = dict(wp=wp, dst=out, scale=scale, shift=shift, slope=slope, operand_format=fmt)
+    a = conv_launch.conv_transpose(x, x2, Co, **operands) if transposed else conv_launch.conv(x, x2, Co, 4, 4, 2, 1, **operands)
     a.cls_table, a.cls_val = (cls[0].data_ptr(), cls[1].data_ptr()) if cls is not None else (None, None)
-    a.dst, a.Ho, a.Wo, a.ph, a.pw, a.ldc = out.data_ptr(), Ho, Wo, 0, 0, Co
     a.out_mode = ops.OUT_DESLICE if deslice else ops.OUT_NHWC
-    a.operand_format = fmt
     lib = _lib.load()
     n = ws_floats if ws_floats is not None else (4 if transposed else 1) * S * B * Hq * Wq * Co
     ws = torch.empty(n, device=x.device, dtype=torch.float32)

@@ -83,7 +83,7 @@ def _run_bn(row, inp):
     z, ga, be, dy, rm, rv = (_d(inp[k].clone()) for k in ("z", "gamma", "beta", "dy", "running_mean", "running_var"))
     y, dz = torch.empty_like(z), torch.empty_like(z)
     mean, invstd, dga, dbe = (torch.empty(C, device=dev) for _ in range(4))
-    ws = torch.empty((_lib.load().m2h_bn_workspace_bytes(M, C) + 3) // 4, device=dev)
+    ws, _ = ops._workspace(_lib.load().m2h_bn_workspace_bytes(M, C), dev)
     ops.debug_set(37, row["knob"])
     try:
         _call("bn_train_fwd", P(z), P(ga), P(be), K.BN_EPS, K.BN_MOMENTUM, slope, P(rm), P(rv), P(mean), P(invstd), P(y), M, C, P(ws))

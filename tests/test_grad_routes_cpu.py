@@ -7,7 +7,7 @@ import types
 import pytest
 
 import grad_routes as G
-from m2h import _lib, functional as MF, ops
+from m2h import _lib, conv_launch, ops
 
 
 def _fake(B, H, W, C):
@@ -19,9 +19,8 @@ def _workspace_bytes(row):
     B, H, W, C0, C1, Co, k, s, p = (row[f] for f in ("B", "H", "W", "C0", "C1", "Co", "k", "s", "p"))
     x, x2 = _fake(B, H, W, C0), (_fake(B, H, W, C1) if C1 else None)
     if row["op"] == "convT":
-        return lib.m2h_convT_wgrad_workspace_bytes(ctypes.byref(MF._convT_phase_args(x, x2, Co, 0, 0)))
-    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    return lib.m2h_conv_wgrad_workspace_bytes(ctypes.byref(MF._conv_args(x, x2, Co, k, k, s, p, Ho, Wo)))
+        return lib.m2h_convT_wgrad_workspace_bytes(ctypes.byref(conv_launch.conv_transpose_phase(x, x2, Co, 0, 0)))
+    return lib.m2h_conv_wgrad_workspace_bytes(ctypes.byref(conv_launch.conv(x, x2, Co, k, k, s, p)))
 
 
 def test_table_reaches_every_route_cell():

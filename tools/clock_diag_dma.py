@@ -21,7 +21,7 @@ cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"
 cmd += [os.path.join(_lib.CSRC, s) for s in _lib.SOURCES] + ["-o", diag]
 subprocess.check_call(cmd)
 _lib.LIB_PATH = diag
-from m2h import ops  # noqa: E402
+from m2h import conv_launch, ops  # noqa: E402
 
 lib = _lib.load()
 argv = sys.argv[1:]
@@ -39,16 +39,7 @@ def conv_t_layer(x, x2, wp, Co, sc, sh):
     """One transposed-conv layer (two split32 sources) through m2h_conv_igemm_f32 (as tests/test_gpu_patch.py)."""
     B, H, W, C0 = x.shape
     out = torch.empty((B, 2 * H, 2 * W, Co), device=x.device, dtype=torch.float32)
-    a = _lib.ConvArgs()
-    a.src0, a.src1, a.C0, a.C1 = x.data_ptr(), x2.data_ptr(), C0, x2.shape[3]
-    a.B, a.Hi, a.Wi, a.Hq, a.Wq = B, H, W, H, W
-    a.stride, a.nth, a.ntw, a.mulh, a.offh, a.mulw, a.offw = 1, 2, 2, 0, 0, 0, 0
-    a.conv_transpose, a.os = 1, 2
-    a.wp, a.N = wp.data_ptr(), Co
-    a.scale, a.shift, a.slope, a.cls_table, a.cls_val = sc.data_ptr(), sh.data_ptr(), 0.0, None, None
-    a.dst, a.Ho, a.Wo, a.ph, a.pw, a.ldc, a.out_mode = out.data_ptr(), 2 * H, 2 * W, 0, 0, Co, ops.OUT_NHWC
-    a.operand_format = fmt
-    a.workspace, a.workspace_bytes = None, 0
+    a = conv_launch.conv_transpose(x, x2, Co, wp=wp, dst=out, scale=sc, shift=sh, slope=0.0, operand_format=fmt)   # (no workspace: no split-K)
     with torch.cuda.device(x.device):
         _lib.check(lib.m2h_conv_igemm_f32(ctypes.byref(a), ops._stream(x)), "m2h_conv_igemm_f32")
     return out
