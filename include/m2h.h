@@ -809,6 +809,24 @@ int m2h_score_spectral(const float* refs, long long refs_sr, long long refs_ss, 
                        const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0, const float* dft, double* out,
                        int R, int S, int C, long long L, const int* lag, int D, m2h_stream stream);
 
+/* Scorer, interaural cues (m2h/audio/score.py, "Spatial"; csrc/score_spatial.hip).  Two channels throughout: refs [R][S][2][L],
+ * est [R][2][L], mix [R][2][L].  Tiles, the region [D, L - D), the spectrogram of a tile and the table dft are m2h_score_spectral's.
+ * Per recording the three binaural signals, taken raw, are x = 0: G = refs[r][target_r][c][D + t], 1: E = est[r][c][D + lag[2 r] + t]
+ * -- BOTH ears at the one lag of the left ear, so that the estimate's interaural delay survives -- and 2: B = mix[r][c][D + t].
+ *   out [R][J][3][32][4] fp64: signal x, band (bins 16 band .. 16 band + 15), and the four sums over the band's 16 bins x 32 frames of
+ *   the ears' spectra X_L (c = 0), X_R (c = 1):
+ *     0 PL = |X_L|^2   1 PR = |X_R|^2   2 CRE = Re(X_L conj X_R)   3 CIM = Im(X_L conj X_R) = Im X_L Re X_R - Re X_L Im X_R
+ * The transform runs on the exact fp32 matrix instruction; the four fp32 values of a bin are converted to fp64 before they are multiplied
+ * (exact products) and added; the summation order is fixed (no atomics) and does not depend on the batch, the strides or a row's
+ * alignment.  No read leaves [row start, row start + L).  target, lag ([R * 2] int32 ON THE DEVICE, only the even entries are read,
+ * clamped to [-D, D]) and D as for m2h_score_spectral.
+ * Returns a negative status and launches nothing for a null pointer (dft included), S outside 1 .. 6, R < 1, D outside 0 .. 8192 or not
+ * matching lag, L < 2 D + 1, a target0 outside [0, S) when target is NULL, an out that is not 8-byte aligned, or more than 2^31 - 1
+ * (r, j, x) triples. */
+int m2h_score_spatial(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                      const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0, const float* dft, double* out,
+                      int R, int S, long long L, const int* lag, int D, m2h_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-network runner: one C call enqueues every kernel of one separator U-Net forward (K1/K2 slice, 5 down stages, 5 up
  * stages, head) = PassiveSepEncCNN.forward + PassiveSepDecCNN.forward (separator_cnn.py:70-108,153-170) in eval mode.  Same

@@ -93,6 +93,44 @@ caller.  Q = 0 gives NaN; otherwise IEEE rules apply (a silent target makes sc N
 computes the seven sums of every tile straight from the waveforms -- the transform on the exact fp32 matrix instruction, squares added
 in fp64, no frame or spectrum ever in memory -- and spectral_from_sums does the rest in torch float64.  No host synchronisation, and no
 copy from the host apart from the transform table on a Scorer's first spectral call.
+
+Spatial.  score(..., spatial=True) adds the interaural cues of the estimate against the target's, with the mixture as baseline: what
+the numbers above, which score each ear on its own, cannot see (the same mono waveform in both ears scores well on all of them and has
+lost the direction the target came from).  It needs C = 2 and tile = 16000: a mono call or any other tile is a ValueError that names
+the offending value, before any launch; the eleven numbers and the spectral ones do not change by a bit.  Per recording r there are
+three BINAURAL signals, all taken raw: G = references[r, target_r] (the target), E = estimate[r], B = mixture[r] (the baseline).  Tiles,
+windows and the spectrogram of a tile are exactly those of "Spectral" (spectral_table() serves both kernels).  The F = 512 bins form
+NB = 32 bands of 16 bins, band j = bins 16 j .. 16 j + 15, about 250 Hz wide.  With X_L, X_R the two ears' spectrograms of a signal x, a
+tile's four sums over a band's 16 bins x 32 frames, in this order:
+
+  0 PL = sum |X_L|^2   1 PR = sum |X_R|^2   2 CRE = sum Re(X_L conj X_R) = sum (ReL ReR + ImL ImR)
+  3 CIM = sum Im(X_L conj X_R) = sum (ImL ReR - ReL ImR)
+
+The tile sums are [R, J, 3, 32, 4] float64 (signal G, E, B; band; sum) and a window's sums are its tiles' sums added in tile order
+(m2h_score_windows with RC = R and K = 384).  Alignment: with align=D the region is [D, L - D) as above, but BOTH EARS of the estimate
+are read at ONE lag, lag[r, 0] (the left ear's whole-recording lag, clamped to [-D, D]): reading each ear at its own lag would cancel
+the very interaural delay that is being measured.  The per-ear lags are in the result ("lag") for whoever wants their difference.
+
+The cues of a signal in a band, from a window's sums (spatial_from_sums, element-wise torch float64 on any device):
+
+  ILD = 10 log10(PL / PR) dB       IPD = atan2(CIM, CRE) rad, positive when the right ear is late       IC = hypot(CRE, CIM) / sqrt(PL PR)
+
+The errors are band means weighted by the target's band energy w_j = PL_G + PR_G.  A band is valid for a signal x (E or B) where
+w_j > 0 and PL and PR of both G and x are > 0 (all three errors use this one rule); sums run over the valid bands only, numerator and
+denominator alike, and no valid band gives NaN.  The nine numbers, in SPATIAL_ORDER:
+
+  ild_err = sum w |ILD_E - ILD_G| / sum w                    over all 32 bands, dB
+  ipd_err = sum w |wrap(IPD_E - IPD_G)| / sum w              wrapped to (-pi, pi], over the bands 0 .. 5 (SPATIAL_IPD_BANDS: bins below 96,
+                                                             about 1.5 kHz, where phase is a usable cue), rad
+  ic_err  = sum w |IC_E - IC_G| / sum w                      over all 32 bands
+  ild_err_base, ipd_err_base, ic_err_base                    the same with B in place of E
+  ild_erri, ipd_erri, ic_erri                                baseline minus estimate (positive: closer to the target's image than the mixture)
+
+The whole-recording numbers are the long-term cues of the SUMMED spectra (all J tiles' sums added first), not the mean of the track.
+m2h_score_spatial (csrc/score_spatial.hip) computes the tile sums straight from the waveforms -- the same folded transform on the exact
+fp32 matrix instruction, the four fp32 values of a bin converted to fp64 before they are multiplied, no frame or spectrum ever in
+memory.  No host synchronisation; the only copy from the host is the transform table, once.  Not done: a broadband ITD in microseconds
+(a GCC-PHAT peak).
 """
 import operator
 
@@ -111,6 +149,9 @@ _NAN = float("nan")
 SPECTRAL_ORDER = ("stft_l2", "stft_l2_complex", "sc", "stft_l2_base", "stft_l2_complex_base", "sc_base", "stft_l2i", "stft_l2_complexi")
 SPECTRAL_TILE = 16000        # spectral=True: one second, the Separator's segment
 SPECTRAL_BINS, SPECTRAL_FRAMES, SPECTRAL_NFFT = 512, 32, 1023
+SPATIAL_ORDER = ("ild_err", "ipd_err", "ic_err", "ild_err_base", "ipd_err_base", "ic_err_base", "ild_erri", "ipd_erri", "ic_erri")
+SPATIAL_BANDS = 32           # spatial=True: bands of 16 bins, band j = bins 16 j .. 16 j + 15
+SPATIAL_IPD_BANDS = 6        # the phase error is taken over the bands 0 .. 5: bins below 96, about 1.5 kHz
 
 
 def score_plan(L, tile=DEFAULT_TILE, window=1, hop=1):
@@ -354,6 +395,46 @@ def spectral_from_sums(sums, Q):
     return torch.stack([l2, l2c, sc, l2b, l2cb, scb, l2b - l2, l2cb - l2c], dim=-1)
 
 
+def spatial_from_sums(sums):
+    """The interaural cues and their nine errors (module docstring, "Spatial") from band sums, element-wise in torch float64 on sums' device;
+    the bands are added by element-wise additions of slices in a fixed pairwise order (never a library reduction, which may pick another
+    order at another batch size), so a row's result does not depend on the batch around it.
+
+    sums [..., 3, 32, 4] float64 (signal G, E, B; band; PL, PR, CRE, CIM) -> (metrics [..., 9] in SPATIAL_ORDER,
+    cues [..., 3, 32, 3]: ILD in dB, IPD in rad, IC; IEEE rules apply in a band without energy)."""
+    import math
+    if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64:
+        raise TypeError("m2h.Scorer: spatial sums must be a float64 torch tensor, got %s" % (sums.dtype if isinstance(sums, torch.Tensor) else type(sums).__name__))
+    if sums.dim() < 3 or tuple(sums.shape[-3:]) != (3, SPATIAL_BANDS, 4):
+        raise ValueError("m2h.Scorer: spatial sums hold [3, %d, 4] numbers per row, got a tensor of shape %s" % (SPATIAL_BANDS, tuple(sums.shape),))
+    pl, pr, cre, cim = sums[..., 0], sums[..., 1], sums[..., 2], sums[..., 3]           # [..., 3, 32]
+    ild = 10.0 * torch.log10(pl / pr)
+    ipd = torch.atan2(cim, cre)
+    ic = torch.hypot(cre, cim) / torch.sqrt(pl * pr)
+    has = (pl > 0) & (pr > 0)
+    w = pl[..., 0, :] + pr[..., 0, :]                                                   # the target's band energy [..., 32]
+
+    def mean(d, ok, bands):
+        a = torch.stack([w * d, w])[..., :bands]                                        # numerator and denominator terms [2, ..., bands]
+        a = torch.where(ok[..., :bands], a, torch.zeros_like(a))
+        n = bands
+        while n > 1:                                                                    # halves added onto each other; an odd one out is carried
+            h = n // 2
+            a = torch.cat([a[..., :h] + a[..., h:2 * h], a[..., 2 * h:n]], dim=-1)
+            n = a.shape[-1]
+        return a[0, ..., 0] / a[1, ..., 0]                                              # 0 / 0: no valid band is NaN
+
+    def errors(x):
+        ok = (w > 0) & has[..., 0, :] & has[..., x, :]
+        d = ipd[..., x, :] - ipd[..., 0, :]
+        d = d - (2.0 * math.pi) * torch.ceil((d - math.pi) / (2.0 * math.pi))          # wrapped to (-pi, pi]
+        return [mean((ild[..., x, :] - ild[..., 0, :]).abs(), ok, SPATIAL_BANDS), mean(d.abs(), ok, SPATIAL_IPD_BANDS),
+                mean((ic[..., x, :] - ic[..., 0, :]).abs(), ok, SPATIAL_BANDS)]
+
+    e, b = errors(1), errors(2)
+    return torch.stack(e + b + [b[k] - e[k] for k in range(3)], dim=-1), torch.stack([ild, ipd, ic], dim=-1)
+
+
 class Scorer:
     def __init__(self, device, max_corr_bytes=DEFAULT_MAX_CORR_BYTES):
         if isinstance(max_corr_bytes, bool) or int(max_corr_bytes) < 1:
@@ -382,7 +463,7 @@ class Scorer:
             ev.record(torch.cuda.current_stream(self.device))
             self._timing.append((stage, ev))
 
-    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None):
+    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spatial=False):
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("m2h.Scorer: %s must be a torch tensor, got %s" % (name, type(t).__name__))
@@ -434,18 +515,24 @@ class Scorer:
         if not isinstance(target, int) and len(set(target)) == 1:
             target = target[0]
         plan = score_plan(L, tile, window, hop) if align is None else align_plan(L, align, tile, window, hop)      # raises on tile, window, hop, align
+        if spatial and C != 2:
+            raise ValueError("m2h.Scorer: spatial=True compares the two ears and needs C = 2 channels, got C = %d" % C)
+        if spatial and plan["tile"] != SPECTRAL_TILE:
+            raise ValueError("m2h.Scorer: spatial=True needs tile = %d (one second), got %d" % (SPECTRAL_TILE, plan["tile"]))
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not t.is_cuda or t.device != self.device:
                 raise ValueError("m2h.Scorer: %s must live on %s, got %s; the scorer has no CPU path" % (name, self.device, t.device))
         return refs, est, target, plan
 
-    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None, spectral=False):
+    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None, spectral=False, spatial=False):
         """-> {"whole": [R, C, 11], "track": [R, C, M, 11], "active": [R, C, M] bool, "plan": score_plan(...)}; float64 on the device, in
         eval_metrics.METRIC_ORDER; no host synchronisation.  With align=D (an int, the largest lag searched in samples) the estimate is
         aligned to its target first: also "lag": [R, C] int32 and "lag_track": [R, C, M] int32 on the device, and "plan" is
         align_plan(...).  With spectral=True (tile must be 16000) also "spectral_whole": [R, C, 8] and "spectral_track": [R, C, M, 8],
-        float64 in SPECTRAL_ORDER.  The module docstring holds the definition."""
-        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align)
+        float64 in SPECTRAL_ORDER.  With spatial=True (two channels, tile must be 16000) also "spatial_whole": [R, 9] and
+        "spatial_track": [R, M, 9], float64 in SPATIAL_ORDER, and the cues themselves, "spatial_cues": [R, M, 3, 32, 3] (signal target /
+        estimate / mixture, band, ILD / IPD / IC).  The module docstring holds the definition."""
+        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spatial)
         if spectral and plan["tile"] != SPECTRAL_TILE:
             raise ValueError("m2h.Scorer: spectral=True needs tile = %d (one second), got %d" % (SPECTRAL_TILE, plan["tile"]))
         R, S, C, L = refs.shape
@@ -494,13 +581,23 @@ class Scorer:
                 spec = spectral_from_sums(sums, torch.cat([torch.full((1,), float(J), dtype=torch.float64, device=dev), q]))
                 out.update({"spectral_whole": spec[:, :, 0], "spectral_track": spec[:, :, 1:]})
                 self._mark("spectral_metrics")
+            if spatial:
+                sums = ops.score_spatial(refs, est, mixture, target, self._spectral_table(), out.get("lag"), D)         # [R, J, 3, 32, 4]
+                self._mark("score_spatial")
+                K = 3 * SPATIAL_BANDS * 4
+                sums = sums.view(R, 1, J, K)
+                sums = torch.cat([ops.score_windows(sums, 1, J, 1), ops.score_windows(sums, M, window, hop)], dim=2)
+                spat, cues = spatial_from_sums(sums.view(R, 1 + M, 3, SPATIAL_BANDS, 4))
+                out.update({"spatial_whole": spat[:, 0], "spatial_track": spat[:, 1:], "spatial_cues": cues[:, 1:]})
+                self._mark("spatial_metrics")
         out.update({"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan})
         return out
 
 
 def summarize(result):
     """Host-side summary of Scorer.score's result for one call: {"metrics", "whole": [R][C][11], "track_mean", "track_median": over the
-    active windows ([R][C][11], NaN without any), "active_windows": [R][C]} as Python lists (one synchronisation)."""
+    active windows ([R][C][11], NaN without any), "active_windows": [R][C]} as Python lists (one synchronisation); with spectral=True /
+    spatial=True results also the "spectral_*" / "spatial_*" keys (spatial: [R][9], over the windows in which both ears are active)."""
     import numpy as np
     whole, track, active = (result[k].cpu().numpy() for k in ("whole", "track", "active"))
     R, C = whole.shape[:2]
@@ -524,4 +621,14 @@ def summarize(result):
                         smean[r, c], smedian[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
         out.update({"spectral_metrics": list(SPECTRAL_ORDER), "spectral_whole": sw.tolist(), "spectral_track_mean": smean.tolist(),
                     "spectral_track_median": smedian.tolist()})
+    if "spatial_whole" in result:                                                       # score(..., spatial=True): over the windows in which BOTH ears are active
+        pw, pt = result["spatial_whole"].cpu().numpy(), result["spatial_track"].cpu().numpy()
+        pmean, pmedian = np.full((R, 9), np.nan), np.full((R, 9), np.nan)
+        with np.errstate(all="ignore"):
+            for r in range(R):
+                rows = pt[r][active[r].all(axis=0)]
+                if rows.shape[0]:
+                    pmean[r], pmedian[r] = rows.mean(axis=0), np.median(rows, axis=0)
+        out.update({"spatial_metrics": list(SPATIAL_ORDER), "spatial_whole": pw.tolist(), "spatial_track_mean": pmean.tolist(),
+                    "spatial_track_median": pmedian.tolist()})
     return out

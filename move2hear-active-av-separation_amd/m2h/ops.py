@@ -816,6 +816,30 @@ def score_spectral(refs, est, mix, target, dft, lag=None, D=0):
     return out
 
 
+def score_spatial(refs, est, mix, target, dft, lag=None, D=0):
+    """Tile sums of the Scorer's interaural cues (m2h/audio/score.py, "Spatial"): refs [R, S, 2, L], est [R, 2, L], mix [R, 2, L] fp32 with
+    unit last stride (views are read in place); target, dft, lag and D as for score_spectral, but BOTH ears of the estimate are read
+    lag[r, 0] samples later -> [R, J, 3, 32, 4] fp64: signal (target, estimate, mixture), band of 16 bins, (PL, PR, CRE, CIM);
+    J = ceil((L - 2 D) / 16000) (include/m2h.h)."""
+    R, S, C, L = _score_signals("score_spatial", refs, est, mix)
+    if C != 2:
+        raise RuntimeError("m2h.score_spatial: C = %d channels; interaural cues need 2" % C)
+    D = int(D)
+    if not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
+        raise RuntimeError("m2h.score_spatial: D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required" % (D, L))
+    _chk(dft, "score_spatial(dft)")
+    if tuple(dft.shape) != SPECTRAL_TABLE_SHAPE or dft.device != refs.device:
+        raise RuntimeError("m2h.score_spatial: dft must be the %s table on %s" % (list(SPECTRAL_TABLE_SHAPE), refs.device))
+    lptr = None if lag is None else _score_lag("score_spatial", lag, refs)
+    tptr, t0 = _score_target("score_spatial", target, refs)
+    out = torch.empty((R, -(-(L - 2 * D) // 16000), 3, 32, 4), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_score_spatial(*_score_args(refs, est, mix), tptr, t0, _ptr(dft), _ptr(out), R, S, L, lptr, D, _stream(refs)),
+                   "m2h_score_spatial")
+    return out
+
+
 def score_windows(tiles, M, window, hop):
     """tiles [R, C, J, K] fp64 -> [R, C, M, K]: every window's tiles added in tile order (window m: tiles m * hop .. m * hop + window - 1)."""
     _chk(tiles, "score_windows", torch.float64)

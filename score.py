@@ -2,7 +2,7 @@
 """Score a separated recording of any length against its ground truth:
 
     python score.py --estimate out.wav --mixture mix.wav --reference target.wav [--reference other.wav ...] [--window W --hop H]
-                    [--align D] [--spectral] [--json scores.json]
+                    [--align D] [--spectral] [--spatial] [--json scores.json]
 
 ``--reference``: the sources as they are in the mixture, at most six; the FIRST one is the target the estimate is scored against, the
 others are the interferers (they enter SI-SIR and SI-SAR).  ``render.py --out-target / --out-image`` writes such files.  ``--mixture``:
@@ -23,6 +23,13 @@ silent).  ``--json`` writes everything, the per-window track included.  Definiti
 for the mixture as the estimate, and the two improvements; m2h/audio/score.py, "Spectral") for the same whole recording and the same
 windows, as rows under the table and as ``spectral_*`` keys in the JSON.  For two-channel files the paper's binaural distance is the
 sum of the two ears' ``stft_l2``.
+
+``--spatial`` (two-channel files only) adds what the numbers above cannot see, whether the estimate kept the target's spatial image:
+the errors of the interaural level difference (dB), phase difference (rad, below 1.5 kHz) and coherence of the estimate against the
+target's, per window and over the whole recording, the same for the mixture as the estimate, and the three improvements
+(m2h/audio/score.py, "Spatial"), as rows under the table and as ``spatial_*`` keys in the JSON; the JSON also holds the cues
+themselves per window, signal (target, estimate, mixture) and 250 Hz band (``spatial_cues``).  With ``--align`` both ears of the
+estimate are read at the left ear's lag.
 """
 import argparse
 import json
@@ -57,6 +64,7 @@ def main():
     parser.add_argument("--hop", type=int, default=1, help="a window every HOP seconds")
     parser.add_argument("--align", type=int, default=None, metavar="D", help="align the estimate to the target first: the largest lag searched, in samples (1 .. 8192)")
     parser.add_argument("--spectral", action="store_true", help="also the STFT distance per window and over the whole recording")
+    parser.add_argument("--spatial", action="store_true", help="also the interaural cue errors (ILD, IPD, IC) per window and over the whole recording; two-channel files")
     parser.add_argument("--json", default=None, help="write every number here")
     args = parser.parse_args()
     import numpy as np
@@ -69,6 +77,8 @@ def main():
         if x.shape[0] != est.shape[0]:
             raise SystemExit("score.py: %s has %d channel%s and %s has %d; the estimate and every reference need the same count"
                              % (args.estimate, est.shape[0], "" if est.shape[0] == 1 else "s", path, x.shape[0]))
+    if args.spatial and est.shape[0] != 2:
+        raise SystemExit("score.py: --spatial compares the two ears: two channels are needed, and %s has %d" % (args.estimate, est.shape[0]))
     for path, x in [(args.mixture, mix)] + list(zip(args.reference, refs)):
         if x.shape[1] != est.shape[1]:
             raise SystemExit("score.py: %s is %d samples long and %s is %d; equal lengths are required (with --align too)"
@@ -80,7 +90,7 @@ def main():
     try:
         res = Scorer(dev).score(torch.from_numpy(np.ascontiguousarray(est)).to(dev)[None], torch.from_numpy(np.stack(refs)).to(dev)[None],
                                 torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop, align=args.align,
-                                spectral=args.spectral)
+                                spectral=args.spectral, **({"spatial": True} if args.spatial else {}))
     except (ValueError, TypeError) as e:
         raise SystemExit("score.py: %s" % e)
     s = summarize(res)
@@ -105,6 +115,10 @@ def main():
         for c in range(C):
             for label, key in (("spectral whole", "spectral_whole"), ("spectral window mean", "spectral_track_mean"), ("spectral window median", "spectral_track_median")):
                 print("%-8s %-23s" % (names[c], label) + " ".join("%20.12e" % v for v in s[key][0][c]))
+    if args.spatial:
+        print("%-8s %-23s" % ("spatial", "") + " ".join("%20s" % m for m in s["spatial_metrics"]))
+        for label, key in (("spatial whole", "spatial_whole"), ("spatial window mean", "spatial_track_mean"), ("spatial window median", "spatial_track_median")):
+            print("%-8s %-23s" % ("binaural", label) + " ".join("%20.12e" % v for v in s[key][0]))
     if args.json is not None:
         out = {"estimate": args.estimate, "mixture": args.mixture, "references": args.reference, "sample_rate": separate.SAMPLE_RATE,
                "samples": L, "channels": list(names), "window_s": args.window, "hop_s": args.hop, "metrics": s["metrics"],
@@ -115,6 +129,10 @@ def main():
             out.update({"spectral_metrics": s["spectral_metrics"], "spectral_whole": s["spectral_whole"][0],
                         "spectral_track": res["spectral_track"][0].cpu().numpy().tolist(), "spectral_track_mean": s["spectral_track_mean"][0],
                         "spectral_track_median": s["spectral_track_median"][0]})
+        if args.spatial:
+            out.update({"spatial_metrics": s["spatial_metrics"], "spatial_whole": s["spatial_whole"][0],
+                        "spatial_track": res["spatial_track"][0].cpu().numpy().tolist(), "spatial_track_mean": s["spatial_track_mean"][0],
+                        "spatial_track_median": s["spatial_track_median"][0], "spatial_cues": res["spatial_cues"][0].cpu().numpy().tolist()})
         if args.align is not None:
             out.update({"align": args.align, "region": [t0, t1], "lag": lag, "lag_track": res["lag_track"][0].cpu().tolist()})
         with open(args.json, "w") as f:

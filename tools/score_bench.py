@@ -7,6 +7,8 @@
     python tools/score_bench.py --case 1x2x60c2 --align 8192         # one case of it in this process
     python tools/score_bench.py --spectral --out profiles/score_spectral_bench.json                 # the STFT distance, every case
     python tools/score_bench.py --case 16x3x600c1 --spectral         # one case of it in this process
+    python tools/score_bench.py --spatial --out profiles/score_spatial_bench.json                   # the interaural cues, the two-channel cases
+    python tools/score_bench.py --case 16x3x600c2 --spatial          # one case of it in this process
 
 Cases (R recordings x S sources x seconds, C channels): 16x3x600 and 1x2x60, each with C = 1 and C = 2; per-second windows.  Timing: HIP
 events on the stream around the Gram launch and around everything after it (Scorer._timing), summed over the repetitions.
@@ -35,6 +37,14 @@ With --spectral (the m2h_score_spectral launch of Scorer.score(..., spectral=Tru
                           m2h.audio.stft.STFT on the three signals' seconds (frames and spectra stored), then torch float64 reductions,
                           one recording at a time; its largest relative difference from the kernel's sums is recorded
   extra_ms_in_score       what spectral=True adds to one Scorer.score (launch, two m2h_score_windows, spectral_from_sums)
+With --spatial (the m2h_score_spatial launch of Scorer.score(..., spatial=True), timed alone with HIP events, twice; two-channel cases
+only: the cues compare the ears, a mono case has none):
+  spatial_ms              one launch: the [3, 32, 4] fp64 band sums of every (recording, second) straight from the waveforms
+  spectral_c2_ms, spatial_over_spectral   m2h_score_spectral on the same tensors in the same run (the same six transforms per second)
+  stored_spectrum_ms      the same sums from m2h_stft_frames, the fp32 GEMM of m2h.audio.stft.STFT on the six signals' seconds (frames and
+                          spectra stored) and torch float64 reductions, before and after; its largest difference from the kernel's sums,
+                          relative to the band's energies sqrt(PL PR) (a cross term may be near 0), is recorded
+  extra_ms_in_score       what spatial=True adds to one Scorer.score (launch, two m2h_score_windows, spatial_from_sums)
 No threshold is set anywhere: the file reports what came out.  Every GPU step runs under its own timeout and the driver stops at the
 first failure.
 """
@@ -214,6 +224,87 @@ def run_spectral_case(case):
     return res
 
 
+def stored_spectrum_band_sums(stft, sig):
+    """[R, J, 3, 32, 4] float64 from the existing pieces: sig [R, 3, 2, L] (L a multiple of a second) -> frames and spectra of every second
+    stored by m2h_stft_frames and the fp32 GEMM of `stft`, then torch float64 reductions; one recording at a time"""
+    import torch
+    from m2h import _lib, ops
+    lib = _lib.load()
+    R, _, _, L = sig.shape
+    J, T, nb = L // SEG, 32, stft.nb
+    out = []
+    for r in range(R):
+        wave = sig[r].reshape(6 * J, SEG).contiguous()
+        frames = torch.empty((6 * J * T, stft.ld), device=sig.device)
+        _lib.check(lib.m2h_stft_frames(ops._ptr(wave), ops._ptr(stft.window), ops._ptr(frames), 6 * J, SEG, T, stft.n_fft, stft.hop, stft.ld,
+                                       ops._stream(wave)), "m2h_stft_frames")
+        spec = ops.linear(frames, stft.W, None, name="stft.dft").view(3, 2, J, T, stft.ld)
+        re, im = spec[..., :nb].double(), spec[..., nb:2 * nb].double()
+        lr, li, rr, ri = re[:, 0], im[:, 0], re[:, 1], im[:, 1]                              # [3, J, T, 512]
+        terms = torch.stack([lr * lr + li * li, rr * rr + ri * ri, lr * rr + li * ri, li * rr - lr * ri], dim=-1)
+        out.append(terms.view(3, J, T, 32, 16, 4).sum(dim=(2, 4)).transpose(0, 1))          # [J, 3, 32, 4]
+    return torch.stack(out)
+
+
+def run_spatial_case(case):
+    import torch
+    from m2h import ops
+    from m2h.audio.score import Scorer
+    from m2h.audio.stft import STFT
+    if not torch.cuda.is_available():
+        raise SystemExit("score_bench: no GPU; this measurement has no CPU path")
+    R, S, seconds, C, reps = CASES[case]
+    if C != 2:
+        raise SystemExit("score_bench: --spatial compares the two ears; case %s is mono" % case)
+    dev = torch.device("cuda", 0)
+    L = seconds * SEG
+    g = torch.Generator(device=dev).manual_seed(7)
+    refs = torch.randn((R, S, C, L), device=dev, generator=g) * 0.1 + 0.01
+    mix = torch.stack([refs[:, :, 0].mean(1), refs[:, :, C - 1].mean(1)], dim=1) + 0.02 * torch.randn((R, 2, L), device=dev, generator=g)
+    est = 0.8 * refs[:, 0] + 0.03 * torch.randn((R, C, L), device=dev, generator=g)
+    sc, stft = Scorer(dev), STFT(dev)
+    table = sc._spectral_table()
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    kernel = lambda: ops.score_spatial(refs, est, mix, 0, table)                        # noqa: E731
+    yardstick = lambda: ops.score_spectral(refs, est, mix, 0, table)                    # noqa: E731
+    stored = lambda: stored_spectrum_band_sums(stft, torch.stack([refs[:, 0], est, mix], dim=1))   # noqa: E731
+    res0 = sc.score(est, refs, mix, spatial=True)                                       # warm-up of every shape
+    got, want = kernel(), stored()
+    scale = torch.sqrt(want[..., 0:1] * want[..., 1:2])
+    diff = float(((got - want).abs() / scale).max())
+    del want, scale
+    yardstick()
+    torch.cuda.synchronize()
+    n_stored = max(1, reps // 10)
+    before = timed(stored, n_stored)
+    ms = timed(kernel, reps)
+    spec = timed(yardstick, reps)
+    plain = timed(lambda: sc.score(est, refs, mix), reps)
+    full = timed(lambda: sc.score(est, refs, mix, spatial=True), reps)
+    after = timed(stored, n_stored)
+    ms2 = timed(kernel, reps)
+    spec2 = timed(yardstick, reps)
+    flops = R * C * seconds * SPECTRAL_FLOPS_PER_TILE
+    res = {"case": case, "spatial": True, "R": R, "S": S, "C": C, "audio_seconds_per_recording": seconds, "reps": reps, "workgroups": 3 * R * seconds,
+           "spatial_ms": [ms, ms2], "spectral_c2_ms": [spec, spec2], "spatial_over_spectral": (ms + ms2) / (spec + spec2), "flops_unfolded": flops,
+           "flops_per_s_unfolded": flops / (min(ms, ms2) * 1e-3), "share_of_fp32_matrix_peak": flops / (min(ms, ms2) * 1e-3) / FP32_MATRIX_PEAK,
+           "stored_spectrum_ms": [before, after], "stored_spectrum_reps": n_stored, "stored_over_kernel": 0.5 * (before + after) / (0.5 * (ms + ms2)),
+           "score_ms": plain, "score_spatial_ms": full, "extra_ms_in_score": full - plain, "audio_s_per_s": R * seconds / (full * 1e-3),
+           "kernel_vs_stored_max_rel_to_band_energy": diff, "ild_err_whole_db": float(res0["spatial_whole"][0, 0])}
+    print(json.dumps(res))
+    return res
+
+
 def run_align_case(case, D):
     import torch
     from m2h.audio.score import Scorer, lags_from_corr
@@ -291,13 +382,16 @@ def main():
     ap.add_argument("--case", choices=sorted(CASES), default=None)
     ap.add_argument("--align", type=int, action="append", default=None, metavar="D", help="measure the aligned scorer at this largest lag (repeat)")
     ap.add_argument("--spectral", action="store_true", help="measure the STFT distance's launch (Scorer.score(..., spectral=True))")
+    ap.add_argument("--spatial", action="store_true", help="measure the interaural cues' launch (Scorer.score(..., spatial=True)); two-channel cases")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=120, help="driver mode: seconds per case")
     args = ap.parse_args()
-    if args.spectral and args.align:
-        raise SystemExit("score_bench: --spectral and --align are measured separately")
+    if (args.spectral or args.spatial) and args.align or args.spectral and args.spatial:
+        raise SystemExit("score_bench: --spectral, --spatial and --align are measured separately")
     if args.case is not None:
-        if args.spectral:
+        if args.spatial:
+            run_spatial_case(args.case)
+        elif args.spectral:
             run_spectral_case(args.case)
         elif args.align:
             for D in args.align:
@@ -306,9 +400,9 @@ def main():
             run_case(args.case)
         return
     results = []
-    for case, D in [(case, D) for D in (args.align or [None]) for case in ORDER]:
+    for case, D in [(case, D) for D in (args.align or [None]) for case in ORDER if CASES[case][3] == 2 or not args.spatial]:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case] + ([] if D is None else ["--align", str(D)]) + \
-            (["--spectral"] if args.spectral else [])
+            (["--spectral"] if args.spectral else []) + (["--spatial"] if args.spatial else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             print(r.stdout[-4000:])
@@ -319,7 +413,7 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/score_bench.py", "device": "MI355X (gfx950)", "copy_rate_bytes_per_s": COPY_RATE,
-                       **({"fp32_matrix_peak_flops_per_s": FP32_MATRIX_PEAK} if args.spectral else {}), "results": results}, f, indent=1)
+                       **({"fp32_matrix_peak_flops_per_s": FP32_MATRIX_PEAK} if args.spectral or args.spatial else {}), "results": results}, f, indent=1)
             f.write("\n")
 
 
