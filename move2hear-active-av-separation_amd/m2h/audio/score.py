@@ -435,6 +435,11 @@ def spatial_from_sums(sums):
     return torch.stack(e + b + [b[k] - e[k] for k in range(3)], dim=-1), torch.stack([ild, ipd, ic], dim=-1)
 
 
+def _whole_then_track(tiles, plan):
+    """tiles [R, C, J, K] float64 -> [R, C, 1 + M, K]: all J tiles added in tile order, then the plan's M windows"""
+    return torch.cat([ops.score_windows(tiles, 1, plan["J"], 1), ops.score_windows(tiles, plan["M"], plan["window"], plan["hop"])], dim=2)
+
+
 class Scorer:
     def __init__(self, device, max_corr_bytes=DEFAULT_MAX_CORR_BYTES):
         if isinstance(max_corr_bytes, bool) or int(max_corr_bytes) < 1:
@@ -463,7 +468,7 @@ class Scorer:
             ev.record(torch.cuda.current_stream(self.device))
             self._timing.append((stage, ev))
 
-    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spatial=False):
+    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spectral=False, spatial=False):
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("m2h.Scorer: %s must be a torch tensor, got %s" % (name, type(t).__name__))
@@ -517,8 +522,9 @@ class Scorer:
         plan = score_plan(L, tile, window, hop) if align is None else align_plan(L, align, tile, window, hop)      # raises on tile, window, hop, align
         if spatial and C != 2:
             raise ValueError("m2h.Scorer: spatial=True compares the two ears and needs C = 2 channels, got C = %d" % C)
-        if spatial and plan["tile"] != SPECTRAL_TILE:
-            raise ValueError("m2h.Scorer: spatial=True needs tile = %d (one second), got %d" % (SPECTRAL_TILE, plan["tile"]))
+        for name, on in (("spatial", spatial), ("spectral", spectral)):
+            if on and plan["tile"] != SPECTRAL_TILE:
+                raise ValueError("m2h.Scorer: %s=True needs tile = %d (one second), got %d" % (name, SPECTRAL_TILE, plan["tile"]))
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not t.is_cuda or t.device != self.device:
                 raise ValueError("m2h.Scorer: %s must live on %s, got %s; the scorer has no CPU path" % (name, self.device, t.device))
@@ -532,9 +538,7 @@ class Scorer:
         float64 in SPECTRAL_ORDER.  With spatial=True (two channels, tile must be 16000) also "spatial_whole": [R, 9] and
         "spatial_track": [R, M, 9], float64 in SPATIAL_ORDER, and the cues themselves, "spatial_cues": [R, M, 3, 32, 3] (signal target /
         estimate / mixture, band, ILD / IPD / IC).  The module docstring holds the definition."""
-        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spatial)
-        if spectral and plan["tile"] != SPECTRAL_TILE:
-            raise ValueError("m2h.Scorer: spectral=True needs tile = %d (one second), got %d" % (SPECTRAL_TILE, plan["tile"]))
+        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial)
         R, S, C, L = refs.shape
         J, M, tile, window, hop = (plan[k] for k in ("J", "M", "tile", "window", "hop"))
         D = plan.get("offset", 0)
@@ -559,14 +563,14 @@ class Scorer:
                     r1 = min(r0 + step, R)
                     ct = ops.align_corr(refs[r0:r1], est[r0:r1], target if isinstance(target, int) else target[r0:r1], tile, D, tw)     # [r, C, J, 2 D + 1]
                     self._mark("align_corr")
-                    lags.append(lags_from_corr(torch.cat([ops.score_windows(ct, 1, J, 1), ops.score_windows(ct, M, window, hop)], dim=2)))
+                    lags.append(lags_from_corr(_whole_then_track(ct, plan)))
                     del ct
                     self._mark("lag_pick")
                 lags = lags[0] if len(lags) == 1 else torch.cat(lags)                   # [R, C, 1 + M]: whole, then the track
                 out["lag"], out["lag_track"] = lags[:, :, 0].contiguous(), lags[:, :, 1:]
                 tiles = ops.score_gram_lag(refs, est, mixture, tile, out["lag"], D)
             self._mark("score_gram")
-            gram = torch.cat([ops.score_windows(tiles, 1, J, 1), ops.score_windows(tiles, M, window, hop)], dim=2)      # whole, then the track
+            gram = _whole_then_track(tiles, plan)
             m = torch.arange(M, device=dev, dtype=torch.int64) * hop
             n = (torch.clamp((m + window) * tile, max=Ls) - torch.clamp(m * tile, max=Ls)).to(torch.float64)
             n = torch.cat([torch.full((1,), float(Ls), dtype=torch.float64, device=dev), n])
@@ -576,7 +580,7 @@ class Scorer:
             if spectral:
                 sums = ops.score_spectral(refs, est, mixture, target, self._spectral_table(), out.get("lag"), D)        # [R, C, J, 7]
                 self._mark("score_spectral")
-                sums = torch.cat([ops.score_windows(sums, 1, J, 1), ops.score_windows(sums, M, window, hop)], dim=2)
+                sums = _whole_then_track(sums, plan)
                 q = (torch.clamp(m + window, max=J) - torch.clamp(m, max=J)).to(torch.float64)
                 spec = spectral_from_sums(sums, torch.cat([torch.full((1,), float(J), dtype=torch.float64, device=dev), q]))
                 out.update({"spectral_whole": spec[:, :, 0], "spectral_track": spec[:, :, 1:]})
@@ -586,7 +590,7 @@ class Scorer:
                 self._mark("score_spatial")
                 K = 3 * SPATIAL_BANDS * 4
                 sums = sums.view(R, 1, J, K)
-                sums = torch.cat([ops.score_windows(sums, 1, J, 1), ops.score_windows(sums, M, window, hop)], dim=2)
+                sums = _whole_then_track(sums, plan)
                 spat, cues = spatial_from_sums(sums.view(R, 1 + M, 3, SPATIAL_BANDS, 4))
                 out.update({"spatial_whole": spat[:, 0], "spatial_track": spat[:, 1:], "spatial_cues": cues[:, 1:]})
                 self._mark("spatial_metrics")

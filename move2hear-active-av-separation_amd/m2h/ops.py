@@ -794,21 +794,27 @@ def score_gram_lag(refs, est, mix, tile, lag, D):
 SPECTRAL_TABLE_SHAPE = (32, 128, 2, 64)      # m2h_score_spectral's folded transform table (include/m2h.h)
 
 
+def _score_stft(what, refs, dft, target, lag, D):
+    """what score_spectral and score_spatial share beyond the signals: the D / lag rule, the table, the lag and target arguments
+    -> (D, J, lag pointer, target pointer, target int)"""
+    L, D = refs.shape[3], int(D)
+    if not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
+        raise RuntimeError("m2h.%s: D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required" % (what, D, L))
+    _chk(dft, "%s(dft)" % what)
+    if tuple(dft.shape) != SPECTRAL_TABLE_SHAPE or dft.device != refs.device:
+        raise RuntimeError("m2h.%s: dft must be the %s table on %s" % (what, list(SPECTRAL_TABLE_SHAPE), refs.device))
+    lptr = None if lag is None else _score_lag(what, lag, refs)
+    return (D, -(-(L - 2 * D) // 16000), lptr) + _score_target(what, target, refs)
+
+
 def score_spectral(refs, est, mix, target, dft, lag=None, D=0):
     """Tile sums of the Scorer's STFT distance (m2h/audio/score.py, "Spectral"): refs [R, S, C, L], est [R, C, L], mix [R, 2, L] fp32 with
     unit last stride (views are read in place); target an int, or an int64 tensor [R] on the device; dft: the [32, 128, 2, 64] table of
     m2h.audio.score.spectral_table on the device; lag [R, C] int32 on the device with D in 1 .. 8192 (the region [D, L - D), the estimate
     read lag[r, c] samples later), or None with D = 0 -> [R, C, J, 7] fp64, J = ceil((L - 2 D) / 16000) (include/m2h.h)."""
     R, S, C, L = _score_signals("score_spectral", refs, est, mix)
-    D = int(D)
-    if not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
-        raise RuntimeError("m2h.score_spectral: D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required" % (D, L))
-    _chk(dft, "score_spectral(dft)")
-    if tuple(dft.shape) != SPECTRAL_TABLE_SHAPE or dft.device != refs.device:
-        raise RuntimeError("m2h.score_spectral: dft must be the %s table on %s" % (list(SPECTRAL_TABLE_SHAPE), refs.device))
-    lptr = None if lag is None else _score_lag("score_spectral", lag, refs)
-    tptr, t0 = _score_target("score_spectral", target, refs)
-    out = torch.empty((R, C, -(-(L - 2 * D) // 16000), 7), device=refs.device, dtype=torch.float64)
+    D, J, lptr, tptr, t0 = _score_stft("score_spectral", refs, dft, target, lag, D)
+    out = torch.empty((R, C, J, 7), device=refs.device, dtype=torch.float64)
     lib = _lib.load()
     with torch.cuda.device(refs.device):
         _lib.check(lib.m2h_score_spectral(*_score_args(refs, est, mix), tptr, t0, _ptr(dft), _ptr(out), R, S, C, L, lptr, D, _stream(refs)),
@@ -824,15 +830,8 @@ def score_spatial(refs, est, mix, target, dft, lag=None, D=0):
     R, S, C, L = _score_signals("score_spatial", refs, est, mix)
     if C != 2:
         raise RuntimeError("m2h.score_spatial: C = %d channels; interaural cues need 2" % C)
-    D = int(D)
-    if not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
-        raise RuntimeError("m2h.score_spatial: D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required" % (D, L))
-    _chk(dft, "score_spatial(dft)")
-    if tuple(dft.shape) != SPECTRAL_TABLE_SHAPE or dft.device != refs.device:
-        raise RuntimeError("m2h.score_spatial: dft must be the %s table on %s" % (list(SPECTRAL_TABLE_SHAPE), refs.device))
-    lptr = None if lag is None else _score_lag("score_spatial", lag, refs)
-    tptr, t0 = _score_target("score_spatial", target, refs)
-    out = torch.empty((R, -(-(L - 2 * D) // 16000), 3, 32, 4), device=refs.device, dtype=torch.float64)
+    D, J, lptr, tptr, t0 = _score_stft("score_spatial", refs, dft, target, lag, D)
+    out = torch.empty((R, J, 3, 32, 4), device=refs.device, dtype=torch.float64)
     lib = _lib.load()
     with torch.cuda.device(refs.device):
         _lib.check(lib.m2h_score_spatial(*_score_args(refs, est, mix), tptr, t0, _ptr(dft), _ptr(out), R, S, L, lptr, D, _stream(refs)),

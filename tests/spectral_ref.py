@@ -162,6 +162,18 @@ def clicks(seed=0, L=TILE):
     return g[None, None, :L].astype(np.float32), e[None, :L].astype(np.float32), mix[:, :L].astype(np.float32)
 
 
+def fold_on_the_table(x, table):
+    """one second x -> (re, im) float32 [T, F] the way m2h_score_spectral and m2h_score_spatial compute them: raw frames, x[n] +- x[1023 - n]
+    in float32, a float32 product against the rows n = 0 .. 511 of table = m2h.audio.score.spectral_table()"""
+    t = table                                                                           # [bt, ks, q, l]
+    assert t.dtype == np.float32 and t.shape == (32, 128, 2, 64)
+    t = t.reshape(32, 128, 2, 4, 16).transpose(2, 1, 3, 0, 4).reshape(2, 512, 512)       # [q, n = 4 ks + (l >> 4), k = 16 bt + (l & 15)]
+    xp = np.pad(np.asarray(x, np.float32), PAD, mode="reflect")
+    fr = np.stack([xp[f * HOP:f * HOP + NFFT + 1] for f in range(T)])                   # (sample 1023 is the partner of n = 0, whose table row is 0)
+    lo, hi = fr[:, :512], fr[:, :511:-1]                                                # x[n] and x[1023 - n], n = 0 .. 511
+    return (lo + hi) @ t[0], (lo - hi) @ t[1]
+
+
 def worst(got, want, bound):
     """the largest |got - want| / bound; a difference where the bound is 0 counts as inf"""
     d = np.abs(np.asarray(got, np.float64) - want)

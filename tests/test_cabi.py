@@ -143,6 +143,30 @@ def test_scorer_refusals_name_their_own_entry_point():
     assert lib.m2h_launch_count() == n0
 
 
+def test_stft_scorer_refusals_name_their_own_entry_point():
+    """m2h_score_spectral and m2h_score_spatial share one sequence of checks (csrc/score_stft.h): one refused call per shared check, each
+    message names the entry that was called, and nothing is launched.  Refusals return before any HIP call, so this runs without a GPU."""
+    lib = _lib.load()
+    p, odd = ctypes.c_void_p(256), ctypes.c_void_p(260)          # never dereferenced
+    n0 = lib.m2h_launch_count()
+
+    def spectral(target0=0, dft=p, out=p, L=100, lag=None, D=0):
+        return lib.m2h_score_spectral(p, 300, 100, 0, p, 100, 0, p, 200, 100, None, target0, dft, out, 2, 3, 1, L, lag, D, None)
+
+    def spatial(target0=0, dft=p, out=p, L=100, lag=None, D=0):
+        return lib.m2h_score_spatial(p, 600, 200, 100, p, 200, 100, p, 200, 100, None, target0, dft, out, 2, 3, L, lag, D, None)
+
+    rows = [(dict(dft=None), b"null pointer (dft)"), (dict(lag=p), b"a lag table needs D >= 1"), (dict(D=1), b"a null pointer needs D = 0"),
+            (dict(target0=3), b"target = 3"), (dict(target0=-1), b"target = -1"), (dict(out=odd), b"out must be 8-byte aligned"),
+            (dict(lag=p, D=50, L=100), b"L = 100 samples; at least 2 D + 1 = 101")]
+    for name, call in ((b"score_spectral", spectral), (b"score_spatial", spatial)):
+        for kw, text in rows:
+            assert call(**kw) < 0, (name, kw)
+            msg = lib.m2h_last_error()
+            assert msg.startswith(name + b": ") and text in msg, (name, kw, msg)
+    assert lib.m2h_launch_count() == n0
+
+
 def test_rollout_kernel_refusals_name_their_own_entry_point():
     """Argument refusals of the rollout kernels (tests/rollout_kernels.py has their rows): each returns before any launch and names the
     entry that was called, so this runs without a GPU."""

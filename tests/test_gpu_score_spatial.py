@@ -13,16 +13,14 @@ import numpy as np
 import pytest
 import torch
 
-import score_ref
 import spatial_ref as REF
 import spectral_ref as SR
+from score_cases import LMAX, R, _gpu, _same, _target, _write_wav, batch, recordings, targets
 from m2h import ops
 from m2h.audio import score as SC
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-R = 2
-LMAX = 40001
 KEYS = ("spatial_whole", "spatial_track", "spatial_cues")
 
 
@@ -41,53 +39,13 @@ def table(dev):
     return torch.from_numpy(SC.spectral_table()).to(dev)
 
 
-_inputs, _refs = {}, {}
-
-
-def batch(S):
-    """R two-channel recordings of score_ref.inputs at LMAX samples: refs [R, S, 2, L], est [R, 2, L], mix [R, 2, L]; made once, read-only"""
-    if S not in _inputs:
-        _inputs[S] = tuple(np.stack(a) for a in zip(*[score_ref.inputs(S, LMAX, 31 + 50 * r, 2) for r in range(R)]))
-        for a in _inputs[S]:
-            a.setflags(write=False)
-    return _inputs[S]
-
-
 def click_batch():
-    if "clicks" not in _inputs:
-        _inputs["clicks"] = tuple(np.stack(a) for a in zip(*[REF.click_pairs(seed=r) for r in range(R)]))
-        for a in _inputs["clicks"]:
-            a.setflags(write=False)
-    return _inputs["clicks"]
-
-
-def targets(S):
-    """a different non-zero target per recording where there is more than one reference"""
-    return [1, 2] if S >= 3 else [0] * R
+    return recordings("click pairs", lambda r: REF.click_pairs(seed=r))
 
 
 def reference(key, refs, est, mix, tg, lag=None, D=0):
     """(sums [R, J, 3, 32, 4], bound [R, J, 3, 32, 4]) float64 of a batch; computed once per key"""
-    if key not in _refs:
-        out = [REF.recording_sums(refs[r], est[r], mix[r], tg[r], 0 if lag is None else lag[r], D) for r in range(R)]
-        _refs[key] = (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]))
-        for a in _refs[key]:
-            a.setflags(write=False)
-    return _refs[key]
-
-
-def _gpu(dev, *arrays):
-    return [torch.tensor(np.ascontiguousarray(a)).to(dev) for a in arrays]      # (a copy: the shared inputs are read-only)
-
-
-def _target(dev, tg):
-    return tg[0] if len(set(tg)) == 1 else torch.tensor(tg, dtype=torch.int64).to(dev)
-
-
-def _same(a, b):
-    """bit for bit, NaN in the same places"""
-    return a.shape == b.shape and bool(torch.equal(torch.nan_to_num(a, nan=12345.0), torch.nan_to_num(b, nan=12345.0))) and \
-        bool(torch.equal(torch.isnan(a), torch.isnan(b)))
+    return recordings(("spatial", key), lambda r: REF.recording_sums(refs[r], est[r], mix[r], tg[r], 0 if lag is None else lag[r], D))
 
 
 @pytest.mark.parametrize("S,L", [(S, L) for S in (1, 3) for L in (1, 5, 700, 15999, 16000, 16001, 40001)] + [(1, "clicks")])
@@ -282,11 +240,6 @@ def test_scenario_auralizer_separator_scorer(dev, scorer):
     M = out["plan"]["M"]
     assert tuple(out["spatial_whole"].shape) == (R, 9) and tuple(out["spatial_track"].shape) == (R, M, 9) and tuple(out["spatial_cues"].shape) == (R, M, 3, 32, 3)
     assert bool(torch.isfinite(out["spatial_whole"]).all()) and bool(torch.isfinite(out["spatial_track"]).all())
-
-
-def _write_wav(path, data):
-    from scipy.io import wavfile
-    wavfile.write(path, 16000, data)
 
 
 def test_cli_spatial_rows_and_json(dev, tmp_path):

@@ -13,15 +13,13 @@ import numpy as np
 import pytest
 import torch
 
-import score_ref
 import spectral_ref as REF
+from score_cases import LMAX, R, _gpu, _same, _target, _write_wav, batch, recordings, targets
 from m2h import _lib, ops
 from m2h.audio import score as SC
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-R = 2
-LMAX = 40001
 
 
 @pytest.fixture(scope="module")
@@ -39,54 +37,13 @@ def table(dev):
     return torch.from_numpy(SC.spectral_table()).to(dev)
 
 
-_inputs, _refs = {}, {}
-
-
-def batch(S, C, snr43=False):
-    """R recordings of score_ref.inputs at LMAX samples: refs [R, S, C, L], est [R, C, L], mix [R, 2, L]; made once, shared and read-only"""
-    key = (S, C, snr43)
-    if key not in _inputs:
-        _inputs[key] = tuple(np.stack(a) for a in zip(*[score_ref.inputs(S, LMAX, 31 + 50 * r, C, snr43) for r in range(R)]))
-        for a in _inputs[key]:
-            a.setflags(write=False)
-    return _inputs[key]
-
-
 def click_batch():
-    if "clicks" not in _inputs:
-        _inputs["clicks"] = tuple(np.stack(a) for a in zip(*[REF.clicks(seed=r) for r in range(R)]))
-        for a in _inputs["clicks"]:
-            a.setflags(write=False)
-    return _inputs["clicks"]
-
-
-def targets(S):
-    """a different non-zero target per recording where there is more than one reference"""
-    return [1, 2] if S >= 3 else [0] * R
+    return recordings("clicks", lambda r: REF.clicks(seed=r))
 
 
 def reference(key, refs, est, mix, tg, lag=None, D=0):
     """(sums [R, C, J, 7], bound [R, C, J, 7]) float64 of a batch; computed once per key"""
-    if key not in _refs:
-        out = [REF.recording_sums(refs[r], est[r], mix[r], tg[r], None if lag is None else lag[r], D) for r in range(R)]
-        _refs[key] = (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]))
-        for a in _refs[key]:
-            a.setflags(write=False)
-    return _refs[key]
-
-
-def _gpu(dev, *arrays):
-    return [torch.tensor(np.ascontiguousarray(a)).to(dev) for a in arrays]      # (a copy: the shared inputs are read-only)
-
-
-def _target(dev, tg):
-    return tg[0] if len(set(tg)) == 1 else torch.tensor(tg, dtype=torch.int64).to(dev)
-
-
-def _same(a, b):
-    """bit for bit, NaN in the same places"""
-    return a.shape == b.shape and bool(torch.equal(torch.nan_to_num(a, nan=12345.0), torch.nan_to_num(b, nan=12345.0))) and \
-        bool(torch.equal(torch.isnan(a), torch.isnan(b)))
+    return recordings(("spectral", key), lambda r: REF.recording_sums(refs[r], est[r], mix[r], tg[r], None if lag is None else lag[r], D))
 
 
 @pytest.mark.parametrize("C,S,L", [(C, S, L) for C, S in ((1, 1), (1, 3), (2, 1), (2, 3)) for L in (1, 5, 700, 15999, 16000, 16001, 40001)]
@@ -270,11 +227,6 @@ def test_argument_errors_launch_nothing(dev, scorer, table):
     assert lib.m2h_launch_count() == n0
     assert call() == 0 and call(lags=lag, D=24, nL=50) == 0 and lib.m2h_launch_count() == n0 + 2
     torch.cuda.synchronize()
-
-
-def _write_wav(path, data):
-    from scipy.io import wavfile
-    wavfile.write(path, 16000, data)
 
 
 def test_cli_spectral_rows_and_json(dev, tmp_path):

@@ -55,20 +55,10 @@ def test_float32_restatement_stays_within_the_bound(name):
     assert (bound[:, :, :2][big] <= 1e-3 * want[:, :, :2][big]).all()
 
 
-def _fold_on_the_table(x):
-    """one second x -> (re, im) float32 [T, F] the way m2h_score_spatial computes them (it is m2h_score_spectral's transform): raw frames,
-    x[n] +- x[1023 - n] in float32, a float32 product against the rows n = 0 .. 511 of spectral_table()"""
-    t = SC.spectral_table().reshape(32, 128, 2, 4, 16).transpose(2, 1, 3, 0, 4).reshape(2, 512, 512)   # [q, n = 4 ks + (l >> 4), k = 16 bt + (l & 15)]
-    xp = np.pad(np.asarray(x, np.float32), SR.PAD, mode="reflect")
-    fr = np.stack([xp[f * SR.HOP:f * SR.HOP + SR.NFFT + 1] for f in range(SR.T)])
-    lo, hi = fr[:, :512], fr[:, :511:-1]
-    return (lo + hi) @ t[0], (lo - hi) @ t[1]
-
-
 @pytest.mark.parametrize("name", [700, 16000, "clicks", "binaural"])
 def test_the_kernels_folded_arithmetic_stays_within_the_bound(name):
     want, bound = want_of(name)
-    got = REF.sums32([[_fold_on_the_table(SR.second(x, 0)) for x in pair] for pair in case(name)])
+    got = REF.sums32([[SR.fold_on_the_table(SR.second(x, 0), SC.spectral_table()) for x in pair] for pair in case(name)])
     w = REF.worst(got, want, bound)
     print("folded table, %s: worst error / bound %.3e" % (name, w))
     assert w <= 1.0

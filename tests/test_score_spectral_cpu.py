@@ -79,23 +79,11 @@ def test_the_bound_rejects_the_defect(defect):
     assert miss.max() >= 10.0
 
 
-def _fold_on_the_table(x):
-    """one second x -> (re, im) float32 [T, F] the way m2h_score_spectral computes them: raw frames, x[n] +- x[1023 - n] in float32, a
-    float32 product against the rows n = 0 .. 511 of spectral_table()"""
-    t = SC.spectral_table()                                                             # [bt, ks, q, l]
-    assert t.dtype == np.float32 and t.shape == (32, 128, 2, 64)
-    t = t.reshape(32, 128, 2, 4, 16).transpose(2, 1, 3, 0, 4).reshape(2, 512, 512)       # [q, n = 4 ks + (l >> 4), k = 16 bt + (l & 15)]
-    xp = np.pad(np.asarray(x, np.float32), REF.PAD, mode="reflect")
-    fr = np.stack([xp[f * REF.HOP:f * REF.HOP + REF.NFFT + 1] for f in range(REF.T)])   # (sample 1023 is the partner of n = 0, whose table row is 0)
-    lo, hi = fr[:, :512], fr[:, :511:-1]                                                # x[n] and x[1023 - n], n = 0 .. 511
-    return (lo + hi) @ t[0], (lo - hi) @ t[1]
-
-
 @pytest.mark.parametrize("name", [(16000, False), "clicks", "clicks700"])
 def test_the_folded_table_computes_the_definition(name):
     g, e, b = case(name)
     want, bound = REF.tile_sums(g, e, b, 0)
-    got = REF.seven32(*[_fold_on_the_table(REF.second(x, 0)) for x in (g, e, b)])
+    got = REF.seven32(*[REF.fold_on_the_table(REF.second(x, 0), SC.spectral_table()) for x in (g, e, b)])
     w = REF.worst(got, want, bound)
     print("folded table, %s: worst error / bound %.3e" % (name, w))
     assert w <= 1.0
