@@ -827,6 +827,41 @@ int m2h_score_spatial(const float* refs, long long refs_sr, long long refs_ss, l
                       const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0, const float* dft, double* out,
                       int R, int S, long long L, const int* lag, int D, m2h_stream stream);
 
+/* Scorer, STOI and ESTOI (m2h/audio/score.py, "STOI"; csrc/score_stoi.hip).
+ * m2h_stoi_resample: for (r, c) the three signals of m2h_score_spectral over the region [D, L - D) -- 0: the clean signal
+ * refs[r][target_r][c][D + t], 1: the estimate est[r][c][D + lag[r * C + c] + t], 2: the baseline mix[r][c][D + t] for C = 2,
+ * 0.5f * (mix[r][0] + mix[r][1])[D + t] for C = 1 (formed in fp32) -- converted from 16 kHz to 10 kHz:
+ *   out [R][C][3][L10] fp32, L10 = ceil((L - 2 D) * 5 / 8),
+ * by m2h_resample_poly's sum for up / down = 5 / 8 (half = 80, T = 33) with its k = 0 .. 32 fmaf chain and the region zero-extended, so
+ * the bits are m2h_resample_poly's on contiguous copies of the three rows.  G: that ratio's polyphase table [5][33] ON THE DEVICE.  refs,
+ * est, mix, the strides, target, target0, lag and D are m2h_score_spectral's; no read leaves [row start, row start + L).
+ * Returns a negative status and launches nothing for a null pointer (G included), S outside 1 .. 6, C outside {1, 2}, R < 1 or
+ * R > 32767, D outside 0 .. 8192 or not matching lag, L < 2 D + 1, a target0 outside [0, S) when target is NULL, an out that is not
+ * 4-byte aligned, or more than 2^31 - 1 workgroups of 256 outputs in a row. */
+int m2h_stoi_resample(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                      const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0, const float* G, float* out,
+                      int R, int S, int C, long long L, const int* lag, int D, m2h_stream stream);
+
+/* m2h_stoi_ranges: steps 1 .. 3 of the definition on every range of a table, for RC rows of three 10 kHz signals (clean, estimate,
+ * baseline): x10 [RC][3] rows of L10 samples, consecutive rows ld >= L10 elements apart (a slice of m2h_stoi_resample's output is read in
+ * place).  ranges [NR][3] 64-bit ON THE DEVICE: (start, end, slot): the samples [start, end) of every row, and the first of the range's
+ * frame slots; a range of n samples has ceil((n - 256) / 128) frames (0 for n <= 256) and owns that many consecutive slots; the slot
+ * offsets ascend and Ftot is the total.  Every value of the table is clamped where it is read (start and end into [0, L10], slots into
+ * [0, Ftot]): a wrong table gives wrong numbers, never an address outside a buffer.  window: hanning(258)[1:-1] as 256 floats;
+ * twiddles: m2h.audio.twiddles.packed_twiddles(512), [2][256][2] floats.  Outputs and work buffers, all ON THE DEVICE:
+ *   energy [RC][Ftot] fp64     |w x_f|^2 of every frame of the clean signal (256 fp32 products squared and added in fp64)
+ *   list   [RC][Ftot] int32    per range, from its first slot on: the indices of the kept frames, ascending
+ *   kept   [RC][NR][2] int32   K, the kept-frame count of the range, and 1 where the clean signal's largest frame energy is 0
+ *   env    [RC][3][15][Ftot] fp64   the third-octave envelopes of the K - 1 frames of the compacted signals, from the range's first slot on
+ *   dseg   [RC][4][Ftot] fp64  d_m of every segment: STOI and ESTOI of the estimate, then of the baseline
+ *   out    [RC][NR][6] fp64    stoi, estoi, stoi_base, estoi_base, stoii, estoii; NaN for K < 31 or a silent clean signal
+ * K never reaches the host: grids are sized for "every frame kept" and workgroups beyond K leave at once.  No atomics; every sum has a
+ * fixed order that depends on the range alone.  Slots that a range does not use are left unwritten.
+ * Returns a negative status and launches nothing for a null pointer, RC outside 1 .. 65535, NR < 1, L10 < 1, ld < L10, Ftot outside
+ * 1 .. 2^31 - 1 (more workgroups than a grid holds), an fp64 buffer or the table not 8-byte aligned, any other buffer not 4-byte aligned. */
+int m2h_stoi_ranges(const float* x10, long long ld, long long L10, const float* window, const float* twiddles, const long long* ranges, int NR,
+                    long long Ftot, int RC, double* energy, int* list, int* kept, double* env, double* dseg, double* out, m2h_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-network runner: one C call enqueues every kernel of one separator U-Net forward (K1/K2 slice, 5 down stages, 5 up
  * stages, head) = PassiveSepEncCNN.forward + PassiveSepDecCNN.forward (separator_cnn.py:70-108,153-170) in eval mode.  Same

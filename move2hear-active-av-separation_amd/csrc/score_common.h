@@ -33,6 +33,13 @@ __device__ __forceinline__ long long score_lag(const int* lag, long long rc, int
   return v < -D ? -D : (v > D ? D : v);
 }
 
+// The sum of a double over the 64 lanes of a wave, in every lane: the xor butterfly, a fixed order.
+__device__ __forceinline__ double wave_sum(double s) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return s;
+}
+
 // The entry points' argument checks.  Each returns 0 or, with the message set, the library's error code; `what` is the entry's name.
 // The signals, the output and the scored region [D, L - D) of every row: min_D <= D, and at least `least` samples beyond the 2 D.
 inline int check_signals(const char* what, const ScoreSignals& a, bool with_mix, const void* out, int R, int S, int C, long long L, int D, int min_D,

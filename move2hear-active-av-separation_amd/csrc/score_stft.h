@@ -111,13 +111,6 @@ __device__ __forceinline__ void stft_half(const float* smem, const float* dft, i
   }
 }
 
-// The sum of a double over the 64 lanes of a wave, in every lane: the xor butterfly, a fixed order.
-__device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
-
 // Host.  The checks the two entry points share, in their order; Ls = the scored samples per row, J = its tiles in each of `rows` rows.
 inline int check_stft(const char* what, const ScoreSignals& a, const long long* target, int target0, const float* dft, const double* out, int R, int S,
                       int C, long long L, const int* lag, int D, long long rows, long long& Ls, long long& J) {

@@ -131,6 +131,53 @@ m2h_score_spatial (csrc/score_spatial.hip) computes the tile sums straight from 
 fp32 matrix instruction, the four fp32 values of a bin converted to fp64 before they are multiplied, no frame or spectrum ever in
 memory.  No host synchronisation; the only copy from the host is the transform table, once.  Not done: a broadband ITD in microseconds
 (a GCC-PHAT peak).
+
+STOI.  score(..., stoi=True) adds the short-time objective intelligibility of the estimate (Taal et al. 2011) and its extended form
+ESTOI (Jensen & Taal 2016), with the mixture as baseline, per window and over the whole recording; every other number is unchanged by a
+bit.  It is the published algorithm with the conventions of the widely used Python package, quirks included.  The tile must be 16000
+(a tile is then exactly 10000 resampled samples): any other tile is a ValueError that names it, before any launch.
+
+Constants.  FS = 10000, N_FRAME = 256, HOP = 128, NFFT = 512; 15 third-octave bands; a segment is N = 30 frames; BETA = -15 dB, so the
+clip factor is 1 + 10^(15/20); dynamic range 40 dB; EPS = 2^-52; the window is w = hanning(258)[1:-1], 256 values.
+
+Signals.  Per (r, c) the three signals of "Spectral" for the same C, with the same align=D rule: the clean signal
+x = references[r, target_r, c], the estimate y, the baseline b (C = 1: 0.5 (mixture[r, 0] + mixture[r, 1]) formed in float32, C = 2:
+mixture[r, c]); the region is [D, L - D) and the estimate is read at ITS OWN EAR's whole-recording lag, clamped to [-D, D].  Each
+signal is converted to 10 kHz by this project's resampler (m2h.audio.resample: up / down = 5 / 8, the table of design(16000, 10000);
+scipy.signal.resample_poly(x, 5, 8, padtype="constant") to the resampler's accuracy); Lr = L - 2 D samples give L10 = ceil(Lr 5 / 8).
+
+Ranges.  The whole recording is the range [0, L10) of the 10 kHz signals; window m of score_plan / align_plan is the range
+[m hop 10000, min((m hop + window) 10000, L10)).  Every range is analysed on its own by the three steps below, so stoi_track[..., m, :]
+is, by construction, what the whole-recording analysis gives on that slice of the 10 kHz signals (stoi_plan() returns the ranges).
+
+Step 1, silent frames.  Frames start at i = 0, 128, ... < n - 256, n the range's length: the end is EXCLUSIVE, so when n - 256 is a
+multiple of 128 the last full frame is not taken.  The energy of frame f is e_f = 20 log10(|w x_f|_2 + EPS), from the clean signal only;
+frame f is kept iff e_f > max_f e_f - 40.  The K kept frames of x, y and b -- one mask for all three -- are windowed by w and
+overlap-added at hop 128: three signals of (K - 1) 128 + 256 samples.
+
+Step 2, envelopes.  These signals are framed again by the same exclusive rule, which gives K - 1 frames; each is windowed by w again and
+transformed at 512 points.  With f_k = k FS / 512 the band edges are the bins nearest to 150 2^((2 j -+ 1) / 6) Hz, j = 0 .. 14; the
+half-open bin ranges are [7,9) [9,11) [11,14) [14,17) [17,22) [22,27) [27,34) [34,43) [43,55) [55,69) [69,87) [87,109) [109,138)
+[138,174) [174,219), and the envelope is X[j, t] = sqrt(sum over the band's bins of |S|^2).
+
+Step 3, segments.  For every m = 30 .. K - 1 take the 15 x 30 blocks X (clean) and Y (processed), columns [m - 30, m).
+  STOI:  per band row alpha = |X_row| / (|Y_row| + EPS);  Y' = min(alpha Y, (1 + 10^0.75) X);  each row's mean is removed from X and from
+         Y';  each row is divided by (its norm + EPS);  d_m = sum X Y' / 15;  STOI is the mean of d_m over the segments.
+  ESTOI: X and Y are normalised by rows (mean removed, divided by norm + EPS), then by columns the same way;  d_m = sum X Y / 30;  ESTOI
+         is the mean of d_m over the segments.
+
+Choices where the package is arbitrary: a range with fewer than 30 envelope frames (K < 31) gives NaN (the package returns 1e-5 and
+warns), and so does a range whose clean signal has max_f |w x_f| = 0.
+
+Result.  STOI_ORDER = (stoi, estoi, stoi_base, estoi_base, stoii, estoii): base is the same with b as the processed signal, the
+improvements are estimate minus base.  "stoi_whole" [R, C, 6] and "stoi_track" [R, C, M, 6] float64, and "stoi_frames" [R, C, 1 + M]
+int64: the kept-frame count K of the whole recording, then of every window.  m2h_stoi_resample (csrc/score_stoi.hip) reads the
+three signals in place and writes them at 10 kHz with the resampler's own chain of operations (the same bits as Resampler(16000, 10000)
+on copies); m2h_stoi_ranges does steps 1 .. 3 for the whole recording and every window in the same five launches: frame energies in fp64
+from fp32 products, the mask and its scan, the envelopes (gather through the kept-frame list, overlap-add, the packed transform of
+fft_lds.h in LDS, band sums in fp64 -- no frame, no overlap-added signal and no spectrum in memory) and the segments in fp64.  K stays
+on the device: no host synchronisation, and no copy from the host apart from three small tables on a Scorer's first stoi call.  No
+atomics, fixed summation orders: a recording's bits do not depend on the batch around it, on strides or on alignment.
 """
 import operator
 
@@ -152,6 +199,9 @@ SPECTRAL_BINS, SPECTRAL_FRAMES, SPECTRAL_NFFT = 512, 32, 1023
 SPATIAL_ORDER = ("ild_err", "ipd_err", "ic_err", "ild_err_base", "ipd_err_base", "ic_err_base", "ild_erri", "ipd_erri", "ic_erri")
 SPATIAL_BANDS = 32           # spatial=True: bands of 16 bins, band j = bins 16 j .. 16 j + 15
 SPATIAL_IPD_BANDS = 6        # the phase error is taken over the bands 0 .. 5: bins below 96, about 1.5 kHz
+STOI_ORDER = ("stoi", "estoi", "stoi_base", "estoi_base", "stoii", "estoii")
+STOI_TILE = 16000            # stoi=True: a tile is exactly STOI_FS resampled samples
+STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT, STOI_BANDS, STOI_SEGMENT = 10000, 256, 128, 512, 15, 30
 
 
 def score_plan(L, tile=DEFAULT_TILE, window=1, hop=1):
@@ -195,6 +245,32 @@ def align_plan(L, D, tile=DEFAULT_TILE, window=1, hop=1):
     plan["offset"] = d
     plan["samples"] = [(t0 + d, t1 + d) for t0, t1 in plan["samples"]]
     return plan
+
+
+def stoi_frames(n):
+    """the frames of a range of n samples at 10 kHz: starts 0, 128, ... < n - 256 (the end is exclusive)"""
+    return max(0, -(-(n - STOI_FRAME) // STOI_HOP))
+
+
+def stoi_plan(plan):
+    """Pure Python: the ranges of stoi=True for a score_plan / align_plan with tile = 16000 (module docstring, "STOI").
+
+    -> {"L10", "ranges": [(start, end)] at 10 kHz, the whole recording first and then the plan's M windows, "slots": the first frame slot of
+    every range in m2h_stoi_ranges' work buffers (a window owns "per_window" of them), "total": their count (at least 1)}."""
+    if plan["tile"] != STOI_TILE:
+        raise ValueError("m2h.Scorer: stoi=True needs tile = %d (one second), got %d" % (STOI_TILE, plan["tile"]))
+    L10 = -(-plan["L"] * 5 // 8)
+    ranges = [(0, L10)] + [(min(m * plan["hop"] * STOI_FS, L10), min((m * plan["hop"] + plan["window"]) * STOI_FS, L10)) for m in range(plan["M"])]
+    per_window = stoi_frames(min(plan["window"] * STOI_FS, L10))
+    slots = [0] + [stoi_frames(L10) + m * per_window for m in range(plan["M"])]
+    return {"L10": L10, "ranges": ranges, "slots": slots, "per_window": per_window,
+            "total": max(1, stoi_frames(L10) + plan["M"] * per_window)}
+
+
+def stoi_window():
+    """w = hanning(258)[1:-1] rounded to float32, numpy [256]"""
+    import numpy as np
+    return np.hanning(STOI_FRAME + 2)[1:-1].astype(np.float32)
 
 
 def lags_from_corr(c):
@@ -448,6 +524,7 @@ class Scorer:
         self.max_corr_bytes = int(max_corr_bytes)   # align: recordings are processed in groups whose tile correlations stay under this
         self._twiddles = None
         self._dft = None
+        self._stoi = None
         self._timing = None          # tools/score_bench.py: a list that receives (stage, event) marks
 
     def _twiddle_table(self):
@@ -462,13 +539,38 @@ class Scorer:
             self._dft = torch.from_numpy(spectral_table()).to(self.device)
         return self._dft
 
+    def _stoi_tables(self):
+        """(the 16 kHz -> 10 kHz polyphase table [5, 33], the window [256], the 512-point transform's twiddles) on the device, copied from the
+        host once"""
+        if self._stoi is None:
+            from .resample import design, polyphase_table
+            from .twiddles import device_twiddles as tw
+            import numpy as np
+            up, _, _, taps = design(STOI_TILE, STOI_FS)
+            self._stoi = (torch.from_numpy(polyphase_table(taps.astype(np.float32), up)).to(self.device), torch.from_numpy(stoi_window()).to(self.device),
+                          tw(self.device, STOI_NFFT))
+        return self._stoi
+
+    def _stoi_ranges(self, plan, sp):
+        """m2h_stoi_ranges' table [1 + M, 3] int64 of stoi_plan's ranges, built on the device: fills and aranges, no copy from the host"""
+        dev, M, L10 = self.device, plan["M"], sp["L10"]
+        m = torch.arange(M, device=dev, dtype=torch.int64)
+        table = torch.empty((1 + M, 3), dtype=torch.int64, device=dev)
+        table[0, 0].fill_(0)
+        table[0, 1].fill_(L10)
+        table[0, 2].fill_(0)
+        table[1:, 0] = torch.clamp(m * (plan["hop"] * STOI_FS), max=L10)
+        table[1:, 1] = torch.clamp((m * plan["hop"] + plan["window"]) * STOI_FS, max=L10)
+        table[1:, 2] = sp["slots"][1] + m * sp["per_window"]
+        return table
+
     def _mark(self, stage):
         if self._timing is not None:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record(torch.cuda.current_stream(self.device))
             self._timing.append((stage, ev))
 
-    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spectral=False, spatial=False):
+    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spectral=False, spatial=False, stoi=False):
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("m2h.Scorer: %s must be a torch tensor, got %s" % (name, type(t).__name__))
@@ -522,7 +624,7 @@ class Scorer:
         plan = score_plan(L, tile, window, hop) if align is None else align_plan(L, align, tile, window, hop)      # raises on tile, window, hop, align
         if spatial and C != 2:
             raise ValueError("m2h.Scorer: spatial=True compares the two ears and needs C = 2 channels, got C = %d" % C)
-        for name, on in (("spatial", spatial), ("spectral", spectral)):
+        for name, on in (("spatial", spatial), ("spectral", spectral), ("stoi", stoi)):
             if on and plan["tile"] != SPECTRAL_TILE:
                 raise ValueError("m2h.Scorer: %s=True needs tile = %d (one second), got %d" % (name, SPECTRAL_TILE, plan["tile"]))
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
@@ -530,15 +632,18 @@ class Scorer:
                 raise ValueError("m2h.Scorer: %s must live on %s, got %s; the scorer has no CPU path" % (name, self.device, t.device))
         return refs, est, target, plan
 
-    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None, spectral=False, spatial=False):
+    def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None, spectral=False, spatial=False,
+              stoi=False):
         """-> {"whole": [R, C, 11], "track": [R, C, M, 11], "active": [R, C, M] bool, "plan": score_plan(...)}; float64 on the device, in
         eval_metrics.METRIC_ORDER; no host synchronisation.  With align=D (an int, the largest lag searched in samples) the estimate is
         aligned to its target first: also "lag": [R, C] int32 and "lag_track": [R, C, M] int32 on the device, and "plan" is
         align_plan(...).  With spectral=True (tile must be 16000) also "spectral_whole": [R, C, 8] and "spectral_track": [R, C, M, 8],
         float64 in SPECTRAL_ORDER.  With spatial=True (two channels, tile must be 16000) also "spatial_whole": [R, 9] and
         "spatial_track": [R, M, 9], float64 in SPATIAL_ORDER, and the cues themselves, "spatial_cues": [R, M, 3, 32, 3] (signal target /
-        estimate / mixture, band, ILD / IPD / IC).  The module docstring holds the definition."""
-        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial)
+        estimate / mixture, band, ILD / IPD / IC).  With stoi=True (tile must be 16000) also "stoi_whole": [R, C, 6] and "stoi_track":
+        [R, C, M, 6], float64 in STOI_ORDER, and "stoi_frames": [R, C, 1 + M] int64, the kept-frame count of the whole recording and of
+        every window.  The module docstring holds the definition."""
+        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial, stoi)
         R, S, C, L = refs.shape
         J, M, tile, window, hop = (plan[k] for k in ("J", "M", "tile", "window", "hop"))
         D = plan.get("offset", 0)
@@ -594,6 +699,14 @@ class Scorer:
                 spat, cues = spatial_from_sums(sums.view(R, 1 + M, 3, SPATIAL_BANDS, 4))
                 out.update({"spatial_whole": spat[:, 0], "spatial_track": spat[:, 1:], "spatial_cues": cues[:, 1:]})
                 self._mark("spatial_metrics")
+            if stoi:
+                table, win, tw = self._stoi_tables()
+                sp = stoi_plan(plan)
+                x10 = ops.stoi_resample(refs, est, mixture, target, table, out.get("lag"), D)                            # [R, C, 3, L10]
+                self._mark("stoi_resample")
+                st = ops.stoi_ranges(x10, self._stoi_ranges(plan, sp), sp["total"], win, tw)
+                out.update({"stoi_whole": st["out"][:, :, 0], "stoi_track": st["out"][:, :, 1:], "stoi_frames": st["kept"][..., 0].to(torch.int64)})
+                self._mark("stoi_ranges")
         out.update({"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan})
         return out
 
@@ -601,7 +714,9 @@ class Scorer:
 def summarize(result):
     """Host-side summary of Scorer.score's result for one call: {"metrics", "whole": [R][C][11], "track_mean", "track_median": over the
     active windows ([R][C][11], NaN without any), "active_windows": [R][C]} as Python lists (one synchronisation); with spectral=True /
-    spatial=True results also the "spectral_*" / "spatial_*" keys (spatial: [R][9], over the windows in which both ears are active)."""
+    spatial=True results also the "spectral_*" / "spatial_*" keys (spatial: [R][9], over the windows in which both ears are active); with
+    stoi=True results also "stoi_metrics", "stoi_whole" [R][C][6], "stoi_track_mean" / "stoi_track_median" over the windows that are not NaN
+    and "stoi_frames" [R][C][1 + M]."""
     import numpy as np
     whole, track, active = (result[k].cpu().numpy() for k in ("whole", "track", "active"))
     R, C = whole.shape[:2]
@@ -635,4 +750,15 @@ def summarize(result):
                     pmean[r], pmedian[r] = rows.mean(axis=0), np.median(rows, axis=0)
         out.update({"spatial_metrics": list(SPATIAL_ORDER), "spatial_whole": pw.tolist(), "spatial_track_mean": pmean.tolist(),
                     "spatial_track_median": pmedian.tolist()})
+    if "stoi_whole" in result:                                                         # score(..., stoi=True): over the windows that are not NaN
+        tw, tt = result["stoi_whole"].cpu().numpy(), result["stoi_track"].cpu().numpy()
+        tmean, tmedian = np.full((R, C, 6), np.nan), np.full((R, C, 6), np.nan)
+        with np.errstate(all="ignore"):
+            for r in range(R):
+                for c in range(C):
+                    rows = tt[r, c][~np.isnan(tt[r, c]).any(axis=-1)]
+                    if rows.shape[0]:
+                        tmean[r, c], tmedian[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
+        out.update({"stoi_metrics": list(STOI_ORDER), "stoi_whole": tw.tolist(), "stoi_track_mean": tmean.tolist(), "stoi_track_median": tmedian.tolist(),
+                    "stoi_frames": result["stoi_frames"].cpu().tolist()})
     return out

@@ -839,6 +839,62 @@ def score_spatial(refs, est, mix, target, dft, lag=None, D=0):
     return out
 
 
+STOI_TABLE_SHAPE = (5, 33)                   # the polyphase table of 16 kHz -> 10 kHz (m2h.audio.resample)
+
+
+def stoi_resample(refs, est, mix, target, table, lag=None, D=0):
+    """The Scorer's three signals at 10 kHz (m2h/audio/score.py, "STOI"): refs [R, S, C, L], est [R, C, L], mix [R, 2, L] fp32 with unit
+    last stride (views are read in place); target, lag and D as for score_spectral; table: Resampler(16000, 10000).table, [5, 33] on the
+    device -> [R, C, 3, L10] fp32 (clean, estimate, baseline), L10 = ceil((L - 2 D) * 5 / 8): bit for bit Resampler(16000, 10000) on
+    contiguous copies of the three rows (include/m2h.h)."""
+    R, S, C, L = _score_signals("stoi_resample", refs, est, mix)
+    D = int(D)
+    if not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
+        raise RuntimeError("m2h.stoi_resample: D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required" % (D, L))
+    _chk(table, "stoi_resample(table)")
+    if tuple(table.shape) != STOI_TABLE_SHAPE or table.device != refs.device:
+        raise RuntimeError("m2h.stoi_resample: table must be the %s table on %s" % (list(STOI_TABLE_SHAPE), refs.device))
+    lptr = None if lag is None else _score_lag("stoi_resample", lag, refs)
+    tptr, t0 = _score_target("stoi_resample", target, refs)
+    out = torch.empty((R, C, 3, -(-(L - 2 * D) * 5 // 8)), device=refs.device, dtype=torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_stoi_resample(*_score_args(refs, est, mix), tptr, t0, _ptr(table), _ptr(out), R, S, C, L, lptr, D, _stream(refs)),
+                   "m2h_stoi_resample")
+    return out
+
+
+def stoi_ranges(x10, ranges, slots, window, twiddles):
+    """Steps 1 .. 3 of STOI / ESTOI on every range of a table (m2h/audio/score.py, "STOI"; include/m2h.h): x10 [R, C, 3, n] fp32, rows of
+    unit stride a constant distance apart (stoi_resample's output or a slice of its last axis, read in place); ranges [NR, 3] int64 on
+    the device: (start, end, first frame slot); slots: the total of frame slots, a Python int; window [256] fp32 and twiddles [2, 256, 2]
+    fp32 on the device -> {"out": [R, C, NR, 6] fp64, "kept": [R, C, NR, 2] int32 (K, silent), "list": [R, C, slots] int32,
+    "env": [R, C, 3, 15, slots] fp64, "energy": [R, C, slots] fp64}.  Slots that a range does not use are left unwritten."""
+    _chk(window, "stoi_ranges(window)")
+    _chk(twiddles, "stoi_ranges(twiddles)")
+    _chk(ranges, "stoi_ranges(ranges)", torch.int64)
+    if not x10.is_cuda or x10.dtype != torch.float32 or x10.dim() != 4 or x10.shape[2] != 3 or x10.shape[3] < 1:
+        raise RuntimeError("m2h.stoi_ranges: x10 must be float32 [R, C, 3, n] on the GPU; the m2h ops have no CPU path")
+    R, C, _, n = x10.shape
+    ld = x10.stride(2)
+    if (n > 1 and x10.stride(3) != 1) or ld < n or (C > 1 and x10.stride(1) != 3 * ld) or (R > 1 and x10.stride(0) != 3 * C * ld):
+        raise RuntimeError("m2h.stoi_ranges: the rows of x10 must have unit stride and lie a constant distance apart (strides %s)" % (tuple(x10.stride()),))
+    slots = int(slots)
+    if ranges.dim() != 2 or ranges.shape[1] != 3 or ranges.shape[0] < 1 or slots < 1 or tuple(window.shape) != (256,) or tuple(twiddles.shape) != (2, 256, 2) \
+            or any(t.device != x10.device for t in (ranges, window, twiddles)):
+        raise RuntimeError("m2h.stoi_ranges: ranges [NR, 3] int64, slots >= 1, window [256] and twiddles [2, 256, 2] on %s are required" % (x10.device,))
+    NR, dev = ranges.shape[0], x10.device
+    res = {"out": torch.empty((R, C, NR, 6), device=dev, dtype=torch.float64), "kept": torch.empty((R, C, NR, 2), device=dev, dtype=torch.int32),
+           "list": torch.empty((R, C, slots), device=dev, dtype=torch.int32), "env": torch.empty((R, C, 3, 15, slots), device=dev, dtype=torch.float64),
+           "energy": torch.empty((R, C, slots), device=dev, dtype=torch.float64)}
+    dseg = torch.empty((R, C, 4, slots), device=dev, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.m2h_stoi_ranges(_ptr(x10), ld, n, _ptr(window), _ptr(twiddles), _ptr(ranges), NR, slots, R * C, _ptr(res["energy"]), _ptr(res["list"]),
+                                       _ptr(res["kept"]), _ptr(res["env"]), _ptr(dseg), _ptr(res["out"]), _stream(x10)), "m2h_stoi_ranges")
+    return res
+
+
 def score_windows(tiles, M, window, hop):
     """tiles [R, C, J, K] fp64 -> [R, C, M, K]: every window's tiles added in tile order (window m: tiles m * hop .. m * hop + window - 1)."""
     _chk(tiles, "score_windows", torch.float64)

@@ -2,7 +2,7 @@
 """Score a separated recording of any length against its ground truth:
 
     python score.py --estimate out.wav --mixture mix.wav --reference target.wav [--reference other.wav ...] [--window W --hop H]
-                    [--align D] [--spectral] [--spatial] [--json scores.json]
+                    [--align D] [--spectral] [--spatial] [--stoi] [--json scores.json]
 
 ``--reference``: the sources as they are in the mixture, at most six; the FIRST one is the target the estimate is scored against, the
 others are the interferers (they enter SI-SIR and SI-SAR).  ``render.py --out-target / --out-image`` writes such files.  ``--mixture``:
@@ -30,6 +30,11 @@ target's, per window and over the whole recording, the same for the mixture as t
 (m2h/audio/score.py, "Spatial"), as rows under the table and as ``spatial_*`` keys in the JSON; the JSON also holds the cues
 themselves per window, signal (target, estimate, mixture) and 250 Hz band (``spatial_cues``).  With ``--align`` both ears of the
 estimate are read at the left ear's lag.
+
+``--stoi`` adds the intelligibility figures STOI and ESTOI of the estimate against the clean target (m2h/audio/score.py, "STOI"), the
+same for the mixture as the estimate, and the two improvements, for the same whole recording and the same windows, as rows under the
+table and as ``stoi_*`` keys in the JSON (``stoi_frames``: the frames kept after silent-frame removal, whole recording first).  A window
+with fewer than 31 kept frames has no STOI (NaN) and is left out of the mean and the median.
 """
 import argparse
 import json
@@ -65,6 +70,7 @@ def main():
     parser.add_argument("--align", type=int, default=None, metavar="D", help="align the estimate to the target first: the largest lag searched, in samples (1 .. 8192)")
     parser.add_argument("--spectral", action="store_true", help="also the STFT distance per window and over the whole recording")
     parser.add_argument("--spatial", action="store_true", help="also the interaural cue errors (ILD, IPD, IC) per window and over the whole recording; two-channel files")
+    parser.add_argument("--stoi", action="store_true", help="also STOI and ESTOI per window and over the whole recording")
     parser.add_argument("--json", default=None, help="write every number here")
     args = parser.parse_args()
     import numpy as np
@@ -90,7 +96,7 @@ def main():
     try:
         res = Scorer(dev).score(torch.from_numpy(np.ascontiguousarray(est)).to(dev)[None], torch.from_numpy(np.stack(refs)).to(dev)[None],
                                 torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop, align=args.align,
-                                spectral=args.spectral, **({"spatial": True} if args.spatial else {}))
+                                spectral=args.spectral, **({"spatial": True} if args.spatial else {}), **({"stoi": True} if args.stoi else {}))
     except (ValueError, TypeError) as e:
         raise SystemExit("score.py: %s" % e)
     s = summarize(res)
@@ -119,6 +125,11 @@ def main():
         print("%-8s %-23s" % ("spatial", "") + " ".join("%20s" % m for m in s["spatial_metrics"]))
         for label, key in (("spatial whole", "spatial_whole"), ("spatial window mean", "spatial_track_mean"), ("spatial window median", "spatial_track_median")):
             print("%-8s %-23s" % ("binaural", label) + " ".join("%20.12e" % v for v in s[key][0]))
+    if args.stoi:
+        print("%-8s %-23s" % ("stoi", "") + " ".join("%20s" % m for m in s["stoi_metrics"]))
+        for c in range(C):
+            for label, key in (("stoi whole", "stoi_whole"), ("stoi window mean", "stoi_track_mean"), ("stoi window median", "stoi_track_median")):
+                print("%-8s %-23s" % (names[c], label) + " ".join("%20.12e" % v for v in s[key][0][c]))
     if args.json is not None:
         out = {"estimate": args.estimate, "mixture": args.mixture, "references": args.reference, "sample_rate": separate.SAMPLE_RATE,
                "samples": L, "channels": list(names), "window_s": args.window, "hop_s": args.hop, "metrics": s["metrics"],
@@ -133,6 +144,9 @@ def main():
             out.update({"spatial_metrics": s["spatial_metrics"], "spatial_whole": s["spatial_whole"][0],
                         "spatial_track": res["spatial_track"][0].cpu().numpy().tolist(), "spatial_track_mean": s["spatial_track_mean"][0],
                         "spatial_track_median": s["spatial_track_median"][0], "spatial_cues": res["spatial_cues"][0].cpu().numpy().tolist()})
+        if args.stoi:
+            out.update({"stoi_metrics": s["stoi_metrics"], "stoi_whole": s["stoi_whole"][0], "stoi_track": res["stoi_track"][0].cpu().numpy().tolist(),
+                        "stoi_track_mean": s["stoi_track_mean"][0], "stoi_track_median": s["stoi_track_median"][0], "stoi_frames": s["stoi_frames"][0]})
         if args.align is not None:
             out.update({"align": args.align, "region": [t0, t1], "lag": lag, "lag_track": res["lag_track"][0].cpu().tolist()})
         with open(args.json, "w") as f:

@@ -9,6 +9,8 @@
     python tools/score_bench.py --case 16x3x600c1 --spectral         # one case of it in this process
     python tools/score_bench.py --spatial --out profiles/score_spatial_bench.json                   # the interaural cues, the two-channel cases
     python tools/score_bench.py --case 16x3x600c2 --spatial          # one case of it in this process
+    python tools/score_bench.py --stoi --out profiles/score_stoi_bench.json                         # STOI / ESTOI, every case
+    python tools/score_bench.py --case 1x2x60c2 --stoi               # one case of it in this process
 
 Cases (R recordings x S sources x seconds, C channels): 16x3x600 and 1x2x60, each with C = 1 and C = 2; per-second windows.  Timing: HIP
 events on the stream around the Gram launch and around everything after it (Scorer._timing), summed over the repetitions.
@@ -45,6 +47,13 @@ only: the cues compare the ears, a mono case has none):
                           spectra stored) and torch float64 reductions, before and after; its largest difference from the kernel's sums,
                           relative to the band's energies sqrt(PL PR) (a cross term may be near 0), is recorded
   extra_ms_in_score       what spatial=True adds to one Scorer.score (launch, two m2h_score_windows, spatial_from_sums)
+With --stoi (Scorer.score(..., stoi=True): the whole recording and every one-second window are ranges of the same launches):
+  resample_ms, ranges_ms  m2h_stoi_resample and the five launches of m2h_stoi_ranges, each timed alone with HIP events, twice
+  bytes                   what each stage has to move at least (every sample, frame slot and envelope counted once), from the shapes
+  torch_stoi_ms           the yardstick in the same run, before and after: the same definition composed on the GPU from Resampler, unfold,
+                          boolean-mask compaction (one host synchronisation per range), torch.fft.rfft and float64 tensor algebra, one
+                          recording at a time; the largest difference of its six numbers from the kernels' is recorded
+  extra_ms_in_score       what stoi=True adds to one Scorer.score
 No threshold is set anywhere: the file reports what came out.  Every GPU step runs under its own timeout and the driver stops at the
 first failure.
 """
@@ -305,6 +314,121 @@ def run_spatial_case(case):
     return res
 
 
+def torch_stoi(rs, win, x, y, b, ranges):
+    """[C, len(ranges), 6] float64: STOI / ESTOI (m2h/audio/score.py, "STOI") of one recording composed from torch on the GPU.  x, y, b
+    [C, L] at 16 kHz; ranges at 10 kHz.  The boolean mask costs one host synchronisation per range."""
+    import torch
+    dev, eps, clip = x.device, 2.0 ** -52, 1.0 + 10.0 ** 0.75
+    edges = (7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219)
+    bands = torch.zeros((257, 15), dtype=torch.float64, device=dev)
+    for j in range(15):
+        bands[edges[j]:edges[j + 1], j] = 1.0
+    nan6 = torch.full((6,), float("nan"), dtype=torch.float64, device=dev)
+
+    def normalise(a, dim):
+        a = a - a.mean(dim=dim, keepdim=True)
+        return a / (a.norm(dim=dim, keepdim=True) + eps)
+
+    def pair(X, Y):                                                                     # [15, nseg, 30] each
+        alpha = X.norm(dim=-1, keepdim=True) / (Y.norm(dim=-1, keepdim=True) + eps)
+        d = (normalise(X, -1) * normalise(torch.minimum(alpha * Y, clip * X), -1)).sum(dim=(0, 2)) / 15.0
+        de = (normalise(normalise(X, -1), 0) * normalise(normalise(Y, -1), 0)).sum(dim=(0, 2)) / 30.0
+        return d.mean(), de.mean()
+
+    out = []
+    x10 = rs(torch.stack([x, y, b], dim=1).contiguous())                                # [C, 3, L10]
+    for c in range(x.shape[0]):
+        row = []
+        for s, e in ranges:
+            nf = max(0, -(-(e - s - 256) // 128))
+            if nf < 31:
+                row.append(nan6)
+                continue
+            fw = x10[c, :, s:e].unfold(-1, 256, 128)[:, :nf] * win                       # [3, nf, 256]
+            en = 20.0 * torch.log10(fw[0].double().norm(dim=-1) + eps)
+            kept = fw[:, en > en.max() - 40.0]                                           # (synchronises)
+            K = kept.shape[1]
+            if K < 31:
+                row.append(nan6)
+                continue
+            ola = torch.zeros((3, (K + 1) * 128), device=dev)
+            ola[:, :K * 128] += kept[..., :128].reshape(3, K * 128)
+            ola[:, 128:] += kept[..., 128:].reshape(3, K * 128)
+            spec = torch.fft.rfft(ola.unfold(-1, 256, 128)[:, :K - 1] * win, 512)       # [3, K - 1, 257]
+            env = torch.sqrt((spec.real.double() ** 2 + spec.imag.double() ** 2) @ bands).transpose(1, 2)      # [3, 15, K - 1]
+            seg = env.unfold(-1, 30, 1)                                                 # [3, 15, K - 30, 30]
+            (d1, e1), (d2, e2) = pair(seg[0], seg[1]), pair(seg[0], seg[2])
+            row.append(torch.stack([d1, e1, d2, e2, d1 - d2, e1 - e2]))
+        out.append(torch.stack(row))
+    return torch.stack(out)
+
+
+def run_stoi_case(case):
+    import torch
+    from m2h import ops
+    from m2h.audio import score as SC
+    from m2h.audio.resample import Resampler
+    if not torch.cuda.is_available():
+        raise SystemExit("score_bench: no GPU; this measurement has no CPU path")
+    R, S, seconds, C, reps = CASES[case]
+    reps = max(1, reps // 5)
+    dev = torch.device("cuda", 0)
+    L = seconds * SEG
+    g = torch.Generator(device=dev).manual_seed(7)
+    refs = torch.randn((R, S, C, L), device=dev, generator=g) * 0.1 + 0.01
+    mix = torch.stack([refs[:, :, 0].mean(1), refs[:, :, C - 1].mean(1)], dim=1) + 0.02 * torch.randn((R, 2, L), device=dev, generator=g)
+    est = 0.8 * refs[:, 0] + 0.03 * torch.randn((R, C, L), device=dev, generator=g)
+    sc, rs = SC.Scorer(dev), Resampler(16000, 10000, dev)
+    table, win, tw = sc._stoi_tables()
+    plan = SC.score_plan(L)
+    sp = SC.stoi_plan(plan)
+    base = mix if C == 2 else 0.5 * (mix[:, :1] + mix[:, 1:])
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    rtab = sc._stoi_ranges(plan, sp)
+    resample = lambda: ops.stoi_resample(refs, est, mix, 0, table)                      # noqa: E731
+    x10 = resample()
+    ranges = lambda: ops.stoi_ranges(x10, rtab, sp["total"], win, tw)                   # noqa: E731
+    yard = lambda: torch.stack([torch_stoi(rs, win, refs[r, 0], est[r], base[r], sp["ranges"]) for r in range(R)])   # noqa: E731
+    res0 = sc.score(est, refs, mix, stoi=True)                                          # warm-up of every shape
+    got = torch.cat([res0["stoi_whole"][:, :, None], res0["stoi_track"]], dim=2)
+    want = yard()
+    diff = float(torch.nan_to_num((got - want).abs(), nan=0.0).max())
+    same_nan = bool(torch.equal(torch.isnan(got), torch.isnan(want)))
+    del want
+    torch.cuda.synchronize()
+    before = timed(yard, 1)
+    t_res, t_rng = timed(resample, reps), timed(ranges, reps)
+    plain = timed(lambda: sc.score(est, refs, mix), reps)
+    full = timed(lambda: sc.score(est, refs, mix, stoi=True), reps)
+    after = timed(yard, 1)
+    t_res2, t_rng2 = timed(resample, reps), timed(ranges, reps)
+    RC, L10, slots = R * C, sp["L10"], sp["total"]
+    frames = sum(SC.stoi_frames(e - s) for s, e in sp["ranges"])
+    samples = sum(e - s for s, e in sp["ranges"])
+    nbytes = {"resample": RC * ((3 if C == 2 else 4) * L * 4 + 3 * L10 * 4), "energy": RC * (samples * 4 + frames * 8), "mask": RC * frames * (8 + 4),
+              "envelope": RC * (3 * samples * 4 + frames * 4 + 45 * frames * 8), "segments": RC * frames * (45 * 8 + 4 * 8), "mean": RC * frames * 4 * 8}
+    kernel = 0.5 * (t_res + t_res2 + t_rng + t_rng2)
+    res = {"case": case, "stoi": True, "R": R, "S": S, "C": C, "audio_seconds_per_recording": seconds, "reps": reps, "ranges": len(sp["ranges"]),
+           "frame_slots": slots, "frames": frames, "resample_ms": [t_res, t_res2], "ranges_ms": [t_rng, t_rng2], "bytes": nbytes,
+           "resample_bytes_per_s": nbytes["resample"] / (min(t_res, t_res2) * 1e-3), "torch_stoi_ms": [before, after], "torch_stoi_reps": 1,
+           "torch_stoi_host_synchronisations": RC * len(sp["ranges"]), "torch_over_kernels": 0.5 * (before + after) / kernel, "score_ms": plain,
+           "score_stoi_ms": full, "extra_ms_in_score": full - plain, "audio_s_per_s": R * seconds / (full * 1e-3),
+           "kernels_vs_torch_max_abs": diff, "nan_in_the_same_places": same_nan, "stoi_whole": float(res0["stoi_whole"][0, 0, 0]),
+           "estoi_whole": float(res0["stoi_whole"][0, 0, 1]), "kept_frames_whole": int(res0["stoi_frames"][0, 0, 0])}
+    print(json.dumps(res))
+    return res
+
+
 def run_align_case(case, D):
     import torch
     from m2h.audio.score import Scorer, lags_from_corr
@@ -383,13 +507,16 @@ def main():
     ap.add_argument("--align", type=int, action="append", default=None, metavar="D", help="measure the aligned scorer at this largest lag (repeat)")
     ap.add_argument("--spectral", action="store_true", help="measure the STFT distance's launch (Scorer.score(..., spectral=True))")
     ap.add_argument("--spatial", action="store_true", help="measure the interaural cues' launch (Scorer.score(..., spatial=True)); two-channel cases")
+    ap.add_argument("--stoi", action="store_true", help="measure STOI / ESTOI (Scorer.score(..., stoi=True)) against its composition from torch")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=120, help="driver mode: seconds per case")
     args = ap.parse_args()
-    if (args.spectral or args.spatial) and args.align or args.spectral and args.spatial:
-        raise SystemExit("score_bench: --spectral, --spatial and --align are measured separately")
+    if (args.spectral or args.spatial or args.stoi) and args.align or args.spectral + args.spatial + args.stoi > 1:
+        raise SystemExit("score_bench: --spectral, --spatial, --stoi and --align are measured separately")
     if args.case is not None:
-        if args.spatial:
+        if args.stoi:
+            run_stoi_case(args.case)
+        elif args.spatial:
             run_spatial_case(args.case)
         elif args.spectral:
             run_spectral_case(args.case)
@@ -402,7 +529,7 @@ def main():
     results = []
     for case, D in [(case, D) for D in (args.align or [None]) for case in ORDER if CASES[case][3] == 2 or not args.spatial]:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case] + ([] if D is None else ["--align", str(D)]) + \
-            (["--spectral"] if args.spectral else []) + (["--spatial"] if args.spatial else [])
+            (["--spectral"] if args.spectral else []) + (["--spatial"] if args.spatial else []) + (["--stoi"] if args.stoi else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             print(r.stdout[-4000:])
