@@ -862,6 +862,31 @@ int m2h_stoi_resample(const float* refs, long long refs_sr, long long refs_ss, l
 int m2h_stoi_ranges(const float* x10, long long ld, long long L10, const float* window, const float* twiddles, const long long* ranges, int NR,
                     long long Ftot, int RC, double* energy, int* list, int* kept, double* env, double* dseg, double* out, m2h_stream stream);
 
+/* Scorer, BSS-eval SDR / SIR / SAR through a distortion filter of T taps (m2h/audio/score.py, "BSS"; csrc/score_bss.hip).  refs, est,
+ * mix, the strides, lag and D are m2h_score_spectral's; tiles are `tile` samples of the region [D, L - D), Lr = L - 2 D samples,
+ * J = ceil(Lr / tile).  Per (r, c) the signals, taken raw, are v_0 .. v_{S-1} = refs[r][s][c][D + t], v_S = est[r][c][D + lag[r * C + c] + t]
+ * and v_{S+1} = the baseline (mix[r][c][D + t] for C = 2, 0.5f * (mix[r][0] + mix[r][1])[D + t] formed in fp32 for C = 1), every one zero
+ * outside the region: no read leaves [row start, row start + L), and no sample outside the region is used.
+ * m2h_bss_corr: the one-sided lagged correlations of every tile,
+ *   out [R][C][J][S][S + 2][T] fp64:  out[r][c][j][i][k][d] = sum over t in tile j of v_i[t] * v_k[t + d],   d = 0 .. T - 1.
+ * m2h_bss_project: h [R][C][2][S + 1][T] fp64 ON THE DEVICE holds, for the right-hand sides 0 (estimate) and 1 (baseline), the joint
+ * filters h_0 .. h_{S-1} and in slot S the filter g of the target alone.  With s_t[n] = sum_a g[a] v_j[n - a], j the target, and
+ * P[n] = sum_i sum_a h_i[a] v_i[n - a] (i ascending, then a ascending), y = v_S for side 0 and v_{S+1} for side 1,
+ *   out [R][C][J][10] fp64: per side the five sums over the tile's n of  s_t^2, (y - s_t)^2, (P - s_t)^2, P^2, (y - P)^2;
+ * tile j owns n in [j * tile, min((j + 1) * tile, Lr)) and the last tile also the tail [Lr, Lr + T - 1), where y is zero.
+ * target: [R] 64-bit reference indices ON THE DEVICE (clamped to [0, S)), or NULL: target0 for every recording.
+ * Samples are converted to fp64 before they are multiplied (in m2h_bss_corr every product is exact); all sums are fp64 in an order fixed
+ * by the recording alone (no atomics): the bits do not depend on the batch, the strides or a row's alignment.
+ * Both return a negative status and launch nothing for a null pointer, S outside 1 .. 6, C outside {1, 2}, R < 1, D outside 0 .. 8192 or
+ * not matching lag, L < 2 D + 1, T outside 1 .. 512, tile < 1, an out (or h) that is not 8-byte aligned, more than 2^31 - 1 (r, c, j)
+ * triples, and m2h_bss_project also for a target0 outside [0, S) when target is NULL. */
+int m2h_bss_corr(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                 const float* mix, long long mix_sr, long long mix_sc, double* out, int R, int S, int C, long long L, int tile, int T, const int* lag,
+                 int D, m2h_stream stream);
+int m2h_bss_project(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                    const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0, const double* h, double* out, int R,
+                    int S, int C, long long L, int tile, int T, const int* lag, int D, m2h_stream stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Whole-network runner: one C call enqueues every kernel of one separator U-Net forward (K1/K2 slice, 5 down stages, 5 up
  * stages, head) = PassiveSepEncCNN.forward + PassiveSepDecCNN.forward (separator_cnn.py:70-108,153-170) in eval mode.  Same

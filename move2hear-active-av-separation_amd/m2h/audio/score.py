@@ -178,6 +178,51 @@ from fp32 products, the mask and its scan, the envelopes (gather through the kep
 fft_lds.h in LDS, band sums in fp64 -- no frame, no overlap-added signal and no spectrum in memory) and the segments in fp64.  K stays
 on the device: no host synchronisation, and no copy from the host apart from three small tables on a Scorer's first stoi call.  No
 atomics, fixed summation orders: a recording's bits do not depend on the batch around it, on strides or on alignment.
+
+BSS.  score(..., bss=T) adds the number most separation papers call plain SDR: BSS-eval's SDR, SIR and SAR (Vincent et al. 2006), in which
+the estimate is projected on the references through a time-invariant distortion filter of T taps before anything is compared, so an
+estimate that carries a short FIR of the target (an early reflection, a codec's response) is not punished as if it were noise.  It is
+mir_eval.separation.bss_eval_sources for one target without permutation search, with the filter timing of museval v4: one filter set
+from the whole recording, window numbers from that filter's components.  T is a Python int in 1 .. 512 (None, the default: off); a bool,
+a float or a value outside the range is a TypeError / ValueError that names the value, before any launch.  Every other number is
+unchanged by a bit.
+
+Signals.  Per recording r and channel c the signals are those of "Spectral", taken raw, no mean removed: s_0 .. s_{S-1} =
+references[r, :, c] with the target j = target_r, x = estimate[r, c], and the baseline b = 0.5f (mixture[r, 0] + mixture[r, 1]) formed
+in float32 for C = 1, mixture[r, c] for C = 2.  With align=D the region is [D, L - D) and x is read lag[r, c] samples later, clamped to
+[-D, D], exactly as m2h_score_spectral reads it.  Lr is the region's length; every signal counts as zero outside the region -- no real
+sample outside it is used -- so an aligned call equals the unaligned call on hand-cut slices.  N = Lr + T - 1.
+
+  c_ik[d] = sum_t s_i[t] s_k[t + d]      d = -(T-1) .. T-1
+  p_i[a]  = sum_t s_i[t] x[t + a]        a = 0 .. T-1                (q_i the same with b)
+  G[(i,a),(k,b)] = c_ik[a - b]           (S T square, symmetric, block-Toeplitz: the Gram matrix of the shifted references)
+  G h = p  (joint filters h [S, T])      G_jj g = p_j  (the target alone, g [T])
+  s_t[n] = sum_a g[a] s_j[n - a]         P[n] = sum_i sum_a h_i[a] s_i[n - a]       n = 0 .. N-1, x zero-extended
+  sdr = 10 log10(|s_t|^2 / |x - s_t|^2)  sir = 10 log10(|s_t|^2 / |P - s_t|^2)      sar = 10 log10(|P|^2 / |x - P|^2)
+
+and the same with b in place of x, with its own h and g.  BSS_ORDER = (sdr, sir, sar, sdr_base, sir_base, sar_base, sdri, siri, sari),
+the improvements estimate minus baseline.  The kernel sums one-sided lags: co[i, k, d] = sum_t s_i[t] v_k[t + d], d = 0 .. T - 1, for
+v = (s_0 .. s_{S-1}, x, b); c_ik[d] is co[i, k, d] for d >= 0 and co[k, i, -d] for d < 0 when i <= k, and c_ki[d] = c_ik[-d], so G is
+symmetric by construction.
+
+Tiles and windows are score_plan's / align_plan's.  Tile j owns the output samples n in [j tile, (j + 1) tile) of [0, Lr); the last tile
+also owns the tail [Lr, N).  A tile's ten sums are |s_t|^2, |x - s_t|^2, |P - s_t|^2, |P|^2, |x - P|^2 and the five of the baseline; a
+window's sums are its tiles' sums in tile order (m2h_score_windows), the whole recording's are all J.  The result gains "bss_whole"
+[R, C, 9] and "bss_track" [R, C, M, 9], float64; the track uses the whole recording's filters.
+
+Degenerate input.  Lr >= S T is required (below that the normal equations are rank-deficient): a ValueError that names the values,
+before any launch.  A reference whose whole-recording energy c_ii[0] is 0 is left out: its block becomes the identity, its right-hand
+side 0 and its filter 0 (the rule of metrics_from_gram).  A silent target gives nine NaN; a factorisation that reports failure gives
+NaN for that (r, c) only.  Otherwise IEEE rules apply (a perfect estimate gives +inf, a window without tiles NaN); no non-negative
+quantity is formed as a difference.
+
+Method.  m2h_bss_corr (csrc/score_bss.hip) writes co per tile in fp64 -- every product of two fp32 samples exact, the sums in an order
+fixed by the recording alone, reads across the tile border but never past the region -- and m2h_score_windows adds the tiles; recordings
+go in groups whose tile correlations stay under `max_corr_bytes`.  bss_filters builds G by index gather and factorises ONE (r, c) at a
+time with torch.linalg.cholesky_ex + cholesky_solve in float64 on the device (never one batched call: the batch must not change a
+recording's bits); the joint system, the target-alone system and both right-hand sides share the factorisations.  m2h_bss_project
+applies the filters and writes the ten sums of every tile, no component signal ever stored, and bss_from_sums does the rest.  The
+Scorer's own code makes no host synchronisation; what the library's factorisation does is recorded in DESIGN.md 8.11.
 """
 import operator
 
@@ -202,6 +247,8 @@ SPATIAL_IPD_BANDS = 6        # the phase error is taken over the bands 0 .. 5: b
 STOI_ORDER = ("stoi", "estoi", "stoi_base", "estoi_base", "stoii", "estoii")
 STOI_TILE = 16000            # stoi=True: a tile is exactly STOI_FS resampled samples
 STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT, STOI_BANDS, STOI_SEGMENT = 10000, 256, 128, 512, 15, 30
+BSS_ORDER = ("sdr", "sir", "sar", "sdr_base", "sir_base", "sar_base", "sdri", "siri", "sari")
+BSS_MAX_TAPS = 512           # bss=T: the longest distortion filter
 
 
 def score_plan(L, tile=DEFAULT_TILE, window=1, hop=1):
@@ -511,6 +558,62 @@ def spatial_from_sums(sums):
     return torch.stack(e + b + [b[k] - e[k] for k in range(3)], dim=-1), torch.stack([ild, ipd, ic], dim=-1)
 
 
+def bss_filters(corr, target):
+    """The distortion filters of "BSS" (module docstring) from the whole-recording one-sided correlations, torch float64 on corr's device.
+
+    corr [R, C, S, S + 2, T] float64 (m2h_bss_corr's layout, tiles added); target an int or R ints (host)
+    -> (h [R, C, 2, S + 1, T]: per right-hand side (estimate, baseline) the joint filters and, in slot S, the target-alone filter;
+        ok [R, C] bool: the target has energy and both factorisations succeeded).
+    One (r, c) at a time, so that a recording's bits do not depend on the batch; no host synchronisation of its own."""
+    if not isinstance(corr, torch.Tensor) or corr.dtype != torch.float64:
+        raise TypeError("m2h.Scorer: correlations must be a float64 torch tensor, got %s" % (corr.dtype if isinstance(corr, torch.Tensor) else type(corr).__name__))
+    if corr.dim() != 5 or corr.shape[3] != corr.shape[2] + 2:
+        raise ValueError("m2h.Scorer: correlations must be [R, C, S, S + 2, T], got a tensor of shape %s" % (tuple(corr.shape),))
+    R, C, S, _, T = corr.shape
+    dev = corr.device
+    target = [int(target)] * R if isinstance(target, int) else [int(t) for t in target]
+    a = torch.arange(T, device=dev, dtype=torch.int64)
+    idx = (T - 1) + a[:, None] - a[None, :]                                             # G[(i, a), (k, b)] = c_ik[a - b]
+    eye4 = (torch.eye(S, dtype=torch.float64, device=dev)[:, None, :, None] * torch.eye(T, dtype=torch.float64, device=dev)[None, :, None, :])
+    h = torch.empty((R, C, 2, S + 1, T), dtype=torch.float64, device=dev)
+    ok = torch.empty((R, C), dtype=torch.bool, device=dev)
+    for r in range(R):
+        j = target[r]
+        for c in range(C):
+            co = corr[r, c]
+            two = co.new_empty((S, S, 2 * T - 1))                                       # c_ik[d] at index d + T - 1
+            for i in range(S):
+                for k in range(i, S):
+                    row = torch.cat([co[k, i].flip(0)[:-1], co[i, k]])
+                    two[i, k] = row
+                    if k > i:
+                        two[k, i] = row.flip(0)
+            keep = torch.stack([co[i, i, 0] for i in range(S)]) > 0                     # references with energy
+            G = torch.where(keep[:, None, None, None] & keep[None, None, :, None], two[:, :, idx].permute(0, 2, 1, 3), eye4)
+            rhs = torch.where(keep[:, None, None], co[:, S:].permute(0, 2, 1), torch.zeros((), dtype=torch.float64, device=dev))    # [S, T, 2]
+            chol, info = torch.linalg.cholesky_ex(G.reshape(S * T, S * T))
+            h[r, c, :, :S] = torch.cholesky_solve(rhs.reshape(S * T, 2), chol).t().reshape(2, S, T)
+            chol_j, info_j = torch.linalg.cholesky_ex(two[j, j][idx])
+            h[r, c, :, S] = torch.cholesky_solve(co[j, S:].t().contiguous(), chol_j).t()
+            ok[r, c] = keep[j] & (info == 0) & (info_j == 0)
+    return h, ok
+
+
+def bss_from_sums(sums, ok=None):
+    """The nine BSS numbers (module docstring, "BSS") from the ten sums, element-wise in torch float64 on sums' device.
+
+    sums [..., 10] float64; ok: a bool tensor that broadcasts against sums.shape[:-1] (False: nine NaN) -> [..., 9] in BSS_ORDER."""
+    if not isinstance(sums, torch.Tensor) or sums.dtype != torch.float64:
+        raise TypeError("m2h.Scorer: bss sums must be a float64 torch tensor, got %s" % (sums.dtype if isinstance(sums, torch.Tensor) else type(sums).__name__))
+    if sums.dim() < 1 or sums.shape[-1] != 10:
+        raise ValueError("m2h.Scorer: bss sums hold 10 numbers per row, got a tensor of shape %s" % (tuple(sums.shape),))
+    db = lambda num, den: 10.0 * torch.log10(num / den)                                 # noqa: E731
+    e = [db(sums[..., 0], sums[..., 1]), db(sums[..., 0], sums[..., 2]), db(sums[..., 3], sums[..., 4])]
+    b = [db(sums[..., 5], sums[..., 6]), db(sums[..., 5], sums[..., 7]), db(sums[..., 8], sums[..., 9])]
+    out = torch.stack(e + b + [e[k] - b[k] for k in range(3)], dim=-1)
+    return out if ok is None else torch.where(ok[..., None], out, torch.full_like(out, _NAN))
+
+
 def _whole_then_track(tiles, plan):
     """tiles [R, C, J, K] float64 -> [R, C, 1 + M, K]: all J tiles added in tile order, then the plan's M windows"""
     return torch.cat([ops.score_windows(tiles, 1, plan["J"], 1), ops.score_windows(tiles, plan["M"], plan["window"], plan["hop"])], dim=2)
@@ -570,7 +673,7 @@ class Scorer:
             ev.record(torch.cuda.current_stream(self.device))
             self._timing.append((stage, ev))
 
-    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spectral=False, spatial=False, stoi=False):
+    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spectral=False, spatial=False, stoi=False, bss=None):
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("m2h.Scorer: %s must be a torch tensor, got %s" % (name, type(t).__name__))
@@ -627,13 +730,21 @@ class Scorer:
         for name, on in (("spatial", spatial), ("spectral", spectral), ("stoi", stoi)):
             if on and plan["tile"] != SPECTRAL_TILE:
                 raise ValueError("m2h.Scorer: %s=True needs tile = %d (one second), got %d" % (name, SPECTRAL_TILE, plan["tile"]))
+        if bss is not None:
+            if isinstance(bss, bool) or not isinstance(bss, int):
+                raise TypeError("m2h.Scorer: bss must be an int (the filter length in taps) or None, got %r" % (bss,))
+            if not 1 <= bss <= BSS_MAX_TAPS:
+                raise ValueError("m2h.Scorer: bss must be in 1 .. %d taps, got %r" % (BSS_MAX_TAPS, bss))
+            if plan["L"] < S * bss:
+                raise ValueError("m2h.Scorer: bss = %d taps and S = %d references need at least S * bss = %d scored samples, got %d: the normal "
+                                 "equations would be rank-deficient" % (bss, S, S * bss, plan["L"]))
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not t.is_cuda or t.device != self.device:
                 raise ValueError("m2h.Scorer: %s must live on %s, got %s; the scorer has no CPU path" % (name, self.device, t.device))
         return refs, est, target, plan
 
     def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None, spectral=False, spatial=False,
-              stoi=False):
+              stoi=False, bss=None):
         """-> {"whole": [R, C, 11], "track": [R, C, M, 11], "active": [R, C, M] bool, "plan": score_plan(...)}; float64 on the device, in
         eval_metrics.METRIC_ORDER; no host synchronisation.  With align=D (an int, the largest lag searched in samples) the estimate is
         aligned to its target first: also "lag": [R, C] int32 and "lag_track": [R, C, M] int32 on the device, and "plan" is
@@ -642,8 +753,10 @@ class Scorer:
         "spatial_track": [R, M, 9], float64 in SPATIAL_ORDER, and the cues themselves, "spatial_cues": [R, M, 3, 32, 3] (signal target /
         estimate / mixture, band, ILD / IPD / IC).  With stoi=True (tile must be 16000) also "stoi_whole": [R, C, 6] and "stoi_track":
         [R, C, M, 6], float64 in STOI_ORDER, and "stoi_frames": [R, C, 1 + M] int64, the kept-frame count of the whole recording and of
-        every window.  The module docstring holds the definition."""
-        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial, stoi)
+        every window.  With bss=T (an int, the distortion filter's taps, 1 .. 512) also "bss_whole": [R, C, 9] and "bss_track": [R, C, M, 9],
+        float64 in BSS_ORDER.  The module docstring holds the definition."""
+        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial, stoi, bss)
+        targets = target                                                                # host integers (bss_filters)
         R, S, C, L = refs.shape
         J, M, tile, window, hop = (plan[k] for k in ("J", "M", "tile", "window", "hop"))
         D = plan.get("offset", 0)
@@ -707,6 +820,24 @@ class Scorer:
                 st = ops.stoi_ranges(x10, self._stoi_ranges(plan, sp), sp["total"], win, tw)
                 out.update({"stoi_whole": st["out"][:, :, 0], "stoi_track": st["out"][:, :, 1:], "stoi_frames": st["kept"][..., 0].to(torch.int64)})
                 self._mark("stoi_ranges")
+            if bss is not None:
+                lag = out.get("lag")
+                step = max(1, self.max_corr_bytes // (C * J * S * (S + 2) * bss * 8))   # recordings per group
+                corr = []
+                for r0 in range(0, R, step):
+                    r1 = min(r0 + step, R)
+                    ct = ops.bss_corr(refs[r0:r1], est[r0:r1], mixture[r0:r1], tile, bss, None if lag is None else lag[r0:r1], D)      # [r, C, J, S, S + 2, T]
+                    corr.append(ops.score_windows(ct.view(r1 - r0, C, J, S * (S + 2) * bss), 1, J, 1).view(r1 - r0, C, S, S + 2, bss))
+                    del ct
+                corr = corr[0] if len(corr) == 1 else torch.cat(corr)
+                self._mark("bss_corr")
+                h, ok = bss_filters(corr, targets)
+                self._mark("bss_solve")
+                sums = ops.bss_project(refs, est, mixture, target, h, tile, lag, D)     # [R, C, J, 10]
+                self._mark("bss_project")
+                b9 = bss_from_sums(_whole_then_track(sums, plan), ok[:, :, None])
+                out.update({"bss_whole": b9[:, :, 0], "bss_track": b9[:, :, 1:]})
+                self._mark("bss_metrics")
         out.update({"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan})
         return out
 
@@ -716,7 +847,8 @@ def summarize(result):
     active windows ([R][C][11], NaN without any), "active_windows": [R][C]} as Python lists (one synchronisation); with spectral=True /
     spatial=True results also the "spectral_*" / "spatial_*" keys (spatial: [R][9], over the windows in which both ears are active); with
     stoi=True results also "stoi_metrics", "stoi_whole" [R][C][6], "stoi_track_mean" / "stoi_track_median" over the windows that are not NaN
-    and "stoi_frames" [R][C][1 + M]."""
+    and "stoi_frames" [R][C][1 + M]; with bss=T results also "bss_metrics", "bss_whole" [R][C][9] and "bss_track_mean" / "bss_track_median" over
+    the active windows."""
     import numpy as np
     whole, track, active = (result[k].cpu().numpy() for k in ("whole", "track", "active"))
     R, C = whole.shape[:2]
@@ -761,4 +893,14 @@ def summarize(result):
                         tmean[r, c], tmedian[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
         out.update({"stoi_metrics": list(STOI_ORDER), "stoi_whole": tw.tolist(), "stoi_track_mean": tmean.tolist(), "stoi_track_median": tmedian.tolist(),
                     "stoi_frames": result["stoi_frames"].cpu().tolist()})
+    if "bss_whole" in result:                                                          # score(..., bss=T): over the active windows
+        bw, bt = result["bss_whole"].cpu().numpy(), result["bss_track"].cpu().numpy()
+        bmean, bmedian = np.full((R, C, 9), np.nan), np.full((R, C, 9), np.nan)
+        with np.errstate(all="ignore"):
+            for r in range(R):
+                for c in range(C):
+                    rows = bt[r, c][active[r, c]]
+                    if rows.shape[0]:
+                        bmean[r, c], bmedian[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
+        out.update({"bss_metrics": list(BSS_ORDER), "bss_whole": bw.tolist(), "bss_track_mean": bmean.tolist(), "bss_track_median": bmedian.tolist()})
     return out

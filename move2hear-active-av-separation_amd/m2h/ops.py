@@ -895,6 +895,51 @@ def stoi_ranges(x10, ranges, slots, window, twiddles):
     return res
 
 
+BSS_MAX_TAPS = 512                           # the longest distortion filter of m2h_bss_corr / m2h_bss_project (include/m2h.h)
+
+
+def _score_bss(what, refs, tile, T, lag, D):
+    """what bss_corr and bss_project share beyond the signals: tile, T, the D / lag rule -> (tile, T, D, J, lag pointer)"""
+    L, tile, T, D = refs.shape[3], int(tile), int(T), int(D)
+    if not 1 <= T <= BSS_MAX_TAPS or tile < 1 or not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
+        raise RuntimeError("m2h.%s: T = %d in 1 .. %d, tile = %d >= 1, D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required"
+                           % (what, T, BSS_MAX_TAPS, tile, D, L))
+    return tile, T, D, -(-(L - 2 * D) // tile), None if lag is None else _score_lag(what, lag, refs)
+
+
+def bss_corr(refs, est, mix, tile, T, lag=None, D=0):
+    """Tile correlations of the Scorer's BSS-eval numbers (m2h/audio/score.py, "BSS"): refs [R, S, C, L], est [R, C, L], mix [R, 2, L] fp32
+    with unit last stride (views are read in place); T the filter length, 1 .. 512; lag and D as for score_spectral
+    -> [R, C, J, S, S + 2, T] fp64, J = ceil((L - 2 D) / tile):  out[r, c, j, i, k, d] = sum over tile j of v_i[t] v_k[t + d] with
+    v_0 .. v_{S-1} the references, v_S the estimate at its lag and v_{S+1} the baseline, all zero outside the region (include/m2h.h)."""
+    R, S, C, L = _score_signals("bss_corr", refs, est, mix)
+    tile, T, D, J, lptr = _score_bss("bss_corr", refs, tile, T, lag, D)
+    out = torch.empty((R, C, J, S, S + 2, T), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_bss_corr(*_score_args(refs, est, mix), _ptr(out), R, S, C, L, tile, T, lptr, D, _stream(refs)), "m2h_bss_corr")
+    return out
+
+
+def bss_project(refs, est, mix, target, h, tile, lag=None, D=0):
+    """The filters applied and the ten energies of every tile (m2h/audio/score.py, "BSS"): signals, lag and D as for bss_corr; target an
+    int, or an int64 tensor [R] on the device; h [R, C, 2, S + 1, T] fp64 contiguous on the device: per right-hand side (estimate,
+    baseline) the S joint filters and in slot S the target-alone filter -> [R, C, J, 10] fp64; the last tile also owns the tail of
+    T - 1 samples (include/m2h.h)."""
+    R, S, C, L = _score_signals("bss_project", refs, est, mix)
+    _chk(h, "bss_project(h)", torch.float64)
+    if h.dim() != 5 or tuple(h.shape[:4]) != (R, C, 2, S + 1) or h.device != refs.device:
+        raise RuntimeError("m2h.bss_project: h must be [R, C, 2, S + 1, T] = [%d, %d, 2, %d, T] float64 on %s, got %s" % (R, C, S + 1, refs.device, tuple(h.shape)))
+    tile, T, D, J, lptr = _score_bss("bss_project", refs, tile, h.shape[4], lag, D)
+    tptr, t0 = _score_target("bss_project", target, refs)
+    out = torch.empty((R, C, J, 10), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_bss_project(*_score_args(refs, est, mix), tptr, t0, _ptr(h), _ptr(out), R, S, C, L, tile, T, lptr, D, _stream(refs)),
+                   "m2h_bss_project")
+    return out
+
+
 def score_windows(tiles, M, window, hop):
     """tiles [R, C, J, K] fp64 -> [R, C, M, K]: every window's tiles added in tile order (window m: tiles m * hop .. m * hop + window - 1)."""
     _chk(tiles, "score_windows", torch.float64)

@@ -2,7 +2,7 @@
 """Score a separated recording of any length against its ground truth:
 
     python score.py --estimate out.wav --mixture mix.wav --reference target.wav [--reference other.wav ...] [--window W --hop H]
-                    [--align D] [--spectral] [--spatial] [--stoi] [--json scores.json]
+                    [--align D] [--spectral] [--spatial] [--stoi] [--bss [T]] [--json scores.json]
 
 ``--reference``: the sources as they are in the mixture, at most six; the FIRST one is the target the estimate is scored against, the
 others are the interferers (they enter SI-SIR and SI-SAR).  ``render.py --out-target / --out-image`` writes such files.  ``--mixture``:
@@ -35,6 +35,12 @@ estimate are read at the left ear's lag.
 same for the mixture as the estimate, and the two improvements, for the same whole recording and the same windows, as rows under the
 table and as ``stoi_*`` keys in the JSON (``stoi_frames``: the frames kept after silent-frame removal, whole recording first).  A window
 with fewer than 31 kept frames has no STOI (NaN) and is left out of the mean and the median.
+
+``--bss [T]`` adds BSS-eval's SDR, SIR and SAR (m2h/audio/score.py, "BSS"): the estimate is projected on the references through a
+distortion filter of T taps (512 without a value, at most 512) before it is compared, so a short filtering of the target -- an early
+reflection, a codec's response -- is not counted as noise.  One filter set is fitted to the whole recording; the same numbers for the
+mixture as the estimate and the three improvements come with them, as rows under the table and as ``bss_*`` keys in the JSON.  The
+recording must hold at least T samples per reference.
 """
 import argparse
 import json
@@ -71,6 +77,8 @@ def main():
     parser.add_argument("--spectral", action="store_true", help="also the STFT distance per window and over the whole recording")
     parser.add_argument("--spatial", action="store_true", help="also the interaural cue errors (ILD, IPD, IC) per window and over the whole recording; two-channel files")
     parser.add_argument("--stoi", action="store_true", help="also STOI and ESTOI per window and over the whole recording")
+    parser.add_argument("--bss", type=int, nargs="?", const=512, default=None, metavar="T",
+                        help="also BSS-eval SDR, SIR and SAR through a distortion filter of T taps (default 512)")
     parser.add_argument("--json", default=None, help="write every number here")
     args = parser.parse_args()
     import numpy as np
@@ -96,7 +104,8 @@ def main():
     try:
         res = Scorer(dev).score(torch.from_numpy(np.ascontiguousarray(est)).to(dev)[None], torch.from_numpy(np.stack(refs)).to(dev)[None],
                                 torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop, align=args.align,
-                                spectral=args.spectral, **({"spatial": True} if args.spatial else {}), **({"stoi": True} if args.stoi else {}))
+                                spectral=args.spectral, **({"spatial": True} if args.spatial else {}), **({"stoi": True} if args.stoi else {}),
+                                **({"bss": args.bss} if args.bss is not None else {}))
     except (ValueError, TypeError) as e:
         raise SystemExit("score.py: %s" % e)
     s = summarize(res)
@@ -130,6 +139,11 @@ def main():
         for c in range(C):
             for label, key in (("stoi whole", "stoi_whole"), ("stoi window mean", "stoi_track_mean"), ("stoi window median", "stoi_track_median")):
                 print("%-8s %-23s" % (names[c], label) + " ".join("%20.12e" % v for v in s[key][0][c]))
+    if args.bss is not None:
+        print("%-8s %-23s" % ("bss %d" % args.bss, "") + " ".join("%20s" % m for m in s["bss_metrics"]))
+        for c in range(C):
+            for label, key in (("bss whole", "bss_whole"), ("bss window mean", "bss_track_mean"), ("bss window median", "bss_track_median")):
+                print("%-8s %-23s" % (names[c], label) + " ".join("%20.12e" % v for v in s[key][0][c]))
     if args.json is not None:
         out = {"estimate": args.estimate, "mixture": args.mixture, "references": args.reference, "sample_rate": separate.SAMPLE_RATE,
                "samples": L, "channels": list(names), "window_s": args.window, "hop_s": args.hop, "metrics": s["metrics"],
@@ -147,6 +161,10 @@ def main():
         if args.stoi:
             out.update({"stoi_metrics": s["stoi_metrics"], "stoi_whole": s["stoi_whole"][0], "stoi_track": res["stoi_track"][0].cpu().numpy().tolist(),
                         "stoi_track_mean": s["stoi_track_mean"][0], "stoi_track_median": s["stoi_track_median"][0], "stoi_frames": s["stoi_frames"][0]})
+        if args.bss is not None:
+            out.update({"bss_taps": args.bss, "bss_metrics": s["bss_metrics"], "bss_whole": s["bss_whole"][0],
+                        "bss_track": res["bss_track"][0].cpu().numpy().tolist(), "bss_track_mean": s["bss_track_mean"][0],
+                        "bss_track_median": s["bss_track_median"][0]})
         if args.align is not None:
             out.update({"align": args.align, "region": [t0, t1], "lag": lag, "lag_track": res["lag_track"][0].cpu().tolist()})
         with open(args.json, "w") as f:

@@ -11,6 +11,8 @@
     python tools/score_bench.py --case 16x3x600c2 --spatial          # one case of it in this process
     python tools/score_bench.py --stoi --out profiles/score_stoi_bench.json                         # STOI / ESTOI, every case
     python tools/score_bench.py --case 1x2x60c2 --stoi               # one case of it in this process
+    python tools/score_bench.py --bss --out profiles/score_bss_bench.json                           # BSS-eval SDR / SIR / SAR at 512 taps, every case
+    python tools/score_bench.py --case 1x2x60c2 --bss                # one case of it in this process
 
 Cases (R recordings x S sources x seconds, C channels): 16x3x600 and 1x2x60, each with C = 1 and C = 2; per-second windows.  Timing: HIP
 events on the stream around the Gram launch and around everything after it (Scorer._timing), summed over the repetitions.
@@ -54,6 +56,15 @@ With --stoi (Scorer.score(..., stoi=True): the whole recording and every one-sec
                           boolean-mask compaction (one host synchronisation per range), torch.fft.rfft and float64 tensor algebra, one
                           recording at a time; the largest difference of its six numbers from the kernels' is recorded
   extra_ms_in_score       what stoi=True adds to one Scorer.score
+With --bss (Scorer.score(..., bss=512); per-stage HIP events on the stream, Scorer._timing):
+  corr_ms, solve_ms, project_ms, metrics_ms   m2h_bss_corr with the m2h_score_windows that adds its tiles; bss_filters (torch float64: the
+                          index gather and one Cholesky factorisation and solve per system); m2h_bss_project; the windows and bss_from_sums
+  corr_flops_per_s, project_flops_per_s       2 S (S + 2) T Lr and 4 (S + 1) T (Lr + T - 1) flop per (recording, channel) over the stage's time,
+                          and their share of the published fp64 vector peak, 78.6 TFLOP/s
+  torch_bss_ms            the yardstick in the same run, before and after: the same definition composed on the GPU from torch.fft
+                          correlations in float64, the same factorisations, and float64 conv1d for the two projections, one (recording,
+                          channel) at a time; the largest difference of its nine numbers from the Scorer's, whole and track, is recorded
+  extra_ms_in_score       what bss=512 adds to one Scorer.score
 No threshold is set anywhere: the file reports what came out.  Every GPU step runs under its own timeout and the driver stops at the
 first failure.
 """
@@ -429,6 +440,133 @@ def run_stoi_case(case):
     return res
 
 
+FP64_VECTOR_PEAK = 78.6e12     # flop/s, the published fp64 vector peak of the MI355X
+BSS_TAPS = 512
+
+
+def torch_bss(s, ys, j, T, tile, chunk=1 << 20):
+    """The ten sums of every tile of one (recording, channel), composed from torch: s [S, L] and ys [2, L] fp32 (estimate, baseline), L a
+    multiple of the tile -> [J, 10] float64.  torch.fft correlations, Cholesky, float64 conv1d in chunks of `chunk` outputs."""
+    import torch
+    import torch.nn.functional as F
+    S, L = s.shape
+    N = L + T - 1
+    nfft = 1 << (N - 1).bit_length()
+    sd, yd = s.double(), ys.double()
+    Fs, Fy = torch.fft.rfft(sd, nfft), torch.fft.rfft(yd, nfft)
+
+    def lags(A, B):                                                                     # sum_t a[t] b[t + d], d = -(T - 1) .. T - 1
+        c = torch.fft.irfft(torch.conj(A) * B, nfft)
+        return torch.cat([c[..., nfft - (T - 1):], c[..., :T]], dim=-1)
+
+    a = torch.arange(T, device=s.device)
+    idx = (T - 1) + a[:, None] - a[None, :]
+    c = torch.stack([lags(Fs[i:i + 1], Fs) for i in range(S)])                          # [S, S, 2 T - 1]
+    p = torch.stack([lags(Fs[i:i + 1], Fy)[:, T - 1:] for i in range(S)])               # [S, 2, T]
+    del Fs, Fy
+    G = c[:, :, idx].permute(0, 2, 1, 3).reshape(S * T, S * T)
+    h = torch.cholesky_solve(p.permute(0, 2, 1).reshape(S * T, 2), torch.linalg.cholesky_ex(G)[0])
+    g = torch.cholesky_solve(p[j].t().contiguous(), torch.linalg.cholesky_ex(c[j, j][idx])[0])
+    w = torch.zeros((4, S, T), dtype=torch.float64, device=s.device)                    # P and s_t of the estimate, then of the baseline
+    w[0], w[2] = h[:, 0].reshape(S, T), h[:, 1].reshape(S, T)
+    w[1, j], w[3, j] = g[:, 0], g[:, 1]
+    w = w.flip(-1).contiguous()                                                         # conv1d correlates
+    inp = F.pad(sd, (T - 1, T - 1))[None]
+    comp = torch.cat([F.conv1d(inp[:, :, n0:min(n0 + chunk, N) + T - 1], w)[0] for n0 in range(0, N, chunk)], dim=-1)     # [4, N]
+    yz = F.pad(yd, (0, T - 1))
+    sq = []
+    for q in range(2):
+        P, st, y = comp[2 * q], comp[2 * q + 1], yz[q]
+        sq += [st * st, (y - st) ** 2, (P - st) ** 2, P * P, (y - P) ** 2]
+    sq = torch.stack(sq)                                                                # [10, N]
+    sums = sq[:, :L].reshape(10, L // tile, tile).sum(-1)
+    sums[:, -1] += sq[:, L:].sum(-1)                                                    # the last tile owns the tail
+    return sums.t()
+
+
+def run_bss_case(case):
+    import torch
+    from m2h.audio import score as SC
+    if not torch.cuda.is_available():
+        raise SystemExit("score_bench: no GPU; this measurement has no CPU path")
+    R, S, seconds, C, reps = CASES[case]
+    reps = max(1, reps // 10)
+    dev = torch.device("cuda", 0)
+    L, T = seconds * SEG, BSS_TAPS
+    g = torch.Generator(device=dev).manual_seed(7)
+    refs = torch.randn((R, S, C, L), device=dev, generator=g) * 0.1 + 0.01
+    mix = torch.stack([refs[:, :, 0].mean(1), refs[:, :, C - 1].mean(1)], dim=1) + 0.02 * torch.randn((R, 2, L), device=dev, generator=g)
+    est = 0.8 * refs[:, 0] + 0.03 * torch.randn((R, C, L), device=dev, generator=g)
+    sc = SC.Scorer(dev)
+    plan = SC.score_plan(L)
+    base = mix if C == 2 else 0.5 * (mix[:, :1] + mix[:, 1:])
+    J = plan["J"]
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def yard():
+        rows = []
+        for r in range(R):
+            for c in range(C):
+                tiles = torch_bss(refs[r, :, c], torch.stack([est[r, c], base[r, c]]), 0, T, SEG)
+                rows.append(torch.cat([tiles.sum(0, keepdim=True), tiles]))              # whole, then the one-second track
+        return SC.bss_from_sums(torch.stack(rows).view(R, C, 1 + J, 10))
+
+    def staged():
+        marks = []
+        sc._timing = marks
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            sc.score(est, refs, mix, bss=T)
+        torch.cuda.synchronize()
+        sc._timing = None
+        ms = {}
+        for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
+            if name != "start":
+                ms[name] = ms.get(name, 0.0) + e0.elapsed_time(e1) / reps
+        return ms
+
+    res0 = sc.score(est, refs, mix, bss=T)                                              # warm-up of every shape
+    got = torch.cat([res0["bss_whole"][:, :, None], res0["bss_track"]], dim=2)
+    want = yard()
+    diff = float(torch.nan_to_num((got - want).abs(), nan=0.0, posinf=0.0).max())
+    same_nan = bool(torch.equal(torch.isnan(got), torch.isnan(want)))
+    del want
+    torch.cuda.synchronize()
+    before = timed(yard, 1)
+    ms = staged()
+    plain = timed(lambda: sc.score(est, refs, mix), reps)
+    full = timed(lambda: sc.score(est, refs, mix, bss=T), reps)
+    after = timed(yard, 1)
+    ms2 = staged()
+    RC = R * C
+    flops = {"corr": RC * 2.0 * S * (S + 2) * T * L, "project": RC * 4.0 * (S + 1) * T * (L + T - 1)}
+    kernels = 0.5 * sum(ms[k] + ms2[k] for k in ("bss_corr", "bss_solve", "bss_project", "bss_metrics"))
+    per = C * J * S * (S + 2) * T * 8
+    res = {"case": case, "bss": T, "R": R, "S": S, "C": C, "audio_seconds_per_recording": seconds, "reps": reps,
+           "corr_ms": [ms["bss_corr"], ms2["bss_corr"]], "solve_ms": [ms["bss_solve"], ms2["bss_solve"]],
+           "project_ms": [ms["bss_project"], ms2["bss_project"]], "metrics_ms": [ms["bss_metrics"], ms2["bss_metrics"]],
+           "systems": 2 * RC, "system_size": S * T, "corr_bytes_per_recording": per, "corr_groups": -(-R // max(1, sc.max_corr_bytes // per)),
+           "flops": flops, "corr_flops_per_s": flops["corr"] / (min(ms["bss_corr"], ms2["bss_corr"]) * 1e-3),
+           "project_flops_per_s": flops["project"] / (min(ms["bss_project"], ms2["bss_project"]) * 1e-3),
+           "torch_bss_ms": [before, after], "torch_bss_reps": 1, "torch_over_bss_stages": 0.5 * (before + after) / kernels,
+           "score_ms": plain, "score_bss_ms": full, "extra_ms_in_score": full - plain, "audio_s_per_s": R * seconds / (full * 1e-3),
+           "scorer_vs_torch_max_abs_db": diff, "nan_in_the_same_places": same_nan, "sdr_whole_db": float(res0["bss_whole"][0, 0, 0]),
+           "si_sdr_whole_db": float(res0["whole"][0, 0, 0])}
+    res["corr_share_of_fp64_vector_peak"] = res["corr_flops_per_s"] / FP64_VECTOR_PEAK
+    res["project_share_of_fp64_vector_peak"] = res["project_flops_per_s"] / FP64_VECTOR_PEAK
+    print(json.dumps(res))
+    return res
+
+
 def run_align_case(case, D):
     import torch
     from m2h.audio.score import Scorer, lags_from_corr
@@ -508,13 +646,16 @@ def main():
     ap.add_argument("--spectral", action="store_true", help="measure the STFT distance's launch (Scorer.score(..., spectral=True))")
     ap.add_argument("--spatial", action="store_true", help="measure the interaural cues' launch (Scorer.score(..., spatial=True)); two-channel cases")
     ap.add_argument("--stoi", action="store_true", help="measure STOI / ESTOI (Scorer.score(..., stoi=True)) against its composition from torch")
+    ap.add_argument("--bss", action="store_true", help="measure BSS-eval SDR / SIR / SAR at 512 taps (Scorer.score(..., bss=512)) against its composition from torch")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=120, help="driver mode: seconds per case")
     args = ap.parse_args()
-    if (args.spectral or args.spatial or args.stoi) and args.align or args.spectral + args.spatial + args.stoi > 1:
-        raise SystemExit("score_bench: --spectral, --spatial, --stoi and --align are measured separately")
+    if (args.spectral or args.spatial or args.stoi or args.bss) and args.align or args.spectral + args.spatial + args.stoi + args.bss > 1:
+        raise SystemExit("score_bench: --spectral, --spatial, --stoi, --bss and --align are measured separately")
     if args.case is not None:
-        if args.stoi:
+        if args.bss:
+            run_bss_case(args.case)
+        elif args.stoi:
             run_stoi_case(args.case)
         elif args.spatial:
             run_spatial_case(args.case)
@@ -529,7 +670,7 @@ def main():
     results = []
     for case, D in [(case, D) for D in (args.align or [None]) for case in ORDER if CASES[case][3] == 2 or not args.spatial]:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case] + ([] if D is None else ["--align", str(D)]) + \
-            (["--spectral"] if args.spectral else []) + (["--spatial"] if args.spatial else []) + (["--stoi"] if args.stoi else [])
+            (["--spectral"] if args.spectral else []) + (["--spatial"] if args.spatial else []) + (["--stoi"] if args.stoi else []) + (["--bss"] if args.bss else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             print(r.stdout[-4000:])
@@ -540,7 +681,8 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/score_bench.py", "device": "MI355X (gfx950)", "copy_rate_bytes_per_s": COPY_RATE,
-                       **({"fp32_matrix_peak_flops_per_s": FP32_MATRIX_PEAK} if args.spectral or args.spatial else {}), "results": results}, f, indent=1)
+                       **({"fp32_matrix_peak_flops_per_s": FP32_MATRIX_PEAK} if args.spectral or args.spatial else {}),
+                       **({"fp64_vector_peak_flops_per_s": FP64_VECTOR_PEAK} if args.bss else {}), "results": results}, f, indent=1)
             f.write("\n")
 
 
