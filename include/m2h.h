@@ -827,6 +827,25 @@ int m2h_score_spatial(const float* refs, long long refs_sr, long long refs_ss, l
                       const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0, const float* dft, double* out,
                       int R, int S, long long L, const int* lag, int D, m2h_stream stream);
 
+/* Scorer, broadband ITD (m2h/audio/score.py, "ITD"; csrc/score_itd.hip).
+ * m2h_score_itd: the arguments, the signals (BOTH ears of the estimate at the one lag of the left ear), the tiles and the table dft are
+ * m2h_score_spatial's; only the bins 0 .. 255 are transformed.
+ *   out [R][J][3][256][2] fp64: signal x, bin k, and the cross-spectrum of the ears summed over the tile's 32 frames:
+ *     0 CRE = Re(X_L conj X_R)   1 CIM = Im(X_L conj X_R) = Im X_L Re X_R - Re X_L Im X_R
+ * Exact fp64 products of the fp32 spectra, a fixed summation order (no atomics) that does not depend on the batch, the strides or a
+ * row's alignment.  Refusals as m2h_score_spatial's, under the name score_itd.
+ * m2h_itd_gcc: the PHAT-weighted cross-correlation of every row of sums at the lags i / 8 samples, i = -128 .. 128:
+ *   sums [rows][256][2] fp64 (CRE, CIM per bin; tile sums or sums of tiles), gcc [rows][257] fp64,
+ *   gcc[row][i + 128] = 1 / (k_hi - k_lo) * sum over k = k_lo .. k_hi - 1, in ascending k, of Re(P_k exp(-j 2 pi k i / 8184)),
+ *   P_k = (CRE + j CIM) / sqrt(CRE^2 + CIM^2), or 0 where that magnitude is 0.
+ *   table [8184][2] fp64 ON THE DEVICE (m2h.audio.score.itd_table): cos and sin of 2 pi t / 8184; entry (k i) mod 8184 is read.
+ * Returns a negative status and launches nothing for a null pointer, bins outside 0 <= k_lo < k_hi <= 256, rows outside 1 .. 2^31 - 1
+ * or a pointer that is not 8-byte aligned. */
+int m2h_score_itd(const float* refs, long long refs_sr, long long refs_ss, long long refs_sc, const float* est, long long est_sr, long long est_sc,
+                  const float* mix, long long mix_sr, long long mix_sc, const long long* target, int target0, const float* dft, double* out,
+                  int R, int S, long long L, const int* lag, int D, m2h_stream stream);
+int m2h_itd_gcc(const double* sums, const double* table, double* gcc, long long rows, int k_lo, int k_hi, m2h_stream stream);
+
 /* Scorer, STOI and ESTOI (m2h/audio/score.py, "STOI"; csrc/score_stoi.hip).
  * m2h_stoi_resample: for (r, c) the three signals of m2h_score_spectral over the region [D, L - D) -- 0: the clean signal
  * refs[r][target_r][c][D + t], 1: the estimate est[r][c][D + lag[r * C + c] + t], 2: the baseline mix[r][c][D + t] for C = 2,

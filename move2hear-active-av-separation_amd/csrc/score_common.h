@@ -1,4 +1,4 @@
-// What the Scorer's launches share (score.hip, align.hip, score_spectral.hip, score_spatial.hip): the description of the signals, the two rules that keep
+// What the Scorer's launches share (score.hip, align.hip, score_spectral.hip, score_spatial.hip, score_itd.hip): the description of the signals, the two rules that keep
 // device data from becoming an address out of bounds, and the argument checks of the entry points.
 #pragma once
 #include "m2h_internal.h"

@@ -1,7 +1,7 @@
-// The Scorer's tile spectrogram, stated once for score_spectral.hip (three signals: target, estimate, baseline) and score_spatial.hip (the
-// two ears of one signal).  It is the Separator's (m2h.audio.stft): the one-second tile zero-extended to 16000 samples, reflect-padded by
-// 511 inside the tile, 32 frames of 1023 samples every 512, periodic Hann, 1023-point DFT, bins 0 .. 511.  No frame and no spectrum is
-// ever written to memory.
+// The Scorer's tile spectrogram, stated once for score_spectral.hip (three signals: target, estimate, baseline), score_spatial.hip and
+// score_itd.hip (the two ears of one signal).  It is the Separator's (m2h.audio.stft): the one-second tile zero-extended to 16000
+// samples, reflect-padded by 511 inside the tile, 32 frames of 1023 samples every 512, periodic Hann, 1023-point DFT, bins 0 .. 511.  No
+// frame and no spectrum is ever written to memory.
 //
 // The transform is a GEMM on the exact fp32 matrix instruction v_mfma_f32_16x16x4_f32: rows = frames (A operand: samples), columns =
 // bins (B operand: the host-built table, window folded in).  The window and the DFT are both symmetric under n <-> 1023 - n (w[0] = 0),
@@ -17,6 +17,10 @@
 // accumulators of 4 registers, so a lane holds Re and Im of every signal at the same (frame, bin) and an epilogue needs no exchange.
 // Per k-step of 4 samples a wave issues 2 NS LDS reads, 8 coalesced 256-byte table reads (prefetched one step ahead) and 8 NS MFMAs.
 // Only the staged values enter the arithmetic: the same bits for any batch, stride or alignment around a recording.
+//
+// stft_half<NS, NY> is the same with NY column tiles per wave, wave w owning the bins 16 NY w .. 16 NY (w + 1) - 1: NY = 4, the default,
+// is all 512 bins and what is written above; score_itd.hip needs the bins 0 .. 255 only and runs NY = 2 -- half the table reads, MFMAs
+// and accumulators, the same LDS reads.
 #pragma once
 #include "score_common.h"
 
@@ -61,33 +65,33 @@ __device__ __forceinline__ void stft_stage(float* smem, int h, int n, int tid, L
   }
 }
 
-// The staged half's 16 frames x the wave's 64 bins: re[s][y], im[s][y] of signal s and column tile y, from zero.  The lane's addresses are
+// The staged half's 16 frames x the wave's 16 NY bins: re[s][y], im[s][y] of signal s and column tile y, from zero.  The lane's addresses are
 // formed in here (and hoisted out of the caller's loop over the halves): handed in as a struct from a helper, the k-loop comes out scheduled
 // differently and score_spectral_kernel 1 % slower (profiles/score_stft_isa.txt).
-template <int NS>
-__device__ __forceinline__ void stft_half(const float* smem, const float* dft, int lane, int wave, f32x4 (&re)[NS][4], f32x4 (&im)[NS][4]) {
+template <int NS, int NY = 4>
+__device__ __forceinline__ void stft_half(const float* smem, const float* dft, int lane, int wave, f32x4 (&re)[NS][NY], f32x4 (&im)[NS][NY]) {
   // A fragment: lane l holds A[frame l & 15][k = l >> 4]; B fragment: B[k = l >> 4][bin l & 15]; C/D: bin l & 15, frame 4 (l >> 4) + reg
   const int m = lane & 15, kq = lane >> 4;
   const int lo0 = STFT_HOP * m + kq + 4 * m;                             // word of sample n = kq of frame m (then + 4 per k-step)
   const int hi0 = STFT_HOP * m + 1023 - kq + 4 * (m + 1);                // word of its partner 1023 - n (then - 4 per k-step)
-  const float* tb = dft + (size_t)(4 * wave) * STFT_TABLE_BT + lane;
+  const float* tb = dft + (size_t)(NY * wave) * STFT_TABLE_BT + lane;
 #pragma unroll
   for (int s = 0; s < NS; ++s)
 #pragma unroll
-    for (int y = 0; y < 4; ++y) re[s][y] = im[s][y] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int y = 0; y < NY; ++y) re[s][y] = im[s][y] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  float bc[4], bs[4];
+  float bc[NY], bs[NY];
 #pragma unroll
-  for (int y = 0; y < 4; ++y) {
+  for (int y = 0; y < NY; ++y) {
     bc[y] = tb[y * STFT_TABLE_BT];
     bs[y] = tb[y * STFT_TABLE_BT + 64];
   }
 #pragma unroll 2
   for (int ks = 0; ks < STFT_KSTEPS; ++ks) {
     const int kn = ks + 1 < STFT_KSTEPS ? ks + 1 : ks;                   // the next step's table fragments, in flight under this step's MFMAs
-    float nc[4], ns[4];
+    float nc[NY], ns[NY];
 #pragma unroll
-    for (int y = 0; y < 4; ++y) {
+    for (int y = 0; y < NY; ++y) {
       nc[y] = tb[y * STFT_TABLE_BT + kn * 128];
       ns[y] = tb[y * STFT_TABLE_BT + kn * 128 + 64];
     }
@@ -100,14 +104,14 @@ __device__ __forceinline__ void stft_half(const float* smem, const float* dft, i
       ad[s] = x0 - x1;
     }
 #pragma unroll
-    for (int y = 0; y < 4; ++y)
+    for (int y = 0; y < NY; ++y)
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         re[s][y] = __builtin_amdgcn_mfma_f32_16x16x4f32(as[s], bc[y], re[s][y], 0, 0, 0);
         im[s][y] = __builtin_amdgcn_mfma_f32_16x16x4f32(ad[s], bs[y], im[s][y], 0, 0, 0);
       }
 #pragma unroll
-    for (int y = 0; y < 4; ++y) bc[y] = nc[y], bs[y] = ns[y];
+    for (int y = 0; y < NY; ++y) bc[y] = nc[y], bs[y] = ns[y];
   }
 }
 

@@ -129,8 +129,53 @@ denominator alike, and no valid band gives NaN.  The nine numbers, in SPATIAL_OR
 The whole-recording numbers are the long-term cues of the SUMMED spectra (all J tiles' sums added first), not the mean of the track.
 m2h_score_spatial (csrc/score_spatial.hip) computes the tile sums straight from the waveforms -- the same folded transform on the exact
 fp32 matrix instruction, the four fp32 values of a bin converted to fp64 before they are multiplied, no frame or spectrum ever in
-memory.  No host synchronisation; the only copy from the host is the transform table, once.  Not done: a broadband ITD in microseconds
-(a GCC-PHAT peak).
+memory.  No host synchronisation; the only copy from the host is the transform table, once.  The broadband ITD in microseconds is
+itd=True, below.
+
+ITD.  score(..., itd=True) adds the number spatial-audio work reports first: the broadband interaural time difference of the target, the
+estimate and the mixture, in microseconds, as the peak of the PHAT-weighted generalised cross-correlation (GCC-PHAT) of the two ears,
+per window and over the whole recording.  It needs C = 2 and tile = 16000, as spatial=True does (a ValueError that names the offending
+value, before any launch; a non-bool itd is a TypeError); every other number is unchanged by a bit.
+
+Signals, tiles and spectra are those of "Spatial", unchanged: G = references[r, target_r], E = estimate[r], B = mixture[r], raw; the
+spectrogram of a one-second tile is the Separator's; with align=D the region is [D, L - D) and BOTH EARS of the estimate are read at the
+left ear's lag, so that the delay being measured survives the alignment.
+
+Tile sums.  For every (recording, tile, signal) and every bin k = 0 .. 255 the cross-spectrum summed over the tile's 32 frames,
+
+  CRE_k = sum_f Re(X_L conj X_R)      CIM_k = sum_f Im(X_L conj X_R)
+
+-- exactly the cross term of "Spatial", per bin instead of per band of 16: float64 [R, J, 3, 256, 2].  A window's sums are its tiles'
+added in tile order and the whole recording's are all J tiles added (m2h_score_windows with RC = R and K = 1536); as in "Spatial" the
+whole-recording number is the cue of the SUMMED spectra, not the mean of the track.
+
+GCC-PHAT of a window.  The band is ITD_BINS = (6, 256): the bins k_lo = 6 .. k_hi - 1 = 255, about 94 Hz to 4 kHz.  ITD_MAX_LAG = 16
+samples (+-1 ms) and ITD_UPSAMPLE = 8: the lags are tau_i = i / 8 samples for i = -128 .. 128, NL = 257 of them.  With
+Phi_k = CRE_k + j CIM_k and the PHAT weight Phat_k = Phi_k / |Phi_k|, |Phi_k| = sqrt(CRE^2 + CIM^2) (a bin with |Phi_k| = 0 gives
+Phat_k = 0),
+
+  G[i] = (1 / 250) sum_{k = 6}^{255} Re(Phat_k exp(-j 2 pi k i / (1023 . 8)))
+
+Sign: when the right ear is the left ear d samples later, G peaks at tau = +d -- the rule of "Spatial", IPD positive when the right
+ear is late.
+
+Pick.  The ITD is the tau_i that maximises G itself, not |G|; among equal maxima the smallest |i| wins, then the negative one (the
+column reordering of lags_from_corr), so a G of zeros picks 0.  It is reported in microseconds, tau . 62.5: a grid step is 7.8125 us.
+`peak` is that maximum: it lies in [-1, 1] and tends to 1 for one coherent source.  A signal with no bin of the band at |Phi_k| > 0 has
+itd and peak NaN.
+
+Result.  ITD_ORDER = (itd, itd_est, itd_mix, itd_err, itd_err_base, itd_erri, peak, peak_est, peak_mix): itd is the target's,
+itd_err = |itd_est - itd|, itd_err_base = |itd_mix - itd|, itd_erri = itd_err_base - itd_err, all in us.  "itd_whole" [R, 9] and
+"itd_track" [R, M, 9], float64 on the device, and "itd_gcc" [R, 1 + M, 3, 257]: the functions themselves, the whole recording first.
+
+Method.  m2h_score_itd (csrc/score_itd.hip) computes the tile sums straight from the waveforms: the folded transform of "Spectral" on
+the exact fp32 matrix instruction, only the lower 256 bins of it, the four fp32 values of a bin converted to fp64 before they are
+multiplied, no frame or spectrum ever in memory.  m2h_score_windows adds the tiles; m2h_itd_gcc normalises a row's band once, in fp64,
+and adds the bins of every lag in ascending k with twiddles from itd_table(), the index (k i) mod 8184 reduced in integers;
+itd_from_gcc picks, element-wise in torch float64.  The tile sums take 12 KB per recording and second, so recordings go in groups whose
+tile sums stay under `max_corr_bytes` (a single recording above it goes alone); they are independent, so grouping changes no bit.  No
+host synchronisation, and no copy from the host apart from the two tables on a Scorer's first itd call.  Not done: sub-grid
+interpolation of the peak, a caller-chosen band or lag range, an ITD per frequency band.
 
 STOI.  score(..., stoi=True) adds the short-time objective intelligibility of the estimate (Taal et al. 2011) and its extended form
 ESTOI (Jensen & Taal 2016), with the mixture as baseline, per window and over the whole recording; every other number is unchanged by a
@@ -244,6 +289,12 @@ SPECTRAL_BINS, SPECTRAL_FRAMES, SPECTRAL_NFFT = 512, 32, 1023
 SPATIAL_ORDER = ("ild_err", "ipd_err", "ic_err", "ild_err_base", "ipd_err_base", "ic_err_base", "ild_erri", "ipd_erri", "ic_erri")
 SPATIAL_BANDS = 32           # spatial=True: bands of 16 bins, band j = bins 16 j .. 16 j + 15
 SPATIAL_IPD_BANDS = 6        # the phase error is taken over the bands 0 .. 5: bins below 96, about 1.5 kHz
+ITD_ORDER = ("itd", "itd_est", "itd_mix", "itd_err", "itd_err_base", "itd_erri", "peak", "peak_est", "peak_mix")
+ITD_BINS = (6, 256)          # itd=True: the band k_lo <= k < k_hi of GCC-PHAT, about 94 Hz to 4 kHz
+ITD_MAX_LAG = 16             # samples: +-1 ms
+ITD_UPSAMPLE = 8             # lags of 1 / 8 sample: 7.8125 us
+ITD_LAGS = 2 * ITD_MAX_LAG * ITD_UPSAMPLE + 1
+ITD_US_PER_STEP = 1e6 / (16000 * ITD_UPSAMPLE)
 STOI_ORDER = ("stoi", "estoi", "stoi_base", "estoi_base", "stoii", "estoii")
 STOI_TILE = 16000            # stoi=True: a tile is exactly STOI_FS resampled samples
 STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT, STOI_BANDS, STOI_SEGMENT = 10000, 256, 128, 512, 15, 30
@@ -558,6 +609,47 @@ def spatial_from_sums(sums):
     return torch.stack(e + b + [b[k] - e[k] for k in range(3)], dim=-1), torch.stack([ild, ipd, ic], dim=-1)
 
 
+def itd_table():
+    """m2h_itd_gcc's twiddles (include/m2h.h), numpy float64 [8184, 2]: t[q] = (cos, sin)(2 pi q / 8184), 8184 = 1023 . ITD_UPSAMPLE.  The
+    kernel reads entry (k i) mod 8184 for bin k and lag i / 8 samples: the angle is reduced in integers, never as a float."""
+    import numpy as np
+    P = SPECTRAL_NFFT * ITD_UPSAMPLE
+    ang = 2.0 * np.pi * (np.arange(P) % P) / P
+    return np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=-1))
+
+
+def itd_has_band(sums):
+    """sums [..., 256, 2] float64 (CRE, CIM per bin) -> [...] bool: some bin of the band ITD_BINS has |Phi_k| > 0, by m2h_itd_gcc's test"""
+    band = sums[..., ITD_BINS[0]:ITD_BINS[1], :]
+    return (torch.sqrt(band[..., 0] * band[..., 0] + band[..., 1] * band[..., 1]) > 0).any(dim=-1)
+
+
+def itd_from_gcc(g, has=None):
+    """The pick and the nine numbers of "ITD" (module docstring), element-wise in torch float64 on g's device; no synchronisation.
+
+    g [..., 3, 257] float64: GCC-PHAT of the target, the estimate and the mixture, column i + 128 the lag of i / 8 samples;
+    has [..., 3] bool or None: the signal has a bin in the band (False: its itd and peak are NaN) -> [..., 9] in ITD_ORDER.
+    The lag is the one of largest g -- not |g| --; among equal maxima the smallest |i|, then the negative one (the columns reordered as
+    0, -1, +1, -2, +2, ... and the first maximum taken, as in lags_from_corr), so all zeros give 0."""
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float64:
+        raise TypeError("m2h.Scorer: a GCC-PHAT function must be a float64 torch tensor, got %s" % (g.dtype if isinstance(g, torch.Tensor) else type(g).__name__))
+    if g.dim() < 2 or tuple(g.shape[-2:]) != (3, ITD_LAGS):
+        raise ValueError("m2h.Scorer: GCC-PHAT functions hold [3, %d] numbers per row, got a tensor of shape %s" % (ITD_LAGS, tuple(g.shape),))
+    H = ITD_LAGS // 2
+    i = torch.arange(ITD_LAGS, device=g.device, dtype=torch.int64)
+    half = (i + 1) // 2
+    lag = torch.where(i % 2 == 1, -half, half)                                          # 0, -1, +1, -2, +2, ...
+    ordered = g.index_select(-1, lag + H)
+    first = torch.argmax(ordered, dim=-1, keepdim=True)                                 # the first of equal maxima
+    peak = torch.take_along_dim(ordered, first, dim=-1).squeeze(-1)                     # [..., 3]
+    itd = lag[first.squeeze(-1)].to(torch.float64) * ITD_US_PER_STEP
+    if has is not None:
+        nan = torch.full_like(peak, _NAN)
+        itd, peak = torch.where(has, itd, nan), torch.where(has, peak, nan)
+    err, base = (itd[..., 1] - itd[..., 0]).abs(), (itd[..., 2] - itd[..., 0]).abs()
+    return torch.stack([itd[..., 0], itd[..., 1], itd[..., 2], err, base, base - err, peak[..., 0], peak[..., 1], peak[..., 2]], dim=-1)
+
+
 def bss_filters(corr, target):
     """The distortion filters of "BSS" (module docstring) from the whole-recording one-sided correlations, torch float64 on corr's device.
 
@@ -628,6 +720,7 @@ class Scorer:
         self._twiddles = None
         self._dft = None
         self._stoi = None
+        self._itd = None
         self._timing = None          # tools/score_bench.py: a list that receives (stage, event) marks
 
     def _twiddle_table(self):
@@ -641,6 +734,12 @@ class Scorer:
         if self._dft is None:
             self._dft = torch.from_numpy(spectral_table()).to(self.device)
         return self._dft
+
+    def _itd_table(self):
+        """itd_table() on the device, copied from the host once"""
+        if self._itd is None:
+            self._itd = torch.from_numpy(itd_table()).to(self.device)
+        return self._itd
 
     def _stoi_tables(self):
         """(the 16 kHz -> 10 kHz polyphase table [5, 33], the window [256], the 512-point transform's twiddles) on the device, copied from the
@@ -673,7 +772,8 @@ class Scorer:
             ev.record(torch.cuda.current_stream(self.device))
             self._timing.append((stage, ev))
 
-    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spectral=False, spatial=False, stoi=False, bss=None):
+    def _check(self, estimate, references, mixture, target, tile, window, hop, align=None, spectral=False, spatial=False, stoi=False, bss=None,
+               itd=False):
         for name, t in (("estimate", estimate), ("references", references), ("mixture", mixture)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("m2h.Scorer: %s must be a torch tensor, got %s" % (name, type(t).__name__))
@@ -727,7 +827,11 @@ class Scorer:
         plan = score_plan(L, tile, window, hop) if align is None else align_plan(L, align, tile, window, hop)      # raises on tile, window, hop, align
         if spatial and C != 2:
             raise ValueError("m2h.Scorer: spatial=True compares the two ears and needs C = 2 channels, got C = %d" % C)
-        for name, on in (("spatial", spatial), ("spectral", spectral), ("stoi", stoi)):
+        if not isinstance(itd, bool):
+            raise TypeError("m2h.Scorer: itd must be a bool, got %r" % (itd,))
+        if itd and C != 2:
+            raise ValueError("m2h.Scorer: itd=True compares the two ears and needs C = 2 channels, got C = %d" % C)
+        for name, on in (("spatial", spatial), ("spectral", spectral), ("stoi", stoi), ("itd", itd)):
             if on and plan["tile"] != SPECTRAL_TILE:
                 raise ValueError("m2h.Scorer: %s=True needs tile = %d (one second), got %d" % (name, SPECTRAL_TILE, plan["tile"]))
         if bss is not None:
@@ -744,7 +848,7 @@ class Scorer:
         return refs, est, target, plan
 
     def score(self, estimate, references, mixture, target=0, tile=DEFAULT_TILE, window=1, hop=1, align=None, spectral=False, spatial=False,
-              stoi=False, bss=None):
+              stoi=False, bss=None, itd=False):
         """-> {"whole": [R, C, 11], "track": [R, C, M, 11], "active": [R, C, M] bool, "plan": score_plan(...)}; float64 on the device, in
         eval_metrics.METRIC_ORDER; no host synchronisation.  With align=D (an int, the largest lag searched in samples) the estimate is
         aligned to its target first: also "lag": [R, C] int32 and "lag_track": [R, C, M] int32 on the device, and "plan" is
@@ -754,8 +858,11 @@ class Scorer:
         estimate / mixture, band, ILD / IPD / IC).  With stoi=True (tile must be 16000) also "stoi_whole": [R, C, 6] and "stoi_track":
         [R, C, M, 6], float64 in STOI_ORDER, and "stoi_frames": [R, C, 1 + M] int64, the kept-frame count of the whole recording and of
         every window.  With bss=T (an int, the distortion filter's taps, 1 .. 512) also "bss_whole": [R, C, 9] and "bss_track": [R, C, M, 9],
-        float64 in BSS_ORDER.  The module docstring holds the definition."""
-        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial, stoi, bss)
+        float64 in BSS_ORDER.  With itd=True (two channels, tile must be 16000) also "itd_whole": [R, 9] and "itd_track": [R, M, 9], float64
+        in ITD_ORDER (microseconds and peak heights), and the GCC-PHAT functions themselves, "itd_gcc": [R, 1 + M, 3, 257] (the whole
+        recording first; signal target / estimate / mixture; the lags i / 8 samples, i = -128 .. 128).  The module docstring holds the
+        definition."""
+        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial, stoi, bss, itd)
         targets = target                                                                # host integers (bss_filters)
         R, S, C, L = refs.shape
         J, M, tile, window, hop = (plan[k] for k in ("J", "M", "tile", "window", "hop"))
@@ -838,6 +945,26 @@ class Scorer:
                 b9 = bss_from_sums(_whole_then_track(sums, plan), ok[:, :, None])
                 out.update({"bss_whole": b9[:, :, 0], "bss_track": b9[:, :, 1:]})
                 self._mark("bss_metrics")
+            if itd:
+                dft, tab, lag = self._spectral_table(), self._itd_table(), out.get("lag")
+                K = 3 * ITD_BINS[1] * 2
+                step = max(1, self.max_corr_bytes // (J * K * 8))                       # recordings per group
+                gcc, has = [], []
+                for r0 in range(0, R, step):
+                    r1 = min(r0 + step, R)
+                    sums = ops.score_itd(refs[r0:r1], est[r0:r1], mixture[r0:r1], target if isinstance(target, int) else target[r0:r1], dft,
+                                         None if lag is None else lag[r0:r1], D)        # [r, J, 3, 256, 2]
+                    self._mark("score_itd")
+                    sums = _whole_then_track(sums.view(r1 - r0, 1, J, K), plan).view(r1 - r0, 1 + M, 3, ITD_BINS[1], 2)
+                    self._mark("itd_windows")
+                    gcc.append(ops.itd_gcc(sums, tab, *ITD_BINS))                       # [r, 1 + M, 3, 257]
+                    has.append(itd_has_band(sums))
+                    del sums
+                    self._mark("itd_gcc")
+                gcc, has = (gcc[0], has[0]) if len(gcc) == 1 else (torch.cat(gcc), torch.cat(has))
+                nine = itd_from_gcc(gcc, has)
+                out.update({"itd_whole": nine[:, 0], "itd_track": nine[:, 1:], "itd_gcc": gcc})
+                self._mark("itd_metrics")
         out.update({"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan})
         return out
 
@@ -846,6 +973,7 @@ def summarize(result):
     """Host-side summary of Scorer.score's result for one call: {"metrics", "whole": [R][C][11], "track_mean", "track_median": over the
     active windows ([R][C][11], NaN without any), "active_windows": [R][C]} as Python lists (one synchronisation); with spectral=True /
     spatial=True results also the "spectral_*" / "spatial_*" keys (spatial: [R][9], over the windows in which both ears are active); with
+    itd=True results also "itd_metrics", "itd_whole" [R][9] and "itd_track_mean" / "itd_track_median" over the same windows as spatial; with
     stoi=True results also "stoi_metrics", "stoi_whole" [R][C][6], "stoi_track_mean" / "stoi_track_median" over the windows that are not NaN
     and "stoi_frames" [R][C][1 + M]; with bss=T results also "bss_metrics", "bss_whole" [R][C][9] and "bss_track_mean" / "bss_track_median" over
     the active windows."""
@@ -882,6 +1010,15 @@ def summarize(result):
                     pmean[r], pmedian[r] = rows.mean(axis=0), np.median(rows, axis=0)
         out.update({"spatial_metrics": list(SPATIAL_ORDER), "spatial_whole": pw.tolist(), "spatial_track_mean": pmean.tolist(),
                     "spatial_track_median": pmedian.tolist()})
+    if "itd_whole" in result:                                                          # score(..., itd=True): over the windows in which BOTH ears are active
+        iw, it = result["itd_whole"].cpu().numpy(), result["itd_track"].cpu().numpy()
+        imean, imedian = np.full((R, 9), np.nan), np.full((R, 9), np.nan)
+        with np.errstate(all="ignore"):
+            for r in range(R):
+                rows = it[r][active[r].all(axis=0)]
+                if rows.shape[0]:
+                    imean[r], imedian[r] = rows.mean(axis=0), np.median(rows, axis=0)
+        out.update({"itd_metrics": list(ITD_ORDER), "itd_whole": iw.tolist(), "itd_track_mean": imean.tolist(), "itd_track_median": imedian.tolist()})
     if "stoi_whole" in result:                                                         # score(..., stoi=True): over the windows that are not NaN
         tw, tt = result["stoi_whole"].cpu().numpy(), result["stoi_track"].cpu().numpy()
         tmean, tmedian = np.full((R, C, 6), np.nan), np.full((R, C, 6), np.nan)

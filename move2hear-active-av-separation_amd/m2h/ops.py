@@ -839,7 +839,46 @@ def score_spatial(refs, est, mix, target, dft, lag=None, D=0):
     return out
 
 
-STOI_TABLE_SHAPE = (5, 33)                   # the polyphase table of 16 kHz -> 10 kHz (m2h.audio.resample)
+ITD_BINS, ITD_LAGS = 256, 257               # m2h_score_itd's bins 0 .. 255 and m2h_itd_gcc's lags i / 8 samples, i = -128 .. 128 (include/m2h.h)
+ITD_TABLE_SHAPE = (8184, 2)                  # m2h_itd_gcc's twiddles (m2h.audio.score.itd_table)
+
+
+def score_itd(refs, est, mix, target, dft, lag=None, D=0):
+    """Tile cross-spectra of the Scorer's broadband ITD (m2h/audio/score.py, "ITD"): the arguments of score_spatial (BOTH ears of the
+    estimate are read lag[r, 0] samples later) -> [R, J, 3, 256, 2] fp64: signal (target, estimate, mixture), bin, (CRE, CIM) summed over
+    the tile's 32 frames; J = ceil((L - 2 D) / 16000) (include/m2h.h)."""
+    R, S, C, L = _score_signals("score_itd", refs, est, mix)
+    if C != 2:
+        raise RuntimeError("m2h.score_itd: C = %d channels; an interaural delay needs 2" % C)
+    D, J, lptr, tptr, t0 = _score_stft("score_itd", refs, dft, target, lag, D)
+    out = torch.empty((R, J, 3, ITD_BINS, 2), device=refs.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(refs.device):
+        _lib.check(lib.m2h_score_itd(*_score_args(refs, est, mix), tptr, t0, _ptr(dft), _ptr(out), R, S, L, lptr, D, _stream(refs)), "m2h_score_itd")
+    return out
+
+
+def itd_gcc(sums, table, k_lo, k_hi):
+    """GCC-PHAT of every row of cross-spectra (m2h/audio/score.py, "ITD"): sums [..., 256, 2] fp64 contiguous on the device (score_itd's
+    tile sums, or sums of tiles), table: m2h.audio.score.itd_table() on the device, the band k_lo <= k < k_hi
+    -> [..., 257] fp64, column i + 128 the function at the lag of i / 8 samples (include/m2h.h)."""
+    _chk(sums, "itd_gcc(sums)", torch.float64)
+    _chk(table, "itd_gcc(table)", torch.float64)
+    if sums.dim() < 2 or tuple(sums.shape[-2:]) != (ITD_BINS, 2) or sums.numel() == 0:
+        raise RuntimeError("m2h.itd_gcc: sums must be [..., %d, 2] float64 with at least one row, got %s" % (ITD_BINS, tuple(sums.shape)))
+    if tuple(table.shape) != ITD_TABLE_SHAPE or table.device != sums.device:
+        raise RuntimeError("m2h.itd_gcc: table must be the %s table on %s" % (list(ITD_TABLE_SHAPE), sums.device))
+    k_lo, k_hi = int(k_lo), int(k_hi)
+    if not 0 <= k_lo < k_hi <= ITD_BINS:
+        raise RuntimeError("m2h.itd_gcc: bins k_lo = %d .. k_hi = %d; 0 <= k_lo < k_hi <= %d is required" % (k_lo, k_hi, ITD_BINS))
+    out = torch.empty(tuple(sums.shape[:-2]) + (ITD_LAGS,), device=sums.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(sums.device):
+        _lib.check(lib.m2h_itd_gcc(_ptr(sums), _ptr(table), _ptr(out), sums.numel() // (ITD_BINS * 2), k_lo, k_hi, _stream(sums)), "m2h_itd_gcc")
+    return out
+
+
+STOI_TABLE_SHAPE = (5, 33)                  # the polyphase table of 16 kHz -> 10 kHz (m2h.audio.resample)
 
 
 def stoi_resample(refs, est, mix, target, table, lag=None, D=0):

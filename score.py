@@ -2,7 +2,7 @@
 """Score a separated recording of any length against its ground truth:
 
     python score.py --estimate out.wav --mixture mix.wav --reference target.wav [--reference other.wav ...] [--window W --hop H]
-                    [--align D] [--spectral] [--spatial] [--stoi] [--bss [T]] [--json scores.json]
+                    [--align D] [--spectral] [--spatial] [--itd] [--stoi] [--bss [T]] [--json scores.json]
 
 ``--reference``: the sources as they are in the mixture, at most six; the FIRST one is the target the estimate is scored against, the
 others are the interferers (they enter SI-SIR and SI-SAR).  ``render.py --out-target / --out-image`` writes such files.  ``--mixture``:
@@ -30,6 +30,13 @@ target's, per window and over the whole recording, the same for the mixture as t
 (m2h/audio/score.py, "Spatial"), as rows under the table and as ``spatial_*`` keys in the JSON; the JSON also holds the cues
 themselves per window, signal (target, estimate, mixture) and 250 Hz band (``spatial_cues``).  With ``--align`` both ears of the
 estimate are read at the left ear's lag.
+
+``--itd`` (two-channel files only) adds the broadband interaural time difference of the target, the estimate and the mixture in
+microseconds -- the peak of the PHAT-weighted cross-correlation of the two ears between 94 Hz and 4 kHz, searched over +-1 ms in steps
+of 1 / 8 sample (7.8125 us), positive when the right ear is late -- with the estimate's and the mixture's distance from the target's
+and the improvement (m2h/audio/score.py, "ITD"), per window and over the whole recording, as rows under the table and as ``itd_*``
+keys in the JSON; the JSON also holds the correlation functions themselves (``itd_gcc``, the whole recording first).  With ``--align``
+both ears of the estimate are read at the left ear's lag.
 
 ``--stoi`` adds the intelligibility figures STOI and ESTOI of the estimate against the clean target (m2h/audio/score.py, "STOI"), the
 same for the mixture as the estimate, and the two improvements, for the same whole recording and the same windows, as rows under the
@@ -76,6 +83,7 @@ def main():
     parser.add_argument("--align", type=int, default=None, metavar="D", help="align the estimate to the target first: the largest lag searched, in samples (1 .. 8192)")
     parser.add_argument("--spectral", action="store_true", help="also the STFT distance per window and over the whole recording")
     parser.add_argument("--spatial", action="store_true", help="also the interaural cue errors (ILD, IPD, IC) per window and over the whole recording; two-channel files")
+    parser.add_argument("--itd", action="store_true", help="also the broadband ITD in microseconds (GCC-PHAT) per window and over the whole recording; two-channel files")
     parser.add_argument("--stoi", action="store_true", help="also STOI and ESTOI per window and over the whole recording")
     parser.add_argument("--bss", type=int, nargs="?", const=512, default=None, metavar="T",
                         help="also BSS-eval SDR, SIR and SAR through a distortion filter of T taps (default 512)")
@@ -93,6 +101,8 @@ def main():
                              % (args.estimate, est.shape[0], "" if est.shape[0] == 1 else "s", path, x.shape[0]))
     if args.spatial and est.shape[0] != 2:
         raise SystemExit("score.py: --spatial compares the two ears: two channels are needed, and %s has %d" % (args.estimate, est.shape[0]))
+    if args.itd and est.shape[0] != 2:
+        raise SystemExit("score.py: --itd compares the two ears: two channels are needed, and %s has %d" % (args.estimate, est.shape[0]))
     for path, x in [(args.mixture, mix)] + list(zip(args.reference, refs)):
         if x.shape[1] != est.shape[1]:
             raise SystemExit("score.py: %s is %d samples long and %s is %d; equal lengths are required (with --align too)"
@@ -105,7 +115,7 @@ def main():
         res = Scorer(dev).score(torch.from_numpy(np.ascontiguousarray(est)).to(dev)[None], torch.from_numpy(np.stack(refs)).to(dev)[None],
                                 torch.from_numpy(np.ascontiguousarray(mix)).to(dev)[None], target=0, window=args.window, hop=args.hop, align=args.align,
                                 spectral=args.spectral, **({"spatial": True} if args.spatial else {}), **({"stoi": True} if args.stoi else {}),
-                                **({"bss": args.bss} if args.bss is not None else {}))
+                                **({"bss": args.bss} if args.bss is not None else {}), **({"itd": True} if args.itd else {}))
     except (ValueError, TypeError) as e:
         raise SystemExit("score.py: %s" % e)
     s = summarize(res)
@@ -134,6 +144,10 @@ def main():
         print("%-8s %-23s" % ("spatial", "") + " ".join("%20s" % m for m in s["spatial_metrics"]))
         for label, key in (("spatial whole", "spatial_whole"), ("spatial window mean", "spatial_track_mean"), ("spatial window median", "spatial_track_median")):
             print("%-8s %-23s" % ("binaural", label) + " ".join("%20.12e" % v for v in s[key][0]))
+    if args.itd:
+        print("%-8s %-23s" % ("itd us", "") + " ".join("%20s" % m for m in s["itd_metrics"]))
+        for label, key in (("itd whole", "itd_whole"), ("itd window mean", "itd_track_mean"), ("itd window median", "itd_track_median")):
+            print("%-8s %-23s" % ("binaural", label) + " ".join("%20.12e" % v for v in s[key][0]))
     if args.stoi:
         print("%-8s %-23s" % ("stoi", "") + " ".join("%20s" % m for m in s["stoi_metrics"]))
         for c in range(C):
@@ -158,6 +172,10 @@ def main():
             out.update({"spatial_metrics": s["spatial_metrics"], "spatial_whole": s["spatial_whole"][0],
                         "spatial_track": res["spatial_track"][0].cpu().numpy().tolist(), "spatial_track_mean": s["spatial_track_mean"][0],
                         "spatial_track_median": s["spatial_track_median"][0], "spatial_cues": res["spatial_cues"][0].cpu().numpy().tolist()})
+        if args.itd:
+            out.update({"itd_metrics": s["itd_metrics"], "itd_whole": s["itd_whole"][0], "itd_track": res["itd_track"][0].cpu().numpy().tolist(),
+                        "itd_track_mean": s["itd_track_mean"][0], "itd_track_median": s["itd_track_median"][0],
+                        "itd_gcc": res["itd_gcc"][0].cpu().numpy().tolist()})
         if args.stoi:
             out.update({"stoi_metrics": s["stoi_metrics"], "stoi_whole": s["stoi_whole"][0], "stoi_track": res["stoi_track"][0].cpu().numpy().tolist(),
                         "stoi_track_mean": s["stoi_track_mean"][0], "stoi_track_median": s["stoi_track_median"][0], "stoi_frames": s["stoi_frames"][0]})

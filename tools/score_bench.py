@@ -9,6 +9,8 @@
     python tools/score_bench.py --case 16x3x600c1 --spectral         # one case of it in this process
     python tools/score_bench.py --spatial --out profiles/score_spatial_bench.json                   # the interaural cues, the two-channel cases
     python tools/score_bench.py --case 16x3x600c2 --spatial          # one case of it in this process
+    python tools/score_bench.py --itd --out profiles/score_itd_bench.json                           # the broadband ITD, the two-channel cases
+    python tools/score_bench.py --case 16x3x600c2 --itd              # one case of it in this process
     python tools/score_bench.py --stoi --out profiles/score_stoi_bench.json                         # STOI / ESTOI, every case
     python tools/score_bench.py --case 1x2x60c2 --stoi               # one case of it in this process
     python tools/score_bench.py --bss --out profiles/score_bss_bench.json                           # BSS-eval SDR / SIR / SAR at 512 taps, every case
@@ -49,6 +51,15 @@ only: the cues compare the ears, a mono case has none):
                           spectra stored) and torch float64 reductions, before and after; its largest difference from the kernel's sums,
                           relative to the band's energies sqrt(PL PR) (a cross term may be near 0), is recorded
   extra_ms_in_score       what spatial=True adds to one Scorer.score (launch, two m2h_score_windows, spatial_from_sums)
+With --itd (Scorer.score(..., itd=True); every launch timed alone with HIP events; two-channel cases only):
+  itd_ms                  m2h_score_itd, one launch, twice: the [3, 256, 2] fp64 cross-spectra of every (recording, second)
+  spatial_ms, itd_over_spatial   m2h_score_spatial on the same tensors in the same run, before and after (the same staging, twice the MFMAs)
+  windows_ms, gcc_ms      the two m2h_score_windows over the tile sums, and m2h_itd_gcc on the whole recordings' and the windows' rows
+  stored_gcc_ms           the same definition from the existing pieces in the same run, before and after: m2h_stft_frames and the fp32 GEMM
+                          of m2h.audio.stft.STFT on the six signals' seconds (frames and spectra stored), torch float64 products and
+                          sums, and GCC-PHAT as a torch float64 matmul against the cos / sin matrices, one recording at a time; the
+                          largest difference of its functions from the kernels' is recorded
+  extra_ms_in_score       what itd=True adds to one Scorer.score (the launches, itd_has_band, itd_from_gcc)
 With --stoi (Scorer.score(..., stoi=True): the whole recording and every one-second window are ranges of the same launches):
   resample_ms, ranges_ms  m2h_stoi_resample and the five launches of m2h_stoi_ranges, each timed alone with HIP events, twice
   bytes                   what each stage has to move at least (every sample, frame slot and envelope counted once), from the shapes
@@ -321,6 +332,104 @@ def run_spatial_case(case):
            "stored_spectrum_ms": [before, after], "stored_spectrum_reps": n_stored, "stored_over_kernel": 0.5 * (before + after) / (0.5 * (ms + ms2)),
            "score_ms": plain, "score_spatial_ms": full, "extra_ms_in_score": full - plain, "audio_s_per_s": R * seconds / (full * 1e-3),
            "kernel_vs_stored_max_rel_to_band_energy": diff, "ild_err_whole_db": float(res0["spatial_whole"][0, 0])}
+    print(json.dumps(res))
+    return res
+
+
+def stored_spectrum_gcc(stft, sig, cs):
+    """[R, 1 + J, 3, 257] float64, the ITD's GCC-PHAT functions (whole recording, then per-second windows) from the existing pieces:
+    sig [R, 3, 2, L] (L a multiple of a second) -> frames and spectra of every second stored by m2h_stft_frames and the fp32 GEMM of `stft`,
+    torch float64 products and sums, the PHAT weight, and a float64 matmul against cs = (cos, sin) [250, 257]; one recording at a time"""
+    import torch
+    from m2h import _lib, ops
+    from m2h.audio.score import ITD_BINS
+    lib = _lib.load()
+    R, _, _, L = sig.shape
+    J, T, nb = L // SEG, 32, stft.nb
+    out = []
+    for r in range(R):
+        wave = sig[r].reshape(6 * J, SEG).contiguous()
+        frames = torch.empty((6 * J * T, stft.ld), device=sig.device)
+        _lib.check(lib.m2h_stft_frames(ops._ptr(wave), ops._ptr(stft.window), ops._ptr(frames), 6 * J, SEG, T, stft.n_fft, stft.hop, stft.ld,
+                                       ops._stream(wave)), "m2h_stft_frames")
+        spec = ops.linear(frames, stft.W, None, name="stft.dft").view(3, 2, J, T, stft.ld)
+        re, im = spec[..., ITD_BINS[0]:ITD_BINS[1]].double(), spec[..., nb + ITD_BINS[0]:nb + ITD_BINS[1]].double()
+        lr, li, rr, ri = re[:, 0], im[:, 0], re[:, 1], im[:, 1]                              # [3, J, T, 250]
+        cre, cim = (lr * rr + li * ri).sum(dim=2), (li * rr - lr * ri).sum(dim=2)            # [3, J, 250]
+        cre, cim = torch.cat([cre.sum(dim=1, keepdim=True), cre], dim=1), torch.cat([cim.sum(dim=1, keepdim=True), cim], dim=1)
+        mag = torch.sqrt(cre * cre + cim * cim)
+        safe = torch.where(mag > 0, mag, torch.ones_like(mag))
+        g = (torch.where(mag > 0, cre / safe, torch.zeros_like(cre)) @ cs[0] + torch.where(mag > 0, cim / safe, torch.zeros_like(cim)) @ cs[1])
+        out.append((g / float(ITD_BINS[1] - ITD_BINS[0])).transpose(0, 1))                   # [1 + J, 3, 257]
+    return torch.stack(out)
+
+
+def run_itd_case(case):
+    import numpy as np
+    import torch
+    from m2h import ops
+    from m2h.audio.score import ITD_BINS, ITD_LAGS, ITD_UPSAMPLE, Scorer
+    from m2h.audio.stft import STFT
+    if not torch.cuda.is_available():
+        raise SystemExit("score_bench: no GPU; this measurement has no CPU path")
+    R, S, seconds, C, reps = CASES[case]
+    if C != 2:
+        raise SystemExit("score_bench: --itd compares the two ears; case %s is mono" % case)
+    dev = torch.device("cuda", 0)
+    L, J = seconds * SEG, seconds
+    g = torch.Generator(device=dev).manual_seed(7)
+    refs = torch.randn((R, S, C, L), device=dev, generator=g) * 0.1 + 0.01
+    refs[:, :, 1, 5:] = 0.8 * refs[:, :, 0, :L - 5] + 0.1 * refs[:, :, 1, 5:]            # every source's right ear mostly its left one, 5 samples later
+    mix = torch.stack([refs[:, :, 0].mean(1), refs[:, :, C - 1].mean(1)], dim=1) + 0.02 * torch.randn((R, 2, L), device=dev, generator=g)
+    est = 0.8 * refs[:, 0] + 0.03 * torch.randn((R, C, L), device=dev, generator=g)
+    sc, stft = Scorer(dev), STFT(dev)
+    table, tab = sc._spectral_table(), sc._itd_table()
+    k, i = np.arange(*ITD_BINS), np.arange(ITD_LAGS) - ITD_LAGS // 2
+    ang = 2.0 * np.pi * ((k[:, None] * i[None, :]) % (1023 * ITD_UPSAMPLE)) / (1023 * ITD_UPSAMPLE)
+    cs = torch.from_numpy(np.stack([np.cos(ang), np.sin(ang)])).to(dev)
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    kernel = lambda: ops.score_itd(refs, est, mix, 0, table)                            # noqa: E731
+    yardstick = lambda: ops.score_spatial(refs, est, mix, 0, table)                     # noqa: E731
+    stored = lambda: stored_spectrum_gcc(stft, torch.stack([refs[:, 0], est, mix], dim=1), cs)   # noqa: E731
+    res0 = sc.score(est, refs, mix, itd=True)                                           # warm-up of every shape
+    tiles = kernel().view(R, 1, J, 1536)
+    windows = lambda: torch.cat([ops.score_windows(tiles, 1, J, 1), ops.score_windows(tiles, J, 1, 1)], dim=2)   # noqa: E731
+    ws = windows().view(R, 1 + J, 3, 256, 2)
+    gcc = lambda: ops.itd_gcc(ws, tab, *ITD_BINS)                                       # noqa: E731
+    want = stored()
+    diff = float((res0["itd_gcc"] - want).abs().max())
+    del want
+    yardstick()
+    torch.cuda.synchronize()
+    n_stored = max(1, reps // 10)
+    before = timed(stored, n_stored)
+    spat = timed(yardstick, reps)
+    ms = timed(kernel, reps)
+    win_ms = timed(windows, reps)
+    gcc_ms = timed(gcc, reps)
+    plain = timed(lambda: sc.score(est, refs, mix), reps)
+    full = timed(lambda: sc.score(est, refs, mix, itd=True), reps)
+    after = timed(stored, n_stored)
+    ms2 = timed(kernel, reps)
+    spat2 = timed(yardstick, reps)
+    flops = R * C * seconds * SPECTRAL_FLOPS_PER_TILE // 2                              # half the bins
+    res = {"case": case, "itd": True, "R": R, "S": S, "C": C, "audio_seconds_per_recording": seconds, "reps": reps, "workgroups": 3 * R * seconds,
+           "itd_ms": [ms, ms2], "spatial_ms": [spat, spat2], "itd_over_spatial": (ms + ms2) / (spat + spat2), "flops_unfolded": flops,
+           "flops_per_s_unfolded": flops / (min(ms, ms2) * 1e-3), "share_of_fp32_matrix_peak": flops / (min(ms, ms2) * 1e-3) / FP32_MATRIX_PEAK,
+           "windows_ms": win_ms, "gcc_ms": gcc_ms, "gcc_rows": R * (1 + J) * 3, "tile_sum_bytes": R * J * 1536 * 8,
+           "stored_gcc_ms": [before, after], "stored_gcc_reps": n_stored, "stored_over_kernels": 0.5 * (before + after) / (0.5 * (ms + ms2) + win_ms + gcc_ms),
+           "score_ms": plain, "score_itd_ms": full, "extra_ms_in_score": full - plain, "audio_s_per_s": R * seconds / (full * 1e-3),
+           "kernels_vs_stored_max_abs_gcc": diff, "itd_whole_us": [float(v) for v in res0["itd_whole"][0, :3]], "peak_whole": [float(v) for v in res0["itd_whole"][0, 6:]]}
     print(json.dumps(res))
     return res
 
@@ -645,18 +754,21 @@ def main():
     ap.add_argument("--align", type=int, action="append", default=None, metavar="D", help="measure the aligned scorer at this largest lag (repeat)")
     ap.add_argument("--spectral", action="store_true", help="measure the STFT distance's launch (Scorer.score(..., spectral=True))")
     ap.add_argument("--spatial", action="store_true", help="measure the interaural cues' launch (Scorer.score(..., spatial=True)); two-channel cases")
+    ap.add_argument("--itd", action="store_true", help="measure the broadband ITD's launches (Scorer.score(..., itd=True)); two-channel cases")
     ap.add_argument("--stoi", action="store_true", help="measure STOI / ESTOI (Scorer.score(..., stoi=True)) against its composition from torch")
     ap.add_argument("--bss", action="store_true", help="measure BSS-eval SDR / SIR / SAR at 512 taps (Scorer.score(..., bss=512)) against its composition from torch")
     ap.add_argument("--out", default=None, help="driver mode: JSON file for all cases")
     ap.add_argument("--timeout", type=int, default=120, help="driver mode: seconds per case")
     args = ap.parse_args()
-    if (args.spectral or args.spatial or args.stoi or args.bss) and args.align or args.spectral + args.spatial + args.stoi + args.bss > 1:
-        raise SystemExit("score_bench: --spectral, --spatial, --stoi, --bss and --align are measured separately")
+    if (args.spectral or args.spatial or args.itd or args.stoi or args.bss) and args.align or args.spectral + args.spatial + args.itd + args.stoi + args.bss > 1:
+        raise SystemExit("score_bench: --spectral, --spatial, --itd, --stoi, --bss and --align are measured separately")
     if args.case is not None:
         if args.bss:
             run_bss_case(args.case)
         elif args.stoi:
             run_stoi_case(args.case)
+        elif args.itd:
+            run_itd_case(args.case)
         elif args.spatial:
             run_spatial_case(args.case)
         elif args.spectral:
@@ -668,9 +780,9 @@ def main():
             run_case(args.case)
         return
     results = []
-    for case, D in [(case, D) for D in (args.align or [None]) for case in ORDER if CASES[case][3] == 2 or not args.spatial]:
+    for case, D in [(case, D) for D in (args.align or [None]) for case in ORDER if CASES[case][3] == 2 or not (args.spatial or args.itd)]:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--case", case] + ([] if D is None else ["--align", str(D)]) + \
-            (["--spectral"] if args.spectral else []) + (["--spatial"] if args.spatial else []) + (["--stoi"] if args.stoi else []) + (["--bss"] if args.bss else [])
+            (["--spectral"] if args.spectral else []) + (["--spatial"] if args.spatial else []) + (["--itd"] if args.itd else []) + (["--stoi"] if args.stoi else []) + (["--bss"] if args.bss else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             print(r.stdout[-4000:])
@@ -681,7 +793,7 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/score_bench.py", "device": "MI355X (gfx950)", "copy_rate_bytes_per_s": COPY_RATE,
-                       **({"fp32_matrix_peak_flops_per_s": FP32_MATRIX_PEAK} if args.spectral or args.spatial else {}),
+                       **({"fp32_matrix_peak_flops_per_s": FP32_MATRIX_PEAK} if args.spectral or args.spatial or args.itd else {}),
                        **({"fp64_vector_peak_flops_per_s": FP64_VECTOR_PEAK} if args.bss else {}), "results": results}, f, indent=1)
             f.write("\n")
 
