@@ -914,6 +914,22 @@ def load_packed(x, M, drop_odd=False):
     return pad[..., 0::2].copy(), pad[..., 1::2].copy()
 
 
+def rfft_unpack(tr, ti, zkr, zki, zmr, zmi):
+    """fft_lds.h rfft_unpack of the pair (k, M-k), t = tw[k] -> (E, T O): S[k] = E + T O, conj(S[M-k]) = E - T O."""
+    half = F32(0.5)
+    er, ei = half * (zkr + zmr), half * (zki - zmi)
+    dr, di = half * (zkr - zmr), half * (zki + zmi)
+    return (er, ei) + _cmul(tr, ti, di, -dr)
+
+
+def rfft_repack(tr, ti, ykr, yki, ymr, ymi):
+    """fft_lds.h rfft_repack of Y[k] and conj(Y[M-k]) -> (Z'[k], Z'[M-k]) for the inverse packed transform."""
+    half = F32(0.5)
+    e2r, e2i = half * (ykr + ymr), half * (yki + ymi)
+    o2r, o2i = _cmulc(half * (ykr - ymr), half * (yki - ymi), tr, ti)
+    return e2r - o2i, e2i + o2r, e2r + o2i, -e2i + o2r
+
+
 def fc_fp32(row, inp, mutant=None):
     logm = row["log2n"] - 1
     M = 1 << logm
@@ -939,17 +955,11 @@ def fc_fp32(row, inp, mutant=None):
     ik, im = bit_rev(k, logm), bit_rev(M - k, logm)
     tr, ti = tw[k, 0], tw[k, 1]
 
-    def unpack(zkr, zki, zmr, zmi):
-        er, ei = half * (zkr + zmr), half * (zki - zmi)
-        dr, di = half * (zkr - zmr), half * (zki + zmi)
-        return (er, ei) + _cmul(tr, ti, di, -dr)
-    exr, exi, oxr, oxi = unpack(xr[..., ik], xi[..., ik], xr[..., im], xi[..., im])
-    ehr, ehi, ohr, ohi = unpack(hr[..., ik], hi[..., ik], hr[..., im], hi[..., im])
+    exr, exi, oxr, oxi = rfft_unpack(tr, ti, xr[..., ik], xi[..., ik], xr[..., im], xi[..., im])
+    ehr, ehi, ohr, ohi = rfft_unpack(tr, ti, hr[..., ik], hi[..., ik], hr[..., im], hi[..., im])
     ykr, yki = _cmul(exr + oxr, exi + oxi, ehr + ohr, ehi + ohi)
     ymr, ymi = _cmul(exr - oxr, exi - oxi, ehr - ohr, ehi - ohi)
-    e2r, e2i = half * (ykr + ymr), half * (yki + ymi)
-    o2r, o2i = _cmulc(half * (ykr - ymr), half * (yki - ymi), tr, ti)
-    zkr, zki, zmr, zmi = e2r - o2i, e2i + o2r, e2r + o2i, -e2i + o2r
+    zkr, zki, zmr, zmi = rfft_repack(tr, ti, ykr, yki, ymr, ymi)
     last = -1 if mutant == FC_MUTANTS[2] else None
     zr[..., im[:-1]], zi[..., im[:-1]] = zmr[..., :-1], zmi[..., :-1]
     zr[..., ik[:last]], zi[..., ik[:last]] = zkr[..., :last], zki[..., :last]
