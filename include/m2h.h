@@ -846,6 +846,30 @@ int m2h_score_itd(const float* refs, long long refs_sr, long long refs_ss, long 
                   int R, int S, long long L, const int* lag, int D, m2h_stream stream);
 int m2h_itd_gcc(const double* sums, const double* table, double* gcc, long long rows, int k_lo, int k_hi, m2h_stream stream);
 
+/* RoomAcoustics (m2h/audio/acoustics.py holds the definition; csrc/rir_acoustics.hip).  rirs [Q][Lr][2] fp32, contiguous, the ears
+ * interleaved; 1 <= Lr <= 256000.  No entry reads outside the Q rows, none uses atomics: the bits of an RIR depend on the RIR alone.
+ * m2h_rir_onset: per RIR and ear e the first index of max |h| -> peak [Q][2] int32 (0 for a silent ear); the smaller over the non-silent
+ *   ears of the first n with |h[n][e]| >= 0.1 max |h[.][e]| (compared in fp64) -> onset [Q] int32 (0 for a silent RIR);
+ *   sums [Q][2][2] fp64: D = sum of h^2 over |n - peak_e| <= 40 clipped to the row, T = sum of h^2 over the row (the product taken
+ *   after widening); drr [Q][2] fp64 = 10 log10(D / (T - D)), NaN for a silent ear.
+ * m2h_rir_band_energy: onset [Q] int32 and sums [Q][2][2] fp64 ON THE DEVICE, as m2h_rir_onset wrote them (onset is clamped to [0, Lr) before
+ *   use; an ear with T = 0 is silent and stays so in every band: the ears share a transform, whose rounding would leak one into the other); masks [6][16384] fp32: the real 16384-point DFT
+ *   of each octave band's zero-phase filter, in natural bin order; twiddles: the Auralizer's [2][16384][2] table, of which the stage-
+ *   ordered half is read.  Band 0 is the RIR itself, band b >= 1 the circular convolution with masks[b - 1] over segments that start at
+ *   onset - 2064 + 12256 g, of which the wrap-free samples are used.
+ *   energy [Q][2][7][nbs] fp64, nbs = ceil(Lr / 16): bin i = sum over t < 16 of y_b[onset + 16 i + t]^2 at the samples < Lr (0 where none is left);
+ *   iacf [Q][7][35] fp64: k < 33: sum over t in [onset, onset + 1280) of y_b[t][L] y_b[t + k - 16][R]; 33: sum of y_b[t][L]^2; 34: of y_b[t][R]^2;
+ *   iacc [Q][7][2] fp64: max over k of |iacf_k| / sqrt(iacf_33 iacf_34) and the lag k - 16 it is taken at, the lowest on ties; NaN, NaN
+ *   where the denominator is not positive.
+ * m2h_rir_decay: bins [rows][nb] fp64 (rows of m2h_rir_band_energy's energy, or any other) -> params [rows][7] fp64: EDT, T20, T30 (s),
+ *   C50, C80 (dB), D50, centre time (s) of a row, a bin taken as 1 ms.  NaN where a regression range holds fewer than two bins.
+ * Each returns a negative status and launches nothing for a null pointer, Lr outside 1 .. 256000 (nb outside 1 .. 16000), Q or rows < 1,
+ * more than 65535 RIRs in one m2h_rir_band_energy launch, or an fp64 buffer (or the twiddles) not 8-byte aligned. */
+int m2h_rir_onset(const float* rirs, int* onset, int* peak, double* sums, double* drr, int Q, int Lr, m2h_stream stream);
+int m2h_rir_band_energy(const float* rirs, const int* onset, const double* sums, const float* masks, const float* twiddles, double* energy,
+                        double* iacf, double* iacc, int Q, int Lr, m2h_stream stream);
+int m2h_rir_decay(const double* bins, double* params, long long rows, int nb, m2h_stream stream);
+
 /* Scorer, STOI and ESTOI (m2h/audio/score.py, "STOI"; csrc/score_stoi.hip).
  * m2h_stoi_resample: for (r, c) the three signals of m2h_score_spectral over the region [D, L - D) -- 0: the clean signal
  * refs[r][target_r][c][D + t], 1: the estimate est[r][c][D + lag[r * C + c] + t], 2: the baseline mix[r][c][D + t] for C = 2,

@@ -878,6 +878,71 @@ def itd_gcc(sums, table, k_lo, k_hi):
     return out
 
 
+RIR_MAX_TAPS, RIR_BIN, RIR_BANDS, RIR_IACF, RIR_PARAMS = 256000, 16, 7, 35, 7      # csrc/rir_acoustics.hip
+RIR_MASKS_SHAPE = (6, 16384)                # the octave bands' filter spectra (m2h.audio.acoustics.octave_masks)
+RIR_MAX_BATCH = 65535                       # RIRs of one m2h_rir_band_energy launch
+
+
+def _rir_rows(name, rirs):
+    _chk(rirs, name + "(rirs)")
+    if rirs.dim() != 3 or rirs.shape[-1] != 2 or rirs.shape[0] < 1 or not 1 <= rirs.shape[1] <= RIR_MAX_TAPS:
+        raise RuntimeError("m2h.%s: rirs must be [Q >= 1, 1 <= Lr <= %d, 2], got %s" % (name, RIR_MAX_TAPS, tuple(rirs.shape)))
+    return int(rirs.shape[0]), int(rirs.shape[1])
+
+
+def rir_onset(rirs):
+    """Onset and direct sound of RoomAcoustics (m2h/audio/acoustics.py): rirs [Q, Lr, 2] fp32 contiguous on the device ->
+    onset [Q] int32, peak [Q, 2] int32, sums [Q, 2, 2] fp64 (D, T per ear), drr [Q, 2] fp64 (include/m2h.h)."""
+    Q, Lr = _rir_rows("rir_onset", rirs)
+    dev = rirs.device
+    onset, peak = torch.empty((Q,), device=dev, dtype=torch.int32), torch.empty((Q, 2), device=dev, dtype=torch.int32)
+    sums, drr = torch.empty((Q, 2, 2), device=dev, dtype=torch.float64), torch.empty((Q, 2), device=dev, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.m2h_rir_onset(_ptr(rirs), _ptr(onset), _ptr(peak), _ptr(sums), _ptr(drr), Q, Lr, _stream(rirs)), "m2h_rir_onset")
+    return onset, peak, sums, drr
+
+
+def rir_band_energy(rirs, onset, sums, masks, twiddles):
+    """Band energies in 1 ms bins from the onset and the early IACF sums (m2h/audio/acoustics.py): rirs as for rir_onset, onset [Q] int32
+    and sums [Q, 2, 2] fp64 as rir_onset returned them, masks: acoustics.octave_masks() and twiddles: the [2, 16384, 2] table, both on the device ->
+    energy [Q, 2, 7, ceil(Lr / 16)], iacf [Q, 7, 35], iacc [Q, 7, 2], all fp64 (include/m2h.h)."""
+    Q, Lr = _rir_rows("rir_band_energy", rirs)
+    dev = rirs.device
+    _chk(onset, "rir_band_energy(onset)", torch.int32)
+    _chk(sums, "rir_band_energy(sums)", torch.float64)
+    _chk(masks, "rir_band_energy(masks)")
+    _chk(twiddles, "rir_band_energy(twiddles)")
+    if tuple(onset.shape) != (Q,) or onset.device != dev or tuple(sums.shape) != (Q, 2, 2) or sums.device != dev:
+        raise RuntimeError("m2h.rir_band_energy: onset must be [%d] int32 and sums [%d, 2, 2] float64 on %s, got %s and %s" % (Q, Q, dev, tuple(onset.shape), tuple(sums.shape)))
+    if tuple(masks.shape) != RIR_MASKS_SHAPE or masks.device != dev or tuple(twiddles.shape) != (2, 16384, 2) or twiddles.device != dev:
+        raise RuntimeError("m2h.rir_band_energy: masks must be the %s table and twiddles the [2, 16384, 2] table on %s" % (list(RIR_MASKS_SHAPE), dev))
+    if Q > RIR_MAX_BATCH:
+        raise RuntimeError("m2h.rir_band_energy: Q = %d RIRs; one launch takes at most %d" % (Q, RIR_MAX_BATCH))
+    energy = torch.empty((Q, 2, RIR_BANDS, -(-Lr // RIR_BIN)), device=dev, dtype=torch.float64)
+    iacf = torch.empty((Q, RIR_BANDS, RIR_IACF), device=dev, dtype=torch.float64)
+    iacc = torch.empty((Q, RIR_BANDS, 2), device=dev, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.m2h_rir_band_energy(_ptr(rirs), _ptr(onset), _ptr(sums), _ptr(masks), _ptr(twiddles), _ptr(energy), _ptr(iacf), _ptr(iacc), Q, Lr,
+                                           _stream(rirs)), "m2h_rir_band_energy")
+    return energy, iacf, iacc
+
+
+def rir_decay(bins):
+    """Decay times, clarity, definition and centre time of every row of 1 ms energy bins (m2h/audio/acoustics.py): bins [..., nb] fp64
+    contiguous on the device, 1 <= nb <= 16000 -> [..., 7] fp64 in ACOUSTIC_ORDER (include/m2h.h)."""
+    _chk(bins, "rir_decay(bins)", torch.float64)
+    if bins.dim() < 1 or bins.numel() == 0 or bins.shape[-1] > RIR_MAX_TAPS // RIR_BIN:
+        raise RuntimeError("m2h.rir_decay: bins must be [..., 1 <= nb <= %d] float64 with at least one row, got %s" % (RIR_MAX_TAPS // RIR_BIN, tuple(bins.shape)))
+    nb = int(bins.shape[-1])
+    out = torch.empty(tuple(bins.shape[:-1]) + (RIR_PARAMS,), device=bins.device, dtype=torch.float64)
+    lib = _lib.load()
+    with torch.cuda.device(bins.device):
+        _lib.check(lib.m2h_rir_decay(_ptr(bins), _ptr(out), bins.numel() // nb, nb, _stream(bins)), "m2h_rir_decay")
+    return out
+
+
 STOI_TABLE_SHAPE = (5, 33)                  # the polyphase table of 16 kHz -> 10 kHz (m2h.audio.resample)
 
 
