@@ -870,6 +870,18 @@ int m2h_rir_band_energy(const float* rirs, const int* onset, const double* sums,
                         double* iacf, double* iacc, int Q, int Lr, m2h_stream stream);
 int m2h_rir_decay(const double* bins, double* params, long long rows, int nb, m2h_stream stream);
 
+/* RoomSimulator (m2h/audio/room.py holds the definition; csrc/room_sim.hip): binaural RIRs of shoebox rooms by the image-source method.
+ * params [Q][16] fp64, per RIR: the room Lx Ly Lz (m), the amplitude reflection coefficients of the walls x=0 x=Lx y=0 y=Ly z=0 z=Lz, the
+ *   source x y z, the head centre x y z, the heading about z in radians.  rirs [Q][taps][2] fp32, the ears interleaved as
+ *   m2h_rir_onset and the Auralizer read them; every element is written, so the buffer needs no clearing.
+ * max_order: images of more reflections are left out (0: the direct sound); -1: every image that reaches [0, taps).
+ * One launch, grid (ceil(taps / 512), Q); no atomics: the bits of an RIR depend on its 16 parameters, taps and max_order alone.
+ * Values are not validated: a row with a parameter that is not finite or beyond 1e5 in magnitude, a room side below 0.5 m, or a source
+ * or head centre outside its room is written as NaN.  Work grows with taps^3 / volume of the room.
+ * Returns a negative status and launches nothing for a null pointer, taps outside 1 .. 256000, Q outside 1 .. 65535, max_order < -1,
+ * or a buffer that is not 8-byte aligned. */
+int m2h_room_sim(const double* params, float* rirs, int Q, int taps, int max_order, m2h_stream stream);
+
 /* Scorer, STOI and ESTOI (m2h/audio/score.py, "STOI"; csrc/score_stoi.hip).
  * m2h_stoi_resample: for (r, c) the three signals of m2h_score_spectral over the region [D, L - D) -- 0: the clean signal
  * refs[r][target_r][c][D + t], 1: the estimate est[r][c][D + lag[r * C + c] + t], 2: the baseline mix[r][c][D + t] for C = 2,

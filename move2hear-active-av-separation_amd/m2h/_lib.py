@@ -16,7 +16,7 @@ CSRC = os.path.join(_PKG_ROOT, "csrc")
 INCLUDE = os.path.join(_REPO_ROOT, "include")
 # M2H_LIB: kernel-tuning override -- load an experimental build of the same C-ABI (tools/build_variant.sh) instead of the in-tree one
 LIB_PATH = os.environ.get("M2H_LIB") or os.path.join(_HERE, "libm2h.so")
-SOURCES = ["conv_dispatch.hip", "conv_igemm.hip", "conv_dma.hip", "conv_patch.hip", "convt_quad.hip", "convt_tap.hip", "conv_skinny.hip", "conv_row3x3.hip", "conv_strip.hip", "acoustic_mem.hip", "conv_bwd.hip", "wgrad_tiled.hip", "wgrad_row3x3.hip", "wgrad_reduce.hip", "bwd_pointwise.hip", "bn.hip", "stft.hip", "separate.hip", "resample.hip", "layout.hip", "rnn.hip", "policy_heads.hip", "advantage.hip", "losses.hip", "optim.hip", "rollout_ops.hip", "rollout_fused.hip", "pack_batch.hip", "fftconv.hip", "render.hip", "score.hip", "score_spectral.hip", "score_spatial.hip", "score_itd.hip", "score_stoi.hip", "score_bss.hip", "align.hip", "rir_acoustics.hip", "api.hip"]
+SOURCES = ["conv_dispatch.hip", "conv_igemm.hip", "conv_dma.hip", "conv_patch.hip", "convt_quad.hip", "convt_tap.hip", "conv_skinny.hip", "conv_row3x3.hip", "conv_strip.hip", "acoustic_mem.hip", "conv_bwd.hip", "wgrad_tiled.hip", "wgrad_row3x3.hip", "wgrad_reduce.hip", "bwd_pointwise.hip", "bn.hip", "stft.hip", "separate.hip", "resample.hip", "layout.hip", "rnn.hip", "policy_heads.hip", "advantage.hip", "losses.hip", "optim.hip", "rollout_ops.hip", "rollout_fused.hip", "pack_batch.hip", "fftconv.hip", "render.hip", "score.hip", "score_spectral.hip", "score_spatial.hip", "score_itd.hip", "score_stoi.hip", "score_bss.hip", "align.hip", "rir_acoustics.hip", "room_sim.hip", "api.hip"]
 
 _lock = threading.Lock()
 _lib = None
@@ -281,6 +281,7 @@ SIGNATURES = {
     "m2h_rir_onset": [_P, _P, _P, _P, _P, _I, _I, _P],
     "m2h_rir_band_energy": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "m2h_rir_decay": [_P, _P, _L, _I, _P],
+    "m2h_room_sim": [_P, _P, _I, _I, _I, _P],
     "m2h_stoi_resample": [_P, _L, _L, _L, _P, _L, _L, _P, _L, _L, _P, _I, _P, _P, _I, _I, _I, _L, _P, _I, _P],
     "m2h_stoi_ranges": [_P, _L, _L, _P, _P, _P, _I, _L, _I, _P, _P, _P, _P, _P, _P, _P],
     "m2h_bss_corr": [_P, _L, _L, _L, _P, _L, _L, _P, _L, _L, _P, _I, _I, _I, _L, _I, _I, _P, _I, _P],

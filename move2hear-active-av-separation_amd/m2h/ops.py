@@ -943,6 +943,30 @@ def rir_decay(bins):
     return out
 
 
+ROOM_TILE, ROOM_MAX_TAPS, ROOM_MAX_BATCH, ROOM_PARAMS = 512, 256000, 65535, 16     # csrc/room_sim.hip
+
+
+def room_sim(params, taps, max_order=None):
+    """Binaural RIRs of shoebox rooms by the image-source method (m2h/audio/room.py): params [Q, 16] fp64 contiguous on the device, per RIR
+    the room's three sides, the six reflection coefficients, the source, the head centre and the yaw; 1 <= taps <= 256000; max_order: None
+    for every image that reaches the taps -> [Q, taps, 2] fp32, every element written (include/m2h.h)."""
+    _chk(params, "room_sim(params)", torch.float64)
+    taps = int(taps)
+    if params.dim() != 2 or params.shape[1] != ROOM_PARAMS or not 1 <= params.shape[0] <= ROOM_MAX_BATCH:
+        raise RuntimeError("m2h.room_sim: params must be [1 <= Q <= %d, %d] float64, got %s" % (ROOM_MAX_BATCH, ROOM_PARAMS, tuple(params.shape)))
+    if not 1 <= taps <= ROOM_MAX_TAPS:
+        raise RuntimeError("m2h.room_sim: taps = %d; 1 .. %d are supported" % (taps, ROOM_MAX_TAPS))
+    order = -1 if max_order is None else int(max_order)
+    if order < 0 and max_order is not None:
+        raise RuntimeError("m2h.room_sim: max_order = %d; an order >= 0 or None is required" % order)
+    Q = int(params.shape[0])
+    out = torch.empty((Q, taps, 2), device=params.device, dtype=torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(params.device):
+        _lib.check(lib.m2h_room_sim(_ptr(params), _ptr(out), Q, taps, order, _stream(params)), "m2h_room_sim")
+    return out
+
+
 STOI_TABLE_SHAPE = (5, 33)                  # the polyphase table of 16 kHz -> 10 kHz (m2h.audio.resample)
 
 
