@@ -99,7 +99,8 @@ def simulate_f64(rir, mutant=None):
         n, ok = _taps_of(k, taps, mutant)
         x = n - tau[:, None]
         hw = 40.0 if mutant == "half_width_40" else float(HALF_WIDTH)
-        w = np.sinc(x) * 0.5 * (1.0 + np.cos(math.pi * x / hw))
+        sinc = np.where((x != 0) & (x == np.rint(x)), 0.0, np.sinc(x))      # (a delay that is a whole number: numpy's sin(pi n) / (pi n) is 4e-17, the definition's is 0)
+        w = sinc * 0.5 * (1.0 + np.cos(math.pi * x / hw))
         val = A[:, None] * w
         np.add.at(h[:, e], n[ok], val[ok])
         np.add.at(s[:, e], n[ok], np.abs(val[ok]))
