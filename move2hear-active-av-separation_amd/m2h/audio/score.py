@@ -270,6 +270,7 @@ applies the filters and writes the ten sums of every tile, no component signal e
 Scorer's own code makes no host synchronisation; what the library's factorisation does is recorded in DESIGN.md 8.11.
 """
 import operator
+from types import SimpleNamespace
 
 import torch
 
@@ -300,6 +301,15 @@ STOI_TILE = 16000            # stoi=True: a tile is exactly STOI_FS resampled sa
 STOI_FS, STOI_FRAME, STOI_HOP, STOI_NFFT, STOI_BANDS, STOI_SEGMENT = 10000, 256, 128, 512, 15, 30
 BSS_ORDER = ("sdr", "sir", "sar", "sdr_base", "sir_base", "sar_base", "sdri", "siri", "sari")
 BSS_MAX_TAPS = 512           # bss=T: the longest distortion filter
+# The metric families, in the order summarize() and score.py report them.  A row: (key prefix; metric order; rows per recording ("binaural")
+# instead of per channel; the windows that enter the track's mean and median -- "active": the target has energy, "both": active in both
+# ears, "finite": no NaN in the window's row --; the family's extra result keys as (key, whether summarize() carries it too)).
+FAMILIES = (("", METRIC_ORDER, False, "active", ()),
+            ("spectral_", SPECTRAL_ORDER, False, "active", ()),
+            ("spatial_", SPATIAL_ORDER, True, "both", (("spatial_cues", False),)),
+            ("itd_", ITD_ORDER, True, "both", (("itd_gcc", False),)),
+            ("stoi_", STOI_ORDER, False, "finite", (("stoi_frames", True),)),
+            ("bss_", BSS_ORDER, False, "active", ()))
 
 
 def score_plan(L, tile=DEFAULT_TILE, window=1, hop=1):
@@ -706,9 +716,23 @@ def bss_from_sums(sums, ok=None):
     return out if ok is None else torch.where(ok[..., None], out, torch.full_like(out, _NAN))
 
 
-def _whole_then_track(tiles, plan):
-    """tiles [R, C, J, K] float64 -> [R, C, 1 + M, K]: all J tiles added in tile order, then the plan's M windows"""
-    return torch.cat([ops.score_windows(tiles, 1, plan["J"], 1), ops.score_windows(tiles, plan["M"], plan["window"], plan["hop"])], dim=2)
+def _whole_then_track(tiles, plan, lead=2):
+    """tiles [R, C, J, ...] (lead = 2) or [R, J, ...] (lead = 1) float64, contiguous -> the same with 1 + M in place of J: all J tiles added
+    in tile order, then the plan's M windows"""
+    J, M = plan["J"], plan["M"]
+    flat = tiles if (lead, tiles.dim()) == (2, 4) else tiles.view(tiles.shape[0], tiles.shape[1] if lead == 2 else 1, J, -1)
+    both = torch.cat([ops.score_windows(flat, 1, J, 1), ops.score_windows(flat, M, plan["window"], plan["hop"])], dim=2)
+    return both if flat is tiles else both.view(tiles.shape[:lead] + (1 + M,) + tiles.shape[lead + 1:])
+
+
+def _rows(v, r0, r1):
+    """the recordings r0 .. r1 - 1 of a per-recording argument: a tensor is sliced; one int for all (a target) or None (no lag) is passed on"""
+    return v[r0:r1] if isinstance(v, torch.Tensor) else v
+
+
+def _cat(groups):
+    """the groups' results as one tensor (a single group as it is: no copy)"""
+    return groups[0] if len(groups) == 1 else torch.cat(groups)
 
 
 class Scorer:
@@ -716,42 +740,43 @@ class Scorer:
         if isinstance(max_corr_bytes, bool) or int(max_corr_bytes) < 1:
             raise ValueError("m2h.Scorer: max_corr_bytes must be positive, got %r" % (max_corr_bytes,))
         self.device = torch.device(device)
-        self.max_corr_bytes = int(max_corr_bytes)   # align: recordings are processed in groups whose tile correlations stay under this
-        self._twiddles = None
-        self._dft = None
-        self._stoi = None
-        self._itd = None
+        self.max_corr_bytes = int(max_corr_bytes)   # align, bss, itd: recordings are processed in groups whose tile buffers stay under this
+        self._twiddles = self._dft = self._itd = self._stoi = None     # the device tables, each filled by _table on its first use
         self._timing = None          # tools/score_bench.py: a list that receives (stage, event) marks
+
+    def _table(self, slot, make):
+        """the device table kept in the attribute `slot`: make() on the first call (the one copy from the host), the same object afterwards"""
+        if getattr(self, slot) is None:
+            setattr(self, slot, make())
+        return getattr(self, slot)
 
     def _twiddle_table(self):
         """the transform's [2, 16384, 2] table on the device (m2h.audio.twiddles), copied from the host once"""
-        if self._twiddles is None:
-            self._twiddles = device_twiddles(self.device, ALIGN_NFFT)
-        return self._twiddles
+        return self._table("_twiddles", lambda: device_twiddles(self.device, ALIGN_NFFT))
 
     def _spectral_table(self):
         """spectral_table() on the device, copied from the host once"""
-        if self._dft is None:
-            self._dft = torch.from_numpy(spectral_table()).to(self.device)
-        return self._dft
+        return self._table("_dft", lambda: torch.from_numpy(spectral_table()).to(self.device))
 
     def _itd_table(self):
         """itd_table() on the device, copied from the host once"""
-        if self._itd is None:
-            self._itd = torch.from_numpy(itd_table()).to(self.device)
-        return self._itd
+        return self._table("_itd", lambda: torch.from_numpy(itd_table()).to(self.device))
 
     def _stoi_tables(self):
         """(the 16 kHz -> 10 kHz polyphase table [5, 33], the window [256], the 512-point transform's twiddles) on the device, copied from the
         host once"""
-        if self._stoi is None:
+        def make():
             from .resample import design, polyphase_table
-            from .twiddles import device_twiddles as tw
             import numpy as np
             up, _, _, taps = design(STOI_TILE, STOI_FS)
-            self._stoi = (torch.from_numpy(polyphase_table(taps.astype(np.float32), up)).to(self.device), torch.from_numpy(stoi_window()).to(self.device),
-                          tw(self.device, STOI_NFFT))
-        return self._stoi
+            return (torch.from_numpy(polyphase_table(taps.astype(np.float32), up)).to(self.device), torch.from_numpy(stoi_window()).to(self.device),
+                    device_twiddles(self.device, STOI_NFFT))
+        return self._table("_stoi", make)
+
+    def _groups(self, R, bytes_per_recording):
+        """[(r0, r1)]: the R recordings in groups whose tile buffers stay under max_corr_bytes (a single recording above it goes alone)"""
+        step = max(1, self.max_corr_bytes // bytes_per_recording)
+        return [(r0, min(r0 + step, R)) for r0 in range(0, R, step)]
 
     def _stoi_ranges(self, plan, sp):
         """m2h_stoi_ranges' table [1 + M, 3] int64 of stoi_plan's ranges, built on the device: fills and aranges, no copy from the host"""
@@ -862,182 +887,156 @@ class Scorer:
         in ITD_ORDER (microseconds and peak heights), and the GCC-PHAT functions themselves, "itd_gcc": [R, 1 + M, 3, 257] (the whole
         recording first; signal target / estimate / mixture; the lags i / 8 samples, i = -128 .. 128).  The module docstring holds the
         definition."""
-        refs, est, target, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial, stoi, bss, itd)
-        targets = target                                                                # host integers (bss_filters)
-        R, S, C, L = refs.shape
-        J, M, tile, window, hop = (plan[k] for k in ("J", "M", "tile", "window", "hop"))
-        D = plan.get("offset", 0)
-        Ls = L - 2 * D                                                                  # the scored samples per row
-        dev = self.device
-        out = {}
-        with torch.cuda.device(dev):
-            if not isinstance(target, int):                                            # R small fills: no copy from the host
-                tt = torch.empty((R,), dtype=torch.int64, device=dev)
-                for r, t in enumerate(target):
-                    tt[r].fill_(t)
-                target = tt
-            if align is not None:
-                tw = self._twiddle_table()
+        refs, est, targets, plan = self._check(estimate, references, mixture, target, tile, window, hop, align, spectral, spatial, stoi, bss, itd)
+        with torch.cuda.device(self.device):
+            target = targets                                                            # host integers (bss_filters); on the device:
+            if not isinstance(targets, int):                                            # R small fills: no copy from the host
+                target = torch.empty((len(targets),), dtype=torch.int64, device=self.device)
+                for r, t in enumerate(targets):
+                    target[r].fill_(t)
+            # what every stage takes: the signals, the target on the device and on the host, the plan, the region's offset D, the taps of
+            # bss=T; `lag` [R, C] int32 once _stage_align has run and `m`, the windows' first tiles [M] int64, once _stage_eleven has
+            call = SimpleNamespace(refs=refs, est=est, mixture=mixture, target=target, targets=targets, plan=plan, D=plan.get("offset", 0), taps=bss,
+                                   lag=None, m=None)
             self._mark("start")
-            if align is None:
-                tiles = ops.score_gram(refs, est, mixture, tile)                        # [R, C, J, K]
-            else:
-                step = max(1, self.max_corr_bytes // (C * J * (2 * D + 1) * 8))         # recordings per group
-                lags = []
-                for r0 in range(0, R, step):
-                    r1 = min(r0 + step, R)
-                    ct = ops.align_corr(refs[r0:r1], est[r0:r1], target if isinstance(target, int) else target[r0:r1], tile, D, tw)     # [r, C, J, 2 D + 1]
-                    self._mark("align_corr")
-                    lags.append(lags_from_corr(_whole_then_track(ct, plan)))
-                    del ct
-                    self._mark("lag_pick")
-                lags = lags[0] if len(lags) == 1 else torch.cat(lags)                   # [R, C, 1 + M]: whole, then the track
-                out["lag"], out["lag_track"] = lags[:, :, 0].contiguous(), lags[:, :, 1:]
-                tiles = ops.score_gram_lag(refs, est, mixture, tile, out["lag"], D)
-            self._mark("score_gram")
-            gram = _whole_then_track(tiles, plan)
-            m = torch.arange(M, device=dev, dtype=torch.int64) * hop
-            n = (torch.clamp((m + window) * tile, max=Ls) - torch.clamp(m * tile, max=Ls)).to(torch.float64)
-            n = torch.cat([torch.full((1,), float(Ls), dtype=torch.float64, device=dev), n])
-            scores = metrics_from_gram(gram, n, target, C)
-            active = target_energy(gram[:, :, 1:], n[1:], target) > 0
-            self._mark("metrics")
-            if spectral:
-                sums = ops.score_spectral(refs, est, mixture, target, self._spectral_table(), out.get("lag"), D)        # [R, C, J, 7]
-                self._mark("score_spectral")
-                sums = _whole_then_track(sums, plan)
-                q = (torch.clamp(m + window, max=J) - torch.clamp(m, max=J)).to(torch.float64)
-                spec = spectral_from_sums(sums, torch.cat([torch.full((1,), float(J), dtype=torch.float64, device=dev), q]))
-                out.update({"spectral_whole": spec[:, :, 0], "spectral_track": spec[:, :, 1:]})
-                self._mark("spectral_metrics")
-            if spatial:
-                sums = ops.score_spatial(refs, est, mixture, target, self._spectral_table(), out.get("lag"), D)         # [R, J, 3, 32, 4]
-                self._mark("score_spatial")
-                K = 3 * SPATIAL_BANDS * 4
-                sums = sums.view(R, 1, J, K)
-                sums = _whole_then_track(sums, plan)
-                spat, cues = spatial_from_sums(sums.view(R, 1 + M, 3, SPATIAL_BANDS, 4))
-                out.update({"spatial_whole": spat[:, 0], "spatial_track": spat[:, 1:], "spatial_cues": cues[:, 1:]})
-                self._mark("spatial_metrics")
-            if stoi:
-                table, win, tw = self._stoi_tables()
-                sp = stoi_plan(plan)
-                x10 = ops.stoi_resample(refs, est, mixture, target, table, out.get("lag"), D)                            # [R, C, 3, L10]
-                self._mark("stoi_resample")
-                st = ops.stoi_ranges(x10, self._stoi_ranges(plan, sp), sp["total"], win, tw)
-                out.update({"stoi_whole": st["out"][:, :, 0], "stoi_track": st["out"][:, :, 1:], "stoi_frames": st["kept"][..., 0].to(torch.int64)})
-                self._mark("stoi_ranges")
-            if bss is not None:
-                lag = out.get("lag")
-                step = max(1, self.max_corr_bytes // (C * J * S * (S + 2) * bss * 8))   # recordings per group
-                corr = []
-                for r0 in range(0, R, step):
-                    r1 = min(r0 + step, R)
-                    ct = ops.bss_corr(refs[r0:r1], est[r0:r1], mixture[r0:r1], tile, bss, None if lag is None else lag[r0:r1], D)      # [r, C, J, S, S + 2, T]
-                    corr.append(ops.score_windows(ct.view(r1 - r0, C, J, S * (S + 2) * bss), 1, J, 1).view(r1 - r0, C, S, S + 2, bss))
-                    del ct
-                corr = corr[0] if len(corr) == 1 else torch.cat(corr)
-                self._mark("bss_corr")
-                h, ok = bss_filters(corr, targets)
-                self._mark("bss_solve")
-                sums = ops.bss_project(refs, est, mixture, target, h, tile, lag, D)     # [R, C, J, 10]
-                self._mark("bss_project")
-                b9 = bss_from_sums(_whole_then_track(sums, plan), ok[:, :, None])
-                out.update({"bss_whole": b9[:, :, 0], "bss_track": b9[:, :, 1:]})
-                self._mark("bss_metrics")
-            if itd:
-                dft, tab, lag = self._spectral_table(), self._itd_table(), out.get("lag")
-                K = 3 * ITD_BINS[1] * 2
-                step = max(1, self.max_corr_bytes // (J * K * 8))                       # recordings per group
-                gcc, has = [], []
-                for r0 in range(0, R, step):
-                    r1 = min(r0 + step, R)
-                    sums = ops.score_itd(refs[r0:r1], est[r0:r1], mixture[r0:r1], target if isinstance(target, int) else target[r0:r1], dft,
-                                         None if lag is None else lag[r0:r1], D)        # [r, J, 3, 256, 2]
-                    self._mark("score_itd")
-                    sums = _whole_then_track(sums.view(r1 - r0, 1, J, K), plan).view(r1 - r0, 1 + M, 3, ITD_BINS[1], 2)
-                    self._mark("itd_windows")
-                    gcc.append(ops.itd_gcc(sums, tab, *ITD_BINS))                       # [r, 1 + M, 3, 257]
-                    has.append(itd_has_band(sums))
-                    del sums
-                    self._mark("itd_gcc")
-                gcc, has = (gcc[0], has[0]) if len(gcc) == 1 else (torch.cat(gcc), torch.cat(has))
-                nine = itd_from_gcc(gcc, has)
-                out.update({"itd_whole": nine[:, 0], "itd_track": nine[:, 1:], "itd_gcc": gcc})
-                self._mark("itd_metrics")
-        out.update({"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan})
+            out = self._stage_align(call) if align is not None else {}
+            eleven = self._stage_eleven(call)
+            for on, stage in ((spectral, self._stage_spectral), (spatial, self._stage_spatial), (stoi, self._stage_stoi),
+                              (bss is not None, self._stage_bss), (itd, self._stage_itd)):
+                if on:
+                    out.update(stage(call))
+        out.update(eleven)                                                              # (their keys come last)
         return out
+
+    def _stage_align(self, call):
+        """align=D ("Alignment"): the lags of every recording and channel, whole and per window, as the keys lag and lag_track; sets call.lag"""
+        R, _, C, _ = call.refs.shape
+        plan, D, tw = call.plan, call.D, self._twiddle_table()
+        lags = []
+        for r0, r1 in self._groups(R, C * plan["J"] * (2 * D + 1) * 8):
+            ct = ops.align_corr(call.refs[r0:r1], call.est[r0:r1], _rows(call.target, r0, r1), plan["tile"], D, tw)     # [r, C, J, 2 D + 1]
+            self._mark("align_corr")
+            lags.append(lags_from_corr(_whole_then_track(ct, plan)))
+            del ct
+            self._mark("lag_pick")
+        lags = _cat(lags)                                                               # [R, C, 1 + M]: whole, then the track
+        call.lag = lags[:, :, 0].contiguous()
+        return {"lag": call.lag, "lag_track": lags[:, :, 1:]}
+
+    def _stage_eleven(self, call):
+        """the eleven numbers as the keys whole, track, active and plan; sets call.m"""
+        plan, dev, C = call.plan, self.device, call.refs.shape[2]
+        M, tile, window, hop, Ls = (plan[k] for k in ("M", "tile", "window", "hop", "L"))      # Ls: the scored samples per row
+        if call.lag is None:
+            tiles = ops.score_gram(call.refs, call.est, call.mixture, tile)             # [R, C, J, K]
+        else:
+            tiles = ops.score_gram_lag(call.refs, call.est, call.mixture, tile, call.lag, call.D)
+        self._mark("score_gram")
+        gram = _whole_then_track(tiles, plan)
+        call.m = m = torch.arange(M, device=dev, dtype=torch.int64) * hop
+        n = (torch.clamp((m + window) * tile, max=Ls) - torch.clamp(m * tile, max=Ls)).to(torch.float64)
+        n = torch.cat([torch.full((1,), float(Ls), dtype=torch.float64, device=dev), n])
+        scores = metrics_from_gram(gram, n, call.target, C)
+        active = target_energy(gram[:, :, 1:], n[1:], call.target) > 0
+        self._mark("metrics")
+        return {"whole": scores[:, :, 0], "track": scores[:, :, 1:], "active": active, "plan": plan}
+
+    def _stage_spectral(self, call):
+        """spectral=True ("Spectral"): the keys spectral_whole and spectral_track"""
+        J, window, dev = call.plan["J"], call.plan["window"], self.device
+        sums = ops.score_spectral(call.refs, call.est, call.mixture, call.target, self._spectral_table(), call.lag, call.D)     # [R, C, J, 7]
+        self._mark("score_spectral")
+        sums = _whole_then_track(sums, call.plan)
+        q = (torch.clamp(call.m + window, max=J) - torch.clamp(call.m, max=J)).to(torch.float64)
+        spec = spectral_from_sums(sums, torch.cat([torch.full((1,), float(J), dtype=torch.float64, device=dev), q]))
+        self._mark("spectral_metrics")
+        return {"spectral_whole": spec[:, :, 0], "spectral_track": spec[:, :, 1:]}
+
+    def _stage_spatial(self, call):
+        """spatial=True ("Spatial"): the keys spatial_whole, spatial_track and spatial_cues"""
+        sums = ops.score_spatial(call.refs, call.est, call.mixture, call.target, self._spectral_table(), call.lag, call.D)      # [R, J, 3, 32, 4]
+        self._mark("score_spatial")
+        spat, cues = spatial_from_sums(_whole_then_track(sums, call.plan, lead=1))
+        self._mark("spatial_metrics")
+        return {"spatial_whole": spat[:, 0], "spatial_track": spat[:, 1:], "spatial_cues": cues[:, 1:]}
+
+    def _stage_stoi(self, call):
+        """stoi=True ("STOI"): the keys stoi_whole, stoi_track and stoi_frames"""
+        table, win, tw = self._stoi_tables()
+        sp = stoi_plan(call.plan)
+        x10 = ops.stoi_resample(call.refs, call.est, call.mixture, call.target, table, call.lag, call.D)                        # [R, C, 3, L10]
+        self._mark("stoi_resample")
+        st = ops.stoi_ranges(x10, self._stoi_ranges(call.plan, sp), sp["total"], win, tw)
+        self._mark("stoi_ranges")
+        return {"stoi_whole": st["out"][:, :, 0], "stoi_track": st["out"][:, :, 1:], "stoi_frames": st["kept"][..., 0].to(torch.int64)}
+
+    def _stage_bss(self, call):
+        """bss=T ("BSS"), T = call.taps: the keys bss_whole and bss_track"""
+        R, S, C, _ = call.refs.shape
+        plan, T, J, tile = call.plan, call.taps, call.plan["J"], call.plan["tile"]
+        corr = []
+        for r0, r1 in self._groups(R, C * J * S * (S + 2) * T * 8):
+            ct = ops.bss_corr(call.refs[r0:r1], call.est[r0:r1], call.mixture[r0:r1], tile, T, _rows(call.lag, r0, r1), call.D)   # [r, C, J, S, S + 2, T]
+            corr.append(ops.score_windows(ct.view(r1 - r0, C, J, S * (S + 2) * T), 1, J, 1).view(r1 - r0, C, S, S + 2, T))
+            del ct
+        self._mark("bss_corr")
+        h, ok = bss_filters(_cat(corr), call.targets)
+        self._mark("bss_solve")
+        sums = ops.bss_project(call.refs, call.est, call.mixture, call.target, h, tile, call.lag, call.D)                       # [R, C, J, 10]
+        self._mark("bss_project")
+        b9 = bss_from_sums(_whole_then_track(sums, plan), ok[:, :, None])
+        self._mark("bss_metrics")
+        return {"bss_whole": b9[:, :, 0], "bss_track": b9[:, :, 1:]}
+
+    def _stage_itd(self, call):
+        """itd=True ("ITD"): the keys itd_whole, itd_track and itd_gcc"""
+        dft, tab = self._spectral_table(), self._itd_table()
+        gcc, has = [], []
+        for r0, r1 in self._groups(call.refs.shape[0], call.plan["J"] * 3 * ITD_BINS[1] * 2 * 8):
+            sums = ops.score_itd(call.refs[r0:r1], call.est[r0:r1], call.mixture[r0:r1], _rows(call.target, r0, r1), dft, _rows(call.lag, r0, r1),
+                                 call.D)                                                # [r, J, 3, 256, 2]
+            self._mark("score_itd")
+            sums = _whole_then_track(sums, call.plan, lead=1)                           # [r, 1 + M, 3, 256, 2]
+            self._mark("itd_windows")
+            gcc.append(ops.itd_gcc(sums, tab, *ITD_BINS))                               # [r, 1 + M, 3, 257]
+            has.append(itd_has_band(sums))
+            del sums
+            self._mark("itd_gcc")
+        gcc = _cat(gcc)
+        nine = itd_from_gcc(gcc, _cat(has))
+        self._mark("itd_metrics")
+        return {"itd_whole": nine[:, 0], "itd_track": nine[:, 1:], "itd_gcc": gcc}
 
 
 def summarize(result):
-    """Host-side summary of Scorer.score's result for one call: {"metrics", "whole": [R][C][11], "track_mean", "track_median": over the
-    active windows ([R][C][11], NaN without any), "active_windows": [R][C]} as Python lists (one synchronisation); with spectral=True /
-    spatial=True results also the "spectral_*" / "spatial_*" keys (spatial: [R][9], over the windows in which both ears are active); with
-    itd=True results also "itd_metrics", "itd_whole" [R][9] and "itd_track_mean" / "itd_track_median" over the same windows as spatial; with
-    stoi=True results also "stoi_metrics", "stoi_whole" [R][C][6], "stoi_track_mean" / "stoi_track_median" over the windows that are not NaN
-    and "stoi_frames" [R][C][1 + M]; with bss=T results also "bss_metrics", "bss_whole" [R][C][9] and "bss_track_mean" / "bss_track_median" over
-    the active windows."""
+    """Host-side summary of Scorer.score's result for one call, as Python lists (one synchronisation): {"metrics", "whole": [R][C][11],
+    "track_mean", "track_median": over the active windows ([R][C][11], NaN without any), "active_windows": [R][C]}, and for every other family
+    of FAMILIES that the result holds the same four keys under its prefix ("spectral_metrics", "spectral_whole", ...), the mean and median over
+    that family's windows; spatial and itd are per recording, [R][9]; stoi=True results also carry "stoi_frames" [R][C][1 + M]."""
     import numpy as np
-    whole, track, active = (result[k].cpu().numpy() for k in ("whole", "track", "active"))
-    R, C = whole.shape[:2]
-    mean, median = np.full((R, C, 11), np.nan), np.full((R, C, 11), np.nan)
-    with np.errstate(all="ignore"):
-        for r in range(R):
-            for c in range(C):
-                rows = track[r, c][active[r, c]]
-                if rows.shape[0]:
-                    mean[r, c], median[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
-    out = {"metrics": list(METRIC_ORDER), "whole": whole.tolist(), "track_mean": mean.tolist(), "track_median": median.tolist(),
-           "active_windows": active.sum(axis=-1).tolist()}
-    if "spectral_whole" in result:                                                      # score(..., spectral=True): the same over the same windows
-        sw, st = result["spectral_whole"].cpu().numpy(), result["spectral_track"].cpu().numpy()
-        smean, smedian = np.full((R, C, 8), np.nan), np.full((R, C, 8), np.nan)
-        with np.errstate(all="ignore"):
-            for r in range(R):
-                for c in range(C):
-                    rows = st[r, c][active[r, c]]
-                    if rows.shape[0]:
-                        smean[r, c], smedian[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
-        out.update({"spectral_metrics": list(SPECTRAL_ORDER), "spectral_whole": sw.tolist(), "spectral_track_mean": smean.tolist(),
-                    "spectral_track_median": smedian.tolist()})
-    if "spatial_whole" in result:                                                       # score(..., spatial=True): over the windows in which BOTH ears are active
-        pw, pt = result["spatial_whole"].cpu().numpy(), result["spatial_track"].cpu().numpy()
-        pmean, pmedian = np.full((R, 9), np.nan), np.full((R, 9), np.nan)
-        with np.errstate(all="ignore"):
-            for r in range(R):
-                rows = pt[r][active[r].all(axis=0)]
-                if rows.shape[0]:
-                    pmean[r], pmedian[r] = rows.mean(axis=0), np.median(rows, axis=0)
-        out.update({"spatial_metrics": list(SPATIAL_ORDER), "spatial_whole": pw.tolist(), "spatial_track_mean": pmean.tolist(),
-                    "spatial_track_median": pmedian.tolist()})
-    if "itd_whole" in result:                                                          # score(..., itd=True): over the windows in which BOTH ears are active
-        iw, it = result["itd_whole"].cpu().numpy(), result["itd_track"].cpu().numpy()
-        imean, imedian = np.full((R, 9), np.nan), np.full((R, 9), np.nan)
-        with np.errstate(all="ignore"):
-            for r in range(R):
-                rows = it[r][active[r].all(axis=0)]
-                if rows.shape[0]:
-                    imean[r], imedian[r] = rows.mean(axis=0), np.median(rows, axis=0)
-        out.update({"itd_metrics": list(ITD_ORDER), "itd_whole": iw.tolist(), "itd_track_mean": imean.tolist(), "itd_track_median": imedian.tolist()})
-    if "stoi_whole" in result:                                                         # score(..., stoi=True): over the windows that are not NaN
-        tw, tt = result["stoi_whole"].cpu().numpy(), result["stoi_track"].cpu().numpy()
-        tmean, tmedian = np.full((R, C, 6), np.nan), np.full((R, C, 6), np.nan)
-        with np.errstate(all="ignore"):
-            for r in range(R):
-                for c in range(C):
-                    rows = tt[r, c][~np.isnan(tt[r, c]).any(axis=-1)]
-                    if rows.shape[0]:
-                        tmean[r, c], tmedian[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
-        out.update({"stoi_metrics": list(STOI_ORDER), "stoi_whole": tw.tolist(), "stoi_track_mean": tmean.tolist(), "stoi_track_median": tmedian.tolist(),
-                    "stoi_frames": result["stoi_frames"].cpu().tolist()})
-    if "bss_whole" in result:                                                          # score(..., bss=T): over the active windows
-        bw, bt = result["bss_whole"].cpu().numpy(), result["bss_track"].cpu().numpy()
-        bmean, bmedian = np.full((R, C, 9), np.nan), np.full((R, C, 9), np.nan)
-        with np.errstate(all="ignore"):
-            for r in range(R):
-                for c in range(C):
-                    rows = bt[r, c][active[r, c]]
-                    if rows.shape[0]:
-                        bmean[r, c], bmedian[r, c] = rows.mean(axis=0), np.median(rows, axis=0)
-        out.update({"bss_metrics": list(BSS_ORDER), "bss_whole": bw.tolist(), "bss_track_mean": bmean.tolist(), "bss_track_median": bmedian.tolist()})
+    active = result["active"].cpu().numpy()
+    out = {}
+    for prefix, order, binaural, windows, extras in FAMILIES:
+        if prefix + "whole" not in result:
+            continue
+        whole, track = result[prefix + "whole"].cpu().numpy(), result[prefix + "track"].cpu().numpy()
+        keep = active if windows == "active" else active.all(axis=1) if windows == "both" else ~np.isnan(track).any(axis=-1)
+        mean, median = _mean_median(track, keep)
+        out.update({prefix + "metrics": list(order), prefix + "whole": whole.tolist(), prefix + "track_mean": mean.tolist(),
+                    prefix + "track_median": median.tolist()})
+        if not prefix:
+            out["active_windows"] = active.sum(axis=-1).tolist()
+        out.update({key: result[key].cpu().tolist() for key, carried in extras if carried})
     return out
+
+
+def _mean_median(track, keep):
+    """track [..., M, K] and keep [..., M] bool, numpy -> (mean, median) [..., K] of every row's kept windows, NaN where a row keeps none"""
+    import numpy as np
+    mean, median = (np.full(track.shape[:-2] + track.shape[-1:], np.nan) for _ in range(2))
+    with np.errstate(all="ignore"):
+        for i in np.ndindex(keep.shape[:-1]):
+            rows = track[i][keep[i]]
+            if rows.shape[0]:
+                mean[i], median[i] = rows.mean(axis=0), np.median(rows, axis=0)
+    return mean, median

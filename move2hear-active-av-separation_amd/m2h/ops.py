@@ -794,12 +794,17 @@ def score_gram_lag(refs, est, mix, tile, lag, D):
 SPECTRAL_TABLE_SHAPE = (32, 128, 2, 64)      # m2h_score_spectral's folded transform table (include/m2h.h)
 
 
-def _score_stft(what, refs, dft, target, lag, D):
-    """what score_spectral and score_spatial share beyond the signals: the D / lag rule, the table, the lag and target arguments
-    -> (D, J, lag pointer, target pointer, target int)"""
+def _score_region(what, refs, lag, D):
+    """the D / lag rule of the region [D, L - D): a lag comes with D in 1 .. 8192, no lag with D = 0, and the region holds a sample -> D"""
     L, D = refs.shape[3], int(D)
     if not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
         raise RuntimeError("m2h.%s: D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required" % (what, D, L))
+    return D
+
+
+def _score_stft(what, refs, dft, target, lag, D):
+    """what score_spectral, score_spatial and score_itd share beyond the signals -> (D, J, lag pointer, target pointer, target int)"""
+    L, D = refs.shape[3], _score_region(what, refs, lag, D)
     _chk(dft, "%s(dft)" % what)
     if tuple(dft.shape) != SPECTRAL_TABLE_SHAPE or dft.device != refs.device:
         raise RuntimeError("m2h.%s: dft must be the %s table on %s" % (what, list(SPECTRAL_TABLE_SHAPE), refs.device))
@@ -976,9 +981,7 @@ def stoi_resample(refs, est, mix, target, table, lag=None, D=0):
     device -> [R, C, 3, L10] fp32 (clean, estimate, baseline), L10 = ceil((L - 2 D) * 5 / 8): bit for bit Resampler(16000, 10000) on
     contiguous copies of the three rows (include/m2h.h)."""
     R, S, C, L = _score_signals("stoi_resample", refs, est, mix)
-    D = int(D)
-    if not 0 <= D <= 8192 or (lag is None) != (D == 0) or L < 2 * D + 1:
-        raise RuntimeError("m2h.stoi_resample: D = %d in 1 .. 8192 with a lag (0 without) and L = %d >= 2 D + 1 are required" % (D, L))
+    D = _score_region("stoi_resample", refs, lag, D)
     _chk(table, "stoi_resample(table)")
     if tuple(table.shape) != STOI_TABLE_SHAPE or table.device != refs.device:
         raise RuntimeError("m2h.stoi_resample: table must be the %s table on %s" % (list(STOI_TABLE_SHAPE), refs.device))

@@ -109,7 +109,7 @@ def main():
                              % (args.estimate, est.shape[1], path, x.shape[1]))
 
     import torch
-    from m2h.audio.score import Scorer, summarize
+    from m2h.audio.score import FAMILIES, Scorer, summarize
     dev = torch.device("cuda", 0)
     try:
         res = Scorer(dev).score(torch.from_numpy(np.ascontiguousarray(est)).to(dev)[None], torch.from_numpy(np.stack(refs)).to(dev)[None],
@@ -130,59 +130,33 @@ def main():
         print("score.py: --align %d: samples [%d, %d) of the references and the mixture are scored" % (args.align, t0, t1))
         for c in range(C):
             print("%-8s lag %d samples (%.4f ms)" % (names[c], lag[c], 1000.0 * lag[c] / separate.SAMPLE_RATE))
-    print("%-8s %-14s" % ("channel", "") + " ".join("%13s" % m for m in s["metrics"]))
-    for c in range(C):
-        for label, key in (("whole", "whole"), ("window mean", "track_mean"), ("window median", "track_median")):
-            print("%-8s %-14s" % (names[c], label) + " ".join("%13.7f" % v for v in s[key][0][c]))
-        print("%-8s %d of %d windows active" % (names[c], s["active_windows"][0][c], plan["M"]))
-    if args.spectral:
-        print("%-8s %-23s" % ("spectral", "") + " ".join("%20s" % m for m in s["spectral_metrics"]))
-        for c in range(C):
-            for label, key in (("spectral whole", "spectral_whole"), ("spectral window mean", "spectral_track_mean"), ("spectral window median", "spectral_track_median")):
-                print("%-8s %-23s" % (names[c], label) + " ".join("%20.12e" % v for v in s[key][0][c]))
-    if args.spatial:
-        print("%-8s %-23s" % ("spatial", "") + " ".join("%20s" % m for m in s["spatial_metrics"]))
-        for label, key in (("spatial whole", "spatial_whole"), ("spatial window mean", "spatial_track_mean"), ("spatial window median", "spatial_track_median")):
-            print("%-8s %-23s" % ("binaural", label) + " ".join("%20.12e" % v for v in s[key][0]))
-    if args.itd:
-        print("%-8s %-23s" % ("itd us", "") + " ".join("%20s" % m for m in s["itd_metrics"]))
-        for label, key in (("itd whole", "itd_whole"), ("itd window mean", "itd_track_mean"), ("itd window median", "itd_track_median")):
-            print("%-8s %-23s" % ("binaural", label) + " ".join("%20.12e" % v for v in s[key][0]))
-    if args.stoi:
-        print("%-8s %-23s" % ("stoi", "") + " ".join("%20s" % m for m in s["stoi_metrics"]))
-        for c in range(C):
-            for label, key in (("stoi whole", "stoi_whole"), ("stoi window mean", "stoi_track_mean"), ("stoi window median", "stoi_track_median")):
-                print("%-8s %-23s" % (names[c], label) + " ".join("%20.12e" % v for v in s[key][0][c]))
-    if args.bss is not None:
-        print("%-8s %-23s" % ("bss %d" % args.bss, "") + " ".join("%20s" % m for m in s["bss_metrics"]))
-        for c in range(C):
-            for label, key in (("bss whole", "bss_whole"), ("bss window mean", "bss_track_mean"), ("bss window median", "bss_track_median")):
-                print("%-8s %-23s" % (names[c], label) + " ".join("%20.12e" % v for v in s[key][0][c]))
+    for prefix, _, binaural, _, _ in FAMILIES:                                           # the table, then a block of rows per requested family
+        if prefix + "whole" not in s:
+            continue
+        name = prefix.rstrip("_")
+        head = {"": "channel", "itd": "itd us", "bss": "bss %s" % args.bss}.get(name, name)
+        left, cell, num = ("%-8s %-23s", "%20s", "%20.12e") if prefix else ("%-8s %-14s", "%13s", "%13.7f")
+        print(left % (head, "") + " ".join(cell % m for m in s[prefix + "metrics"]))
+        for c, who in enumerate(("binaural",) if binaural else names):
+            for label, key in (("whole", "whole"), ("window mean", "track_mean"), ("window median", "track_median")):
+                row = s[prefix + key][0] if binaural else s[prefix + key][0][c]
+                print(left % (who, (name + " " + label).lstrip()) + " ".join(num % v for v in row))
+            if not prefix:
+                print("%-8s %d of %d windows active" % (who, s["active_windows"][0][c], plan["M"]))
     if args.json is not None:
         out = {"estimate": args.estimate, "mixture": args.mixture, "references": args.reference, "sample_rate": separate.SAMPLE_RATE,
                "samples": L, "channels": list(names), "window_s": args.window, "hop_s": args.hop, "metrics": s["metrics"],
                "whole": s["whole"][0], "track_mean": s["track_mean"][0], "track_median": s["track_median"][0],
                "active_windows": s["active_windows"][0], "windows": [list(w) for w in plan["samples"]],
                "track": res["track"][0].cpu().numpy().tolist(), "active": res["active"][0].cpu().numpy().tolist()}
-        if args.spectral:
-            out.update({"spectral_metrics": s["spectral_metrics"], "spectral_whole": s["spectral_whole"][0],
-                        "spectral_track": res["spectral_track"][0].cpu().numpy().tolist(), "spectral_track_mean": s["spectral_track_mean"][0],
-                        "spectral_track_median": s["spectral_track_median"][0]})
-        if args.spatial:
-            out.update({"spatial_metrics": s["spatial_metrics"], "spatial_whole": s["spatial_whole"][0],
-                        "spatial_track": res["spatial_track"][0].cpu().numpy().tolist(), "spatial_track_mean": s["spatial_track_mean"][0],
-                        "spatial_track_median": s["spatial_track_median"][0], "spatial_cues": res["spatial_cues"][0].cpu().numpy().tolist()})
-        if args.itd:
-            out.update({"itd_metrics": s["itd_metrics"], "itd_whole": s["itd_whole"][0], "itd_track": res["itd_track"][0].cpu().numpy().tolist(),
-                        "itd_track_mean": s["itd_track_mean"][0], "itd_track_median": s["itd_track_median"][0],
-                        "itd_gcc": res["itd_gcc"][0].cpu().numpy().tolist()})
-        if args.stoi:
-            out.update({"stoi_metrics": s["stoi_metrics"], "stoi_whole": s["stoi_whole"][0], "stoi_track": res["stoi_track"][0].cpu().numpy().tolist(),
-                        "stoi_track_mean": s["stoi_track_mean"][0], "stoi_track_median": s["stoi_track_median"][0], "stoi_frames": s["stoi_frames"][0]})
-        if args.bss is not None:
-            out.update({"bss_taps": args.bss, "bss_metrics": s["bss_metrics"], "bss_whole": s["bss_whole"][0],
-                        "bss_track": res["bss_track"][0].cpu().numpy().tolist(), "bss_track_mean": s["bss_track_mean"][0],
-                        "bss_track_median": s["bss_track_median"][0]})
+        for prefix, _, _, _, extras in FAMILIES[1:]:
+            if prefix + "whole" in s:
+                if prefix == "bss_":
+                    out["bss_taps"] = args.bss
+                out.update({prefix + "metrics": s[prefix + "metrics"], prefix + "whole": s[prefix + "whole"][0],
+                            prefix + "track": res[prefix + "track"][0].cpu().numpy().tolist(), prefix + "track_mean": s[prefix + "track_mean"][0],
+                            prefix + "track_median": s[prefix + "track_median"][0]})
+                out.update({key: res[key][0].cpu().numpy().tolist() for key, _ in extras})
         if args.align is not None:
             out.update({"align": args.align, "region": [t0, t1], "lag": lag, "lag_track": res["lag_track"][0].cpu().tolist()})
         with open(args.json, "w") as f:

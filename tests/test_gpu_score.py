@@ -321,3 +321,50 @@ def test_render_separate_score_plumbing(dev, scorer):
     assert bool(res["active"].all()) and bool(torch.isfinite(res["track"][res["active"]]).all()) and bool(torch.isfinite(res["whole"]).all())
     mono = scorer.score(sep.separate(mix, 4, use_memory=False), images[:, :, 0], mix)                    # a mono estimate against the left images
     assert tuple(mono["whole"].shape) == (2, 1, 11) and bool(torch.isfinite(mono["track"][mono["active"]]).all())
+
+
+CLI_JSON_KEYS = ["estimate", "mixture", "references", "sample_rate", "samples", "channels", "window_s", "hop_s",
+                 "metrics", "whole", "track_mean", "track_median", "active_windows", "windows", "track", "active",
+                 "spectral_metrics", "spectral_whole", "spectral_track", "spectral_track_mean", "spectral_track_median",
+                 "spatial_metrics", "spatial_whole", "spatial_track", "spatial_track_mean", "spatial_track_median", "spatial_cues",
+                 "itd_metrics", "itd_whole", "itd_track", "itd_track_mean", "itd_track_median", "itd_gcc",
+                 "stoi_metrics", "stoi_whole", "stoi_track", "stoi_track_mean", "stoi_track_median", "stoi_frames",
+                 "bss_taps", "bss_metrics", "bss_whole", "bss_track", "bss_track_mean", "bss_track_median",
+                 "align", "region", "lag", "lag_track"]
+
+
+def test_cli_every_family_at_once_is_the_summary_of_the_same_call(dev, tmp_path):
+    """score.py with every flag at once on int16 two-channel WAVs (the planted pair of tests/itd_ref.py, S = 2, L = 40001): every family
+    block of the JSON is summarize(Scorer.score(...)) of the same samples scored in this process, number for number (the kernels'
+    bits do not depend on the process); the JSON's keys come in their fixed order; the table's header and each family's appear once,
+    in the order table, spectral, spatial, itd, stoi, bss."""
+    import itd_ref
+    from m2h.audio.score import Scorer, summarize
+    S, L = 2, 40001
+    refs, est, mix = itd_ref.planted(0, L, S)
+    q = lambda a: np.clip(np.rint(np.asarray(a, np.float64) * 32768.0), -32768, 32767).astype(np.int16)      # noqa: E731
+    back = lambda a: a.astype(np.float32) * np.float32(1.0 / 32768.0)                                        # noqa: E731
+    p = {k: str(tmp_path / (k + ".wav")) for k in ("est", "mix", "ref0", "ref1")}
+    for k, v in (("est", est), ("mix", mix), ("ref0", refs[0]), ("ref1", refs[1])):
+        _write_wav(p[k], 16000, np.ascontiguousarray(q(v).T))
+    out_json = str(tmp_path / "scores.json")
+    cmd = [sys.executable, os.path.join(ROOT, "score.py"), "--estimate", p["est"], "--mixture", p["mix"], "--reference", p["ref0"], "--reference", p["ref1"],
+           "--align", "16", "--window", "2", "--hop", "1", "--spectral", "--spatial", "--itd", "--stoi", "--bss", "8", "--json", out_json]
+    run = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)       # (stdout alone: libraries may write to stderr)
+    assert run.returncode == 0, run.stdout + run.stderr
+    got = json.load(open(out_json))
+    assert list(got) == CLI_JSON_KEYS
+    ge, gr, gm = _gpu(dev, back(q(est))[None], back(q(refs))[None], back(q(mix))[None])
+    res = Scorer(dev).score(ge, gr, gm, target=0, window=2, hop=1, align=16, spectral=True, spatial=True, stoi=True, bss=8, itd=True)
+    s = summarize(res)
+    assert res["plan"]["M"] == 2 and got["windows"] == [list(w) for w in res["plan"]["samples"]] and got["bss_taps"] == 8
+    for prefix in ("", "spectral_", "spatial_", "itd_", "stoi_", "bss_"):
+        want = {prefix + "metrics": s[prefix + "metrics"], prefix + "track": res[prefix + "track"][0].tolist()}
+        want.update({prefix + k: s[prefix + k][0] for k in ("whole", "track_mean", "track_median")})
+        for key, value in want.items():
+            assert json.dumps(got[key]) == json.dumps(value), key
+    for key in ("spatial_cues", "itd_gcc", "stoi_frames", "active", "lag", "lag_track"):
+        assert json.dumps(got[key]) == json.dumps(res[key][0].tolist()), key
+    assert json.dumps(got["active_windows"]) == json.dumps(s["active_windows"][0])
+    heads = [ln[:8].rstrip() for ln in run.stdout.splitlines() if not ln.startswith(("left", "right", "binaural", "score.py:"))]
+    assert heads == ["channel", "spectral", "spatial", "itd us", "stoi", "bss 8"], run.stdout

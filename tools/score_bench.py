@@ -94,6 +94,19 @@ SEG = 16000
 COPY_RATE = 6.29e12
 
 
+def timed(fn, n):
+    """milliseconds per call of fn over n calls, between two HIP events on the current stream"""
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
 def torch_gram(refs, est, mix, step):
     """[R, C, J, N] sums and [R, C, J, N, N] products from torch, `step` recordings at a time (L a multiple of the tile)"""
     import torch
@@ -124,7 +137,7 @@ def run_case(case):
     sc = Scorer(dev)
     step = R if R * C * N * L * 8 <= (4 << 30) else 2
 
-    def timed_scorer():
+    def staged():
         marks = []
         sc._timing = marks
         torch.cuda.synchronize()
@@ -138,17 +151,6 @@ def run_case(case):
                 ms[name] += e0.elapsed_time(e1)
         return {k: v / reps for k, v in ms.items()}
 
-    def timed_torch():
-        n = max(1, reps // 5)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(n):
-            torch_gram(refs, est, mix, step)
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
-
     # warm-up of every shape, and the two Grams against each other
     res0 = sc.score(est, refs, mix)
     tiles = ops.score_gram(refs, est, mix, SEG)
@@ -160,9 +162,10 @@ def run_case(case):
     del ts, tp, want, tiles
     torch.cuda.synchronize()
 
-    before = timed_torch()
-    t = timed_scorer()
-    after = timed_torch()
+    yard = lambda: torch_gram(refs, est, mix, step)                                     # noqa: E731
+    before = timed(yard, max(1, reps // 5))
+    t = staged()
+    after = timed(yard, max(1, reps // 5))
     gram_bytes = R * C * N * L * 4 + R * C * (L // SEG) * (N + N * (N + 1) // 2) * 8
     total = t["score_gram"] + t["metrics"]
     rate = gram_bytes / (t["score_gram"] * 1e-3)
@@ -219,16 +222,6 @@ def run_spectral_case(case):
     sc, stft = Scorer(dev), STFT(dev)
     table = sc._spectral_table()
     base = mix if C == 2 else 0.5 * (mix[:, :1] + mix[:, 1:])
-
-    def timed(fn, n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
 
     kernel = lambda: ops.score_spectral(refs, est, mix, 0, table)                       # noqa: E731
     stored = lambda: stored_spectrum_sums(stft, refs[:, 0], est, base)                  # noqa: E731
@@ -295,16 +288,6 @@ def run_spatial_case(case):
     est = 0.8 * refs[:, 0] + 0.03 * torch.randn((R, C, L), device=dev, generator=g)
     sc, stft = Scorer(dev), STFT(dev)
     table = sc._spectral_table()
-
-    def timed(fn, n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
 
     kernel = lambda: ops.score_spatial(refs, est, mix, 0, table)                        # noqa: E731
     yardstick = lambda: ops.score_spectral(refs, est, mix, 0, table)                    # noqa: E731
@@ -387,16 +370,6 @@ def run_itd_case(case):
     k, i = np.arange(*ITD_BINS), np.arange(ITD_LAGS) - ITD_LAGS // 2
     ang = 2.0 * np.pi * ((k[:, None] * i[None, :]) % (1023 * ITD_UPSAMPLE)) / (1023 * ITD_UPSAMPLE)
     cs = torch.from_numpy(np.stack([np.cos(ang), np.sin(ang)])).to(dev)
-
-    def timed(fn, n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
 
     kernel = lambda: ops.score_itd(refs, est, mix, 0, table)                            # noqa: E731
     yardstick = lambda: ops.score_spatial(refs, est, mix, 0, table)                     # noqa: E731
@@ -504,16 +477,6 @@ def run_stoi_case(case):
     sp = SC.stoi_plan(plan)
     base = mix if C == 2 else 0.5 * (mix[:, :1] + mix[:, 1:])
 
-    def timed(fn, n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
-
     rtab = sc._stoi_ranges(plan, sp)
     resample = lambda: ops.stoi_resample(refs, est, mix, 0, table)                      # noqa: E731
     x10 = resample()
@@ -611,16 +574,6 @@ def run_bss_case(case):
     base = mix if C == 2 else 0.5 * (mix[:, :1] + mix[:, 1:])
     J = plan["J"]
 
-    def timed(fn, n):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
-
     def yard():
         rows = []
         for r in range(R):
@@ -701,18 +654,7 @@ def run_align_case(case, D):
             rows.append(torch.cat([c[..., nfft - D:], c[..., :D + 1]], dim=-1))
         return torch.cat(rows)
 
-    def timed_torch():
-        n = max(1, reps // 2)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(n):
-            torch_corr()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
-
-    def timed_scorer():
+    def staged():
         marks = []
         sc._timing = marks
         torch.cuda.synchronize()
@@ -730,9 +672,9 @@ def run_align_case(case, D):
     lag = res0["lag"]
     torch_lag = lags_from_corr(torch_corr().double())
     torch.cuda.synchronize()
-    before = timed_torch()
-    t = timed_scorer()
-    after = timed_torch()
+    before = timed(torch_corr, max(1, reps // 2))
+    t = staged()
+    after = timed(torch_corr, max(1, reps // 2))
     J = res0["plan"]["J"]
     flops = 3 * R * C * J * 2.5 * 32768 * 15
     total = sum(t.values())
